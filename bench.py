@@ -562,6 +562,32 @@ def dry_collectives(args):
         dist_.destroy_process_group()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, res):
+    """--dump-outputs DIR: what the timed path handed its caller in its last step -- the label image and every array of the result
+    dict -- as DIR/<name>.npy in float32 (labels and integer coordinates stay exact below 2^24), so that two builds can be compared
+    output for output.  Should the arrays exceed 64 MB in all (a tile larger than the default), each is cut to the same fixed, seeded
+    sample of its rows, and the row indices are written next to it as <name>_rows.npy (float64).  Returns {name: shape}."""
+    labels, d = res
+    arrays = {"labels": labels}
+    arrays.update(("res_" + k, v) for k, v in sorted(d.items()))
+    arrays = {k: np.ascontiguousarray(np.asarray(v), np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = 0.9 * DUMP_LIMIT_BYTES / total
+        for k in list(arrays):
+            a = arrays[k]
+            rows = np.sort(np.random.RandomState(0).choice(len(a), max(1, int(len(a) * frac)), replace=False)) if len(a) else np.zeros(0, np.int64)
+            arrays[k] = np.ascontiguousarray(a[rows])
+            arrays[k + "_rows"] = rows.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def guarded(fn, what):
     """(result, None) or (None, message): an extra leg that fails is reported in the JSON line instead of losing the whole line"""
     try:
@@ -600,6 +626,9 @@ def main():
                     help="skip the extra legs with the exact-f32 and the six-product bf16 convolution kernels")
     ap.add_argument("--dry-collectives", action="store_true",
                     help="CPU / gloo rehearsal of the sharded path's exchange with asserted byte counts per rank (no GPU, no bench line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the 2D tile leg, write what its last step returned (labels, coord, points, prob) as DIR/<name>.npy "
+                         "(float32, at most 64 MB; rank 0)")
     args = ap.parse_args()
     if args.dry_collectives:
         return dry_collectives(args)
@@ -643,6 +672,7 @@ def main():
     calibrate_heads(model, img if rank == 0 else torch.from_numpy(synth.s2d_nuclei_image(H, W, seed=0)).to(dev))
     macs = conv_macs_per_input_pixel(model.net, model.config)
     elapsed, net_ms, res, st = run_leg(model, img, args.steps, args.warmup, world, dist_)
+    dumped = dump_outputs(args.dump_outputs, res) if args.dump_outputs and rank == 0 else None
     # second number (SURVEY.md 8d defines the metric host-array-in): the same steps with the image handed over as a host numpy array,
     # i.e. including the 16.8 MB H2D copy (staged through page-locked memory, stardist_amd/utils.py to_device); `value` stays the
     # HBM-resident figure the bench contract asks for
@@ -761,6 +791,8 @@ def main():
             "value_host_input": (host_leg_dict(H * W, args.steps, host2d[0], host2d[1], "Mpix/s", ms_per_step) if host2d is not None
                                  else {"value": None, "error": host2d_err}),
         }
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "leg": "2D tile, last timed step", "dtype": "float32", "arrays": dumped}
         if not args.no_cpu_baseline and world == 1:      # reported baseline: rank 0 at N=1 only
             try:
                 out["cpu_baseline"] = cpu_baseline_2d(img_np, model, min(args.cpu_sample, H), threads)

@@ -187,23 +187,30 @@ def test_a_converted_npz_stands_for_its_keras_file_only_while_it_is_not_older(tm
     assert loaded == ["weights_best.npz", "weights_best.h5"]
 
 
+# SHA-256 of dtype.str + shape + bytes of the reference's stardist/data/images/*.tif, every page decoded with Pillow (what the reference's
+# accessors read with tifffile / imageio)
+REFERENCE_IMAGE_SHA256 = {
+    "img2d.tif": "ce5fd80ee4e2f4c6107544f0ef37a9d090961707ddf8f17cc408a19001ec0f9a",
+    "mask2d.tif": "688518d997585f40a4c50ad6caf5cb28056a1170fa230ff3fe5aa61da7172c7d",
+    "img3d.tif": "8187864d6b23b3be71c45e16e8e820613c20deda91a1ca9d81abb7063921842a",
+    "mask3d.tif": "a223083829db4d5f526ccf300b57fe097f242ac785252e7d8084367cf3d4fdb6",
+}
+
+
+def _array_sha256(a):
+    import hashlib
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(("%s%s" % (a.dtype.str, a.shape)).encode() + a.tobytes()).hexdigest()
+
+
 def test_sample_image_accessors_return_the_reference_images():
-    """stardist/data/__init__.py:7-39: the arrays the reference's accessors read with tifffile / imageio (here: Pillow on the reference's files,
-    build container only) == what stardist_amd.data serves from its images.npz"""
+    """stardist/data/__init__.py:7-39: the arrays the reference's accessors read with tifffile / imageio == what stardist_amd.data serves
+    from its images.npz (dtype, shape and every value, through the stored digests of the reference's files)"""
     from stardist_amd.data import test_image_he_2d, test_image_nuclei_2d, test_image_nuclei_3d
     img, mask = test_image_nuclei_2d(return_mask=True)
     assert img.shape == mask.shape == (512, 512) and test_image_nuclei_2d().shape == (512, 512)
     v, vm = test_image_nuclei_3d(return_mask=True)
     assert v.shape == vm.shape == (31, 61, 57) and int(vm.max()) > 10
     assert test_image_he_2d().shape == (300, 500, 3) and test_image_he_2d().dtype == np.uint8
-    src = "/root/reference/stardist/data/images"
-    if os.path.isdir(src):
-        from PIL import Image
-
-        def read(p):
-            im = Image.open(p); pages = []
-            for k in range(getattr(im, "n_frames", 1)):
-                im.seek(k); pages.append(np.array(im))
-            return pages[0] if len(pages) == 1 else np.stack(pages)
-        assert np.array_equal(img, read(os.path.join(src, "img2d.tif"))) and np.array_equal(mask, read(os.path.join(src, "mask2d.tif")))
-        assert np.array_equal(v, read(os.path.join(src, "img3d.tif"))) and np.array_equal(vm, read(os.path.join(src, "mask3d.tif")))
+    served = {"img2d.tif": img, "mask2d.tif": mask, "img3d.tif": v, "mask3d.tif": vm}
+    assert {k: _array_sha256(a) for k, a in served.items()} == REFERENCE_IMAGE_SHA256

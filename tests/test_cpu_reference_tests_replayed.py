@@ -23,7 +23,7 @@ import numpy as np
 import pytest
 
 REF_TESTS = "/root/reference/tests"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_TESTS), reason="needs the reference sources (build container only)")
+needs_ref = pytest.mark.skipif(not os.path.isdir(REF_TESTS), reason="needs the reference sources (build container only)")
 f32, i32 = (lambda a: np.ascontiguousarray(a, np.float32)), (lambda a: np.ascontiguousarray(a, np.int32))
 
 
@@ -169,35 +169,41 @@ def _replay(module_name, skip=()):
     return ran, skipped
 
 
+@needs_ref
 def test_reference_test_stardist2D_runs_against_this_package(as_stardist):
     ran, skipped = _replay("test_stardist2D")
     assert ran == {"test_types": 6, "test_relabel_consistency": 4, "test_grid": 4}, (ran, skipped)
     assert set(skipped) == {"test_types_gpu", "test_cpu_gpu"}
 
 
+@needs_ref
 def test_reference_test_stardist3D_runs_against_this_package(as_stardist):
     ran, skipped = _replay("test_stardist3D")
     assert ran == {"test_types": 12, "test_relabel_consistency": 4, "test_grid": 4}, (ran, skipped)
     assert set(skipped) == {"test_types_gpu", "test_cpu_gpu"}
 
 
+@needs_ref
 def test_reference_test_nms2D_runs_against_this_package(as_stardist):
     ran, skipped = _replay("test_nms2D", skip={"test_speed": "prints timings only", "test_large": "2000 x 2007 smoke run: minutes on the CPU natives"})
     assert ran == {"test_bbox_search_old": 2, "test_old_new": 8, "test_acc": 2, "test_acc_old": 2}, (ran, skipped)       # test_acc*: matching accuracy > 0.9
     assert set(skipped) == {"test_speed", "test_large"}
 
 
+@needs_ref
 def test_reference_test_nms3D_runs_against_this_package(as_stardist):
     ran, skipped = _replay("test_nms3D", skip={"test_speed": "prints timings only", "test_rays_volume_area": "needs skimage.measure.regionprops; prints only"})
     assert ran == {"test_nms": 4, "test_label": 1, "test_nms_kdtree": 1, "test_nms_accuracy": 12}, (ran, skipped)
 
 
+@needs_ref
 def test_reference_test_big_runs_against_this_package(as_stardist):
     ran, skipped = _replay("test_big")
     assert ran == {"test_cover2D": 18, "test_cover3D": 6, "test_edgecases": 1}, (ran, skipped)
     assert set(skipped) == {"test_predict2D", "test_predict3D", "test_polygon_order_2D", "test_polyhedron_order_3D"}
 
 
+@needs_ref
 def test_polygon_and_polyhedron_helpers_equal_the_reference_classes(as_stardist):
     """stardist.big.Polygon / Polyhedron (big.py:452-498) -- bbox, slice, shape, relative coordinates, mask, the common box of several
     objects, clipping to the image -- against the reference's own classes (rasterisers: the same stand-ins on both sides)"""
@@ -244,6 +250,7 @@ def test_predict_big_tells_where_the_function_moved():
         predict_big(m, None)
 
 
+@needs_ref
 def test_reference_test_matching_runs_against_this_package(as_stardist):
     """tests/test_matching.py: matching on shifted discs, _shuffle_labels and group_matching_labels on the package's sample mask with the
     reference's own expected label maxima [183, 199, 215, 231, 247, 263]"""

@@ -441,6 +441,17 @@ int sd_convg_ndhwc_device(const float* d_src, int c_in, int src_stride, int D, i
                           int sx, int pz, int py, int px, int Do, int Ho, int Wo, const float* d_wpacked, const float* d_bias,
                           const float* d_res, int res_stride, int c_out, int act, float* d_out, int out_stride, void* stream);
 
+/* ---- evaluation: sparse overlap of two label images (stardist/matching.py:45-52 without the dense matrix) ------------------
+ * d_true, d_pred: two int32 label images of n elements each (2D or 3D, flattened in the same order).  Result: every pair (t, p) != (0, 0)
+ * of labels that share at least one pixel, ascending by (t, p), as d_keys[i] = t << 32 | p (original ids, no relabelling) and
+ * d_counts[i] = its number of pixels.  Buffer protocol: capacity plus real count -- *h_count (host) receives the number of pairs, the
+ * first min(*h_count, cap) of them are written; a caller whose cap was too small calls again with cap >= *h_count (cap = 0 with NULL
+ * buffers is a pure count query).  h_minmax (host, 4 ints) receives {min, max} of d_true, then of d_pred ({0, 0, 0, 0} for n = 0); if
+ * either minimum is negative nothing else is computed and *h_count = 0.  Integer arithmetic only: the list is bit-identical from call
+ * to call.  Synchronises the stream (the number of runs sizes the sort).  At most 2^31 - 1 runs of equal (t, p). */
+int sd_label_overlap_device(const int32_t* d_true, const int32_t* d_pred, long long n, long long cap, int64_t* d_keys, int64_t* d_counts,
+                            long long* h_count, int32_t* h_minmax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

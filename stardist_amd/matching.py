@@ -148,25 +148,20 @@ _METRIC_KEYS = ("criterion", "thresh", "fp", "tp", "fn", "precision", "recall", 
                 "mean_matched_score", "panoptic_quality")
 
 
-def matching(y_true, y_pred, thresh=0.5, criterion="iou", report_matches=False):
-    """Detection metrics between a ground-truth and a predicted label image (matching.py:109-230): objects are paired one to one by an
-    optimal assignment that maximises the number of pairs whose score reaches `thresh` (the scores break ties); tp / fp / fn, precision,
-    recall, accuracy, f1, mean scores and panoptic quality come back as a namedtuple `Matching` (a tuple of them for a sequence of
-    thresholds).  report_matches adds matched_pairs (original label ids), matched_scores and matched_tps."""
+def _matching_vals(criterion, thr, tp, total, n_true, n_pred):
+    """the fields of Matching from the counts and the matched-score sum (matching.py:185-200): shared by the host path and the sparse
+    finishing of the device path (stardist_amd.matching_sparse)"""
+    fp, fn = n_pred - tp, n_true - tp
+    return dict(criterion=criterion, thresh=thr, fp=fp, tp=tp, fn=fn, precision=precision(tp, fp, fn), recall=recall(tp, fp, fn),
+                accuracy=accuracy(tp, fp, fn), f1=f1(tp, fp, fn), n_true=n_true, n_pred=n_pred, mean_true_score=_safe_divide(total, n_true),
+                mean_matched_score=_safe_divide(total, tp), panoptic_quality=_safe_divide(total, tp + fp / 2 + fn / 2))
+
+
+def _matching_dense(overlap, back_true, back_pred, thresh, criterion, report_matches):
+    """matching() behind the relabelling: overlap = label_overlap of the relabelled images, back_* = their inverse maps"""
     from collections import namedtuple
     from scipy.optimize import linear_sum_assignment
-    _check_label_array(y_true, "y_true")
-    _check_label_array(y_pred, "y_pred")
-    if y_true.shape != y_pred.shape:
-        raise ValueError("y_true (%s) and y_pred (%s) have different shapes" % (y_true.shape, y_pred.shape))
-    if criterion not in matching_criteria:
-        raise ValueError("Matching criterion '%s' not supported." % criterion)
-    if thresh is None:
-        thresh = 0
-    thresh = float(thresh) if np.isscalar(thresh) else [float(t) for t in thresh]
-    y_true, _, back_true = relabel_sequential(y_true)
-    y_pred, _, back_pred = relabel_sequential(y_pred)
-    scores = matching_criteria[criterion](label_overlap(y_true, y_pred, check=False))
+    scores = matching_criteria[criterion](overlap)
     assert 0 <= np.min(scores) <= np.max(scores) <= 1
     scores = scores[1:, 1:]                                           # without the background row / column
     n_true, n_pred = scores.shape
@@ -181,10 +176,7 @@ def matching(y_true, y_pred, thresh=0.5, criterion="iou", report_matches=False):
             ok = scores[ti, pi] >= thr
             tp = int(np.count_nonzero(ok))
             total = np.sum(scores[ti, pi][ok])
-        fp, fn = n_pred - tp, n_true - tp
-        vals = dict(criterion=criterion, thresh=thr, fp=fp, tp=tp, fn=fn, precision=precision(tp, fp, fn), recall=recall(tp, fp, fn),
-                    accuracy=accuracy(tp, fp, fn), f1=f1(tp, fp, fn), n_true=n_true, n_pred=n_pred, mean_true_score=_safe_divide(total, n_true),
-                    mean_matched_score=_safe_divide(total, tp), panoptic_quality=_safe_divide(total, tp + fp / 2 + fn / 2))
+        vals = _matching_vals(criterion, thr, tp, total, n_true, n_pred)
         if bool(report_matches):
             if n_matched > 0:
                 vals.update(matched_pairs=tuple((int(back_true[i]), int(back_pred[j])) for i, j in zip(1 + ti, 1 + pi)),
@@ -195,13 +187,42 @@ def matching(y_true, y_pred, thresh=0.5, criterion="iou", report_matches=False):
     return at(thresh) if np.isscalar(thresh) else tuple(at(t) for t in thresh)
 
 
-def matching_dataset_lazy(y_gen, thresh=0.5, criterion="iou", by_image=False, show_progress=True, parallel=False):
+def matching(y_true, y_pred, thresh=0.5, criterion="iou", report_matches=False, *, device=None):
+    """Detection metrics between a ground-truth and a predicted label image (matching.py:109-230): objects are paired one to one by an
+    optimal assignment that maximises the number of pairs whose score reaches `thresh` (the scores break ties); tp / fp / fn, precision,
+    recall, accuracy, f1, mean scores and panoptic quality come back as a namedtuple `Matching` (a tuple of them for a sequence of
+    thresholds).  report_matches adds matched_pairs (original label ids), matched_scores and matched_tps.
+    Label images that are torch tensors on a HIP device -- or any input when `device` names one -- are evaluated on the device
+    (stardist_amd.matching_sparse.matching_device: sparse overlap kernel, exact host finishing); numpy inputs without `device` stay here."""
+    if device is not None or _on_device(y_true) or _on_device(y_pred):
+        from .matching_sparse import matching_device
+        return matching_device(y_true, y_pred, thresh=thresh, criterion=criterion, report_matches=report_matches, device=device)
+    _check_label_array(y_true, "y_true")
+    _check_label_array(y_pred, "y_pred")
+    if y_true.shape != y_pred.shape:
+        raise ValueError("y_true (%s) and y_pred (%s) have different shapes" % (y_true.shape, y_pred.shape))
+    if criterion not in matching_criteria:
+        raise ValueError("Matching criterion '%s' not supported." % criterion)
+    if thresh is None:
+        thresh = 0
+    thresh = float(thresh) if np.isscalar(thresh) else [float(t) for t in thresh]
+    y_true, _, back_true = relabel_sequential(y_true)
+    y_pred, _, back_pred = relabel_sequential(y_pred)
+    return _matching_dense(label_overlap(y_true, y_pred, check=False), back_true, back_pred, thresh, criterion, report_matches)
+
+
+def _on_device(y):
+    return N.is_torch(y) and y.is_cuda
+
+
+def matching_dataset_lazy(y_gen, thresh=0.5, criterion="iou", by_image=False, show_progress=True, parallel=False, *, device=None):
     """matching() over (y_true, y_pred) pairs, accumulated per threshold: counts are summed, the derived metrics recomputed from the
-    sums -- or, with by_image, averaged over the images (matching.py:244-315).  show_progress is accepted and ignored (no progress bar)."""
+    sums -- or, with by_image, averaged over the images (matching.py:244-315).  show_progress is accepted and ignored (no progress bar).
+    device: passed on to matching() (pairs of device tensors take the device path by themselves)."""
     from collections import namedtuple
     single = np.isscalar(thresh)
     threshs = (thresh,) if single else tuple(thresh)
-    run = lambda pair: matching(pair[0], pair[1], thresh=threshs, criterion=criterion, report_matches=False)
+    run = lambda pair: matching(pair[0], pair[1], thresh=threshs, criterion=criterion, report_matches=False, device=device)
     if parallel:
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor() as pool:
@@ -235,11 +256,12 @@ def matching_dataset_lazy(y_gen, thresh=0.5, criterion="iou", by_image=False, sh
     return out[0] if single else tuple(out)
 
 
-def matching_dataset(y_true, y_pred, thresh=0.5, criterion="iou", by_image=False, show_progress=True, parallel=False):
-    """matching.py:234-241"""
+def matching_dataset(y_true, y_pred, thresh=0.5, criterion="iou", by_image=False, show_progress=True, parallel=False, *, device=None):
+    """matching.py:234-241 (device: see matching_dataset_lazy)"""
     if len(y_true) != len(y_pred):
         raise ValueError("y_true and y_pred must have the same length.")
-    return matching_dataset_lazy(tuple(zip(y_true, y_pred)), thresh=thresh, criterion=criterion, by_image=by_image, show_progress=show_progress, parallel=parallel)
+    return matching_dataset_lazy(tuple(zip(y_true, y_pred)), thresh=thresh, criterion=criterion, by_image=by_image, show_progress=show_progress,
+                                 parallel=parallel, device=device)
 
 
 def _objects(y):

@@ -228,6 +228,15 @@ class StarDistBase(object):
                 json.dump({k: float(v) for k, v in opt_threshs.items()}, fh)      # (numpy 2 keeps the search in float32: not serialisable as it is)
         return opt_threshs
 
+    def _labels_device(self, img_shape, prob, dist, prob_thresh=None, nms_thresh=None):
+        """the label image of _instances_from_prediction(img_shape, prob, dist, prob_thresh=..., nms_thresh=...) as an int32 tensor on
+        self.device: what optimize_threshold evaluates with the device matching (stardist_amd.matching_sparse) when a model offers it"""
+        import torch
+        labels = self._instances_from_prediction(img_shape, prob, dist, prob_thresh=prob_thresh, nms_thresh=nms_thresh)[0]
+        if torch.is_tensor(labels):
+            return labels.to(device=self.device, dtype=torch.int32)
+        return torch.from_numpy(np.ascontiguousarray(labels, np.int32)).to(self.device)
+
     def _find_and_load_weights(self, prefer="best"):
         """csbdeep BaseModel._find_and_load_weights: of the weight files in the model folder (*.h5 / *.hdf5 Keras files, and the *.npz this
         package converts them to: tools/keras_to_npz.py, save_weights_npz) the newest one whose name contains `prefer`, else the newest"""

@@ -250,7 +250,9 @@ def optimize_threshold(Y, Yhat, model, nms_thresh, measure="accuracy", iou_thres
     """Tune prob_thresh for a fixed nms_thresh so that `measure` of stardist.matching (averaged over iou_threshs) between the label images Y
     and the instances of the predictions Yhat = [(prob, dist), ...] is largest: golden-section search over [max prob / 2, max prob]
     (stardist/utils.py:271-307).  Returns (prob_thresh, value).  Host-side tool: every evaluation is one `_instances_from_prediction` per
-    image (NMS + rasteriser natives).  verbose > 1 prints every evaluation; the reference's progress bar is not drawn."""
+    image (NMS + rasteriser natives).  verbose > 1 prints every evaluation; the reference's progress bar is not drawn.  A model on a HIP
+    device with the private hook _labels_device (StarDist2D / StarDist3D) is evaluated with the device matching; other objects take the
+    host path with the reference's calls."""
     import datetime
     from scipy.optimize import minimize_scalar
     from .matching import matching_dataset
@@ -261,11 +263,22 @@ def optimize_threshold(Y, Yhat, model, nms_thresh, measure="accuracy", iou_thres
         top = max([np.max(prob) for prob, dist in Yhat])
         bracket = top / 2, top
     seen = {}
+    on_device = callable(getattr(model, "_labels_device", None)) and getattr(model, "device", None) is not None and \
+        getattr(model.device, "type", None) == "cuda"
+    if on_device:
+        # the model renders its label images on its device: the matching runs there too (stardist_amd.matching_sparse, same results as
+        # the host's for thresholds > 0), Y uploaded once
+        from .matching_sparse import _to_device_int32
+        Y_eval = [_to_device_int32(y, "y_true", model.device) for y in Y]
 
     def negative_score(thr):
         prob_thresh = np.clip(thr, *bracket)
         value = seen.get(prob_thresh)
-        if value is None:
+        if value is None and on_device:
+            instances = [model._labels_device(y.shape, *prob_dist, prob_thresh=prob_thresh, nms_thresh=nms_thresh) for y, prob_dist in zip(Y, Yhat)]
+            stats = matching_dataset(Y_eval, instances, thresh=iou_threshs, show_progress=False, parallel=False)
+            seen[prob_thresh] = value = np.mean([s._asdict()[measure] for s in stats])
+        elif value is None:
             instances = [model._instances_from_prediction(y.shape, *prob_dist, prob_thresh=prob_thresh, nms_thresh=nms_thresh)[0] for y, prob_dist in zip(Y, Yhat)]
             stats = matching_dataset(Y, instances, thresh=iou_threshs, show_progress=False, parallel=True)
             seen[prob_thresh] = value = np.mean([s._asdict()[measure] for s in stats])

@@ -452,6 +452,39 @@ int sd_convg_ndhwc_device(const float* d_src, int c_in, int src_stride, int D, i
 int sd_label_overlap_device(const int32_t* d_true, const int32_t* d_pred, long long n, long long cap, int64_t* d_keys, int64_t* d_counts,
                             long long* h_count, int32_t* h_minmax, void* stream);
 
+/* ---- training (2D): backward pass and losses (csrc/train2d.hip) ---------------------------------------------------------------
+ * The reference trains its Keras model with StarDist2D.train (stardist/models/model2d.py) on the losses of base.py:34-60, 315-325; these
+ * entry points are the pieces of that step the forward kernels above do not cover.  Channels-last float32, batch B (2D: [B][H][W][C]).
+ *
+ * sd_conv_wgrad_ndhwc_device: weight and bias gradient of a 'same' k x k convolution (k = 3, or k = 1 with one full-resolution source)
+ *     dW[co][ci][ky][kx] = sum_{b,y,x} g[b][y][x][co] * in[b][y+ky-1][x+kx-1][ci]      (k = 1: in[b][y][x][ci]; zero padding)
+ *     db[co] = sum g[..][co]   (d_db may be NULL)
+ * with in = [src0 (c0 channels) | src1 (c1 channels)] and the forward kernels' `up` bit masks (1: x, 2: y: the source has half the
+ * resolution and is read through nearest up-sampling).  Any channel counts (c_in = 1 included).  Exact f32 products on the matrix cores;
+ * the pixels are split into chunks that depend on the shape only, the chunk partials are added in chunk order in float64: repeatable bit
+ * for bit.  d_dw is [c_out][c0 + c1][k][k] (the torch layout).
+ * sd_relu_mask_device: out = y > 0 ? dy : 0 (the ReLU adjoint from the saved post-activation output y).
+ * sd_maxpool_adjoint_ndhwc_device: adjoint of sd_maxpool_ndhwc_device (pool py x px, stride = pool, 'valid'): each window's gradient goes
+ * to its first maximum in scan order (y, then x), everything else is zero.  d_in = the pooling's input [B][H][W][C], d_gout [B][H/py][W/px][C].
+ * sd_upcat_adjoint_ndhwc_device: adjoint of [UpSampling(src0) | src1]: d_gcat [B][H][W][c0 + c1] -> d_g1 = its last c1 channels
+ * [B][H][W][c1], d_g0 [B][H >> y][W >> x][c0] = the sum over each up-sampling window (order dy, then dx) of its first c0 channels.
+ * sd_stardist_loss2d_device: the 2D model's losses and their gradients over n_pix pixels (batch and space flattened):
+ *     prob_loss = mean over pixels with prob_true >= 0 of -(t log(pc + e) + (1 - t) log(1 - pc + e)),  pc = clip(prob, e, 1 - e), e = 1e-7
+ *     dist_loss = mean over pixels of  mean_r(m * pen(t_r - d_r)) / (mean(m) + e) + reg * mean_r((1 - m) |d_r|)
+ * (m = the last channel of d_dist_true_mask [n_pix][n_rays + 1]; pen = |.| for dist_loss 0 (mae), square for 1 (mse)); d_losses (device,
+ * 3 doubles) = {prob_loss, dist_loss, w_prob * prob_loss + w_dist * dist_loss}; d_grad_logit [n_pix] = d total / d (logit of prob)
+ * (zero where prob is clipped or masked), d_grad_dist [n_pix][n_rays] = d total / d dist; both NULL: the losses only (evaluation without
+ * a backward pass).  float64 sums in a fixed order. */
+int sd_conv_wgrad_ndhwc_device(const float* d_g, int c_out, const float* d_src0, int c0, int up0, const float* d_src1, int c1, int up1,
+                               int B, int H, int W, int k, float* d_dw, float* d_db, void* stream);
+int sd_relu_mask_device(const float* d_dy, const float* d_y, long long n, float* d_out, void* stream);
+int sd_maxpool_adjoint_ndhwc_device(const float* d_in, const float* d_gout, int n_channels, int B, int H, int W, int py, int px,
+                                    float* d_gin, void* stream);
+int sd_upcat_adjoint_ndhwc_device(const float* d_gcat, int c0, int up0, int c1, int B, int H, int W, float* d_g0, float* d_g1, void* stream);
+int sd_stardist_loss2d_device(const float* d_prob, const float* d_dist, const float* d_prob_true, const float* d_dist_true_mask,
+                              long long n_pix, int n_rays, int dist_loss, double w_prob, double w_dist, double background_reg,
+                              double* d_losses, float* d_grad_logit, float* d_grad_dist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,12 @@ SIGNATURES = {
     "sd_split16_pack_device": (_i, [_vp, ctypes.c_longlong, _i, _vp, _vp, _vp]),
     "sd_split16_unpack_device": (_i, [_vp, ctypes.c_longlong, _i, _vp, _vp]),
     "sd_label_overlap_device": (_i, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp]),
+    "sd_conv_wgrad_ndhwc_device": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sd_relu_mask_device": (_i, [_vp, _vp, ctypes.c_longlong, _vp, _vp]),
+    "sd_maxpool_adjoint_ndhwc_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sd_upcat_adjoint_ndhwc_device": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sd_stardist_loss2d_device": (_i, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                       _vp, _vp, _vp, _vp]),
     "_LIB_non_maximum_suppression_2d": (None, [_vp, _vp, _i, _i, _f, _i, _i, _i, _vp]),
     "_LIB_polygon_to_label": (None, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "_LIB_star_dist": (None, [_vp, _i, _i, _i, _i, _i, _vp]),

@@ -128,6 +128,20 @@ class StarDist2D(StarDistBase):
         r = non_maximum_suppression_sparse(dist, prob, points, nms_thresh=nms_thresh, **nms_kwargs)
         return r[0], r[1], r[2], r[3]
 
+    def train(self, X, Y, validation_data, classes="auto", augmenter=None, seed=None, epochs=None, steps_per_epoch=None, workers=1):
+        """model2d.py train on the library's own kernels (stardist_amd/training.py): U-Net backbone, one input channel, single class,
+        'mae' / 'mse' distance loss, no shape completion -- any other configuration raises NotImplementedError naming the setting.
+        X: input images (2D, no channel axis), Y: label images (negative values switch the losses off there), validation_data: (X_val,
+        Y_val).  With a model folder, weights_best.npz / weights_last.npz are written there and the best weights are loaded at the end.
+        classes: single-class models only, so anything but 'auto' / None is ignored with the reference's warning; workers: accepted for the
+        reference's signature, the host part of the data pipeline runs in the calling thread.
+        Returns the history dict (per epoch: loss, prob_loss, dist_loss, val_loss, val_prob_loss, val_dist_loss, lr)."""
+        import warnings
+        from ..training import train
+        if classes not in ("auto", None):
+            warnings.warn("Ignoring given classes as n_classes is set to None")
+        return train(self, X, Y, validation_data, augmenter=augmenter, seed=seed, epochs=epochs, steps_per_epoch=steps_per_epoch)
+
     def _axes_div_by(self, query_axes):
         """model2d.py:566-574"""
         query_axes = axes_check_and_normalize(query_axes)

@@ -1,0 +1,620 @@
+"""StarDist2D training on the library's own kernels (the reference's StarDist2D.train, stardist/models/model2d.py, with the losses of
+stardist/models/base.py:34-60, 315-325 and the data generator StarDistData2D without shape completion).
+
+  patches      sample_patches / get_valid_inds (stardist/sample_patches.py), StarDistDataBase.get_valid_inds (base.py:129-224) and
+               csbdeep's RollingSequence.batch / utils.choice, restated with the same np.random draws in the same order: np.random.seed(s)
+               gives the reference's patches.  The augmenter runs on the host, as there.
+  targets      one upload of the batch's label patches; prob (edt_prob of the grid-subsampled labels) and dist (star_dist with the grid) on
+               the device by sd_edt_prob_device / sd_star_dist2d_device: equal to stardist_targets() bit for bit.
+  forward      the exact-f32 kernels of inference (sd_conv3_ndhwc_device per sample, sd_maxpool_ndhwc_device and the 1x1 heads on
+               sd_convg_ndhwc_device with the batch on the depth axis) over the parameters of the model's StarDistNet; inference
+               itself (StarDistBase._net_forward) is not involved.
+  backward     csrc/train2d.hip: weight / bias gradients (sd_conv_wgrad_ndhwc_device), ReLU / max-pool / up-sampling adjoints; the data
+               gradient of a 3x3 layer is the forward kernel on the flipped, transposed kernel.
+  loss         sd_stardist_loss2d_device: both losses and their gradients in one call.
+  optimiser    Keras' Adam (epsilon 1e-7) and ReduceLROnPlateau on val_loss, as torch element-wise updates.
+Scope: U-Net backbone, one input channel, no classes, no batch norm / dropout, 'mae' / 'mse' distance loss, no shape completion;
+check_trainable() names the first setting outside it."""
+import ctypes
+import math
+import random
+import threading
+import warnings
+
+import numpy as np
+import torch
+
+from .lib import _native as N
+
+
+# ---- patch sampling ------------------------------------------------------------------------------------------------------------
+def choice(population, k=1, replace=True):
+    """csbdeep.utils.choice: python's `random`, seeded from np.random (one draw), its own state restored afterwards"""
+    state = random.getstate()
+    try:
+        random.seed(np.random.randint(np.iinfo(int).min, np.iinfo(int).max))
+        return random.choices(population, k=k) if replace else random.sample(population, k=k)
+    finally:
+        random.setstate(state)
+
+
+def sample_patches(datas, patch_size, n_samples, valid_inds=None):
+    """stardist/sample_patches.py sample_patches: n_samples patches of every array in `datas` at the same random centres"""
+    if len(patch_size) != datas[0].ndim:
+        raise ValueError()
+    if not all(a.shape == datas[0].shape for a in datas):
+        raise ValueError("all input shapes must be the same: %s" % (" / ".join(str(a.shape) for a in datas)))
+    if not all(0 < s <= d for s, d in zip(patch_size, datas[0].shape)):
+        raise ValueError("patch_size %s negative or larger than data shape %s along some dimensions" % (str(patch_size), str(datas[0].shape)))
+    if valid_inds is None:
+        valid_inds = tuple(_s.ravel() for _s in np.meshgrid(*tuple(np.arange(p // 2, s - p // 2 + 1) for s, p in zip(datas[0].shape, patch_size))))
+    n_valid = len(valid_inds[0])
+    if n_valid == 0:
+        raise ValueError("no regions to sample from!")
+    idx = choice(range(n_valid), n_samples, replace=(n_valid < n_samples))
+    rand_inds = [v[idx] for v in valid_inds]
+    return [np.stack([data[tuple(slice(_r - (_p // 2), _r + _p - (_p // 2)) for _r, _p in zip(r, patch_size))] for r in zip(*rand_inds)])
+            for data in datas]
+
+
+def get_valid_inds(img, patch_size, patch_filter=None):
+    """stardist/sample_patches.py get_valid_inds: the centres of patches inside the image (and inside patch_filter's mask)"""
+    if len(patch_size) != img.ndim:
+        raise ValueError()
+    if not all(0 < s <= d for s, d in zip(patch_size, img.shape)):
+        raise ValueError("patch_size %s negative or larger than image shape %s along some dimensions" % (str(patch_size), str(img.shape)))
+    if patch_filter is None:
+        valid_inds = tuple(np.arange(p // 2, s - p + p // 2 + 1).astype(np.uint32) for p, s in zip(patch_size, img.shape))
+        return tuple(s.ravel() for s in np.meshgrid(*valid_inds, indexing="ij"))
+    patch_mask = patch_filter(img, patch_size)
+    border_slices = tuple(slice(p // 2, s - p + p // 2 + 1) for p, s in zip(patch_size, img.shape))
+    valid_inds = np.where(patch_mask[border_slices])
+    return tuple((v + s.start).astype(np.uint32) for s, v in zip(border_slices, valid_inds))
+
+
+def grid_divisible_patch_size(patch_size, grid):
+    """stardist/utils.py grid_divisible_patch_size"""
+    patch_size, grid = tuple(patch_size), tuple(grid)
+    div = tuple(int(np.ceil(sh / g) * g) for sh, g in zip(patch_size, grid))
+    if div != patch_size:
+        warnings.warn("increasing patch_size from %s to %s, since it was not evenly divisible by grid %s" % (patch_size, div, grid))
+    return div
+
+
+class TrainData2D(object):
+    """StarDistData2D (shape_completion=False) on top of csbdeep's RollingSequence: sample(i) is what its __getitem__(i) draws (image and
+    label patches after the augmenter), batch_device(i) adds the targets, computed on the device"""
+
+    def __init__(self, X, Y, batch_size, n_rays, length, patch_size=(256, 256), grid=(1, 1), augmenter=None, foreground_prob=0,
+                 sample_ind_cache=True, maxfilter_patch_size=None):
+        X = [np.asarray(x).astype(np.float32, copy=False) for x in X]
+        if not (len(X) == len(Y) and len(X) > 0):
+            raise ValueError("X and Y can't be empty and must have same length")
+        self.data_size, self.batch_size = len(X), int(batch_size)
+        self.length = 2 ** 63 - 1 if length is None else int(length)
+        self.index_map = {}
+        patch_size = grid_divisible_patch_size(patch_size, grid)
+        if len(patch_size) != 2 or X[0].ndim != 2:
+            raise ValueError("2D images with one channel (no channel axis) expected")
+        Y = [np.asarray(y) for y in Y]
+        if not all(y.ndim == 2 and x.ndim == 2 and x.shape == y.shape for x, y in zip(X, Y)):
+            raise ValueError("images and masks should have corresponding shapes/dimensions")
+        if not all(x.shape >= tuple(patch_size) for x in X):
+            raise ValueError("Some images are too small for given patch_size {patch_size}".format(patch_size=patch_size))
+        if not 0 <= foreground_prob <= 1:
+            raise ValueError("foreground_prob must lie in [0, 1]")
+        if augmenter is None:
+            augmenter = lambda *args: args
+        if not callable(augmenter):
+            raise ValueError("augmenter must be None or callable")
+        self.X, self.Y, self.n_rays, self.grid = X, Y, int(n_rays), tuple(int(g) for g in grid)
+        self.patch_size, self.augmenter, self.foreground_prob = patch_size, augmenter, foreground_prob
+        self.maxfilter_patch_size = maxfilter_patch_size if maxfilter_patch_size is not None else self.patch_size
+        self.sample_ind_cache = sample_ind_cache
+        self._ind_cache_fg, self._ind_cache_all = {}, {}
+        self.lock = threading.Lock()
+
+    def __len__(self):
+        return self.length
+
+    # csbdeep RollingSequence
+    def _index(self, loop):
+        if loop not in self.index_map:
+            self.index_map[loop] = np.random.permutation(self.data_size)
+        return self.index_map[loop]
+
+    def batch(self, i):
+        pos = i * self.batch_size
+        loop, pos_loop = pos // self.data_size, pos % self.data_size
+        sl = slice(pos_loop, pos_loop + self.batch_size)
+        index = self._index(loop)
+        _loop = loop
+        while sl.stop > len(index):
+            _loop += 1
+            index = np.concatenate((index, self._index(_loop)))
+        return index[sl]
+
+    def max_filter(self, y, patch_size):
+        from scipy.ndimage import maximum_filter
+        return maximum_filter(y, patch_size, mode="constant")
+
+    # StarDistDataBase.get_valid_inds
+    def get_valid_inds(self, k, foreground_prob=None):
+        if foreground_prob is None:
+            foreground_prob = self.foreground_prob
+        foreground_only = np.random.uniform() < foreground_prob
+        _ind_cache = self._ind_cache_fg if foreground_only else self._ind_cache_all
+        if k in _ind_cache:
+            inds = _ind_cache[k]
+        else:
+            patch_filter = (lambda y, p: self.max_filter(y, self.maxfilter_patch_size) > 0) if foreground_only else None
+            inds = get_valid_inds(self.Y[k], self.patch_size, patch_filter=patch_filter)
+            if self.sample_ind_cache:
+                with self.lock:
+                    _ind_cache[k] = inds
+        if foreground_only and len(inds[0]) == 0:
+            return self.get_valid_inds(k, foreground_prob=0)
+        return inds
+
+    def sample(self, i):
+        """(X, Y): the batch's image and label patches (tuples of 2D arrays) after the augmenter"""
+        idx = self.batch(i)
+        arrays = [sample_patches((self.Y[k], self.X[k]), patch_size=self.patch_size, n_samples=1, valid_inds=self.get_valid_inds(k)) for k in idx]
+        X, Y = list(zip(*[(x[0], y[0]) for y, x in arrays]))
+        X, Y = tuple(zip(*tuple(self.augmenter(_x, _y) for _x, _y in zip(X, Y))))
+        return X, Y
+
+    def batch_device(self, i, device):
+        """x (B, H, W, 1), prob_true (B, h, w), dist_true_mask (B, h, w, n_rays + 1): float32 device tensors"""
+        X, Y = self.sample(i)
+        x = torch.from_numpy(np.ascontiguousarray(np.stack(X)[..., None], np.float32)).to(device, non_blocking=False)
+        prob, dtm = targets_device(Y, self.n_rays, self.grid, device)
+        return x, prob, dtm
+
+
+def targets_device(Y, n_rays, grid, device):
+    """the targets of StarDistData2D.__getitem__ (model2d.py:63-104, shape_completion=False) for the label images Y (one shape) from ONE
+    upload: prob_true (B, h, w) (-1 where the label is negative) and dist_true_mask (B, h, w, n_rays + 1) on `device`"""
+    from .utils import edt_prob
+    Y = [np.asarray(y) for y in Y]
+    gy, gx = int(grid[0]), int(grid[1])
+    neg = [y[::gy, ::gx] < 0 for y in Y]
+    has_neg = any(m.any() for m in neg)
+    if has_neg:
+        Y = [np.maximum(y, 0) for y in Y]
+    lab = np.stack(Y)
+    if lab.size and int(lab.max()) >= 2 ** 31:
+        raise ValueError("label ids must fit int32")
+    B, H, W = lab.shape
+    d_lab = torch.from_numpy(np.ascontiguousarray(lab, np.int32)).to(device)
+    d_sub = d_lab[:, ::gy, ::gx].contiguous()
+    # star_dist reads the labels as unsigned short (the reference's geom2d casts with astype(np.uint16)): a 2-byte copy whatever the
+    # dtype of the labels given (the upload above is int32)
+    d_u16 = d_lab.to(torch.uint16).contiguous()
+    h, w = int(d_sub.shape[1]), int(d_sub.shape[2])
+    prob = torch.empty((B, h, w), dtype=torch.float32, device=device)
+    dist = torch.empty((B, h, w, n_rays), dtype=torch.float32, device=device)
+    for b in range(B):
+        sub = lab[b, ::gy, ::gx]
+        lo, hi = (int(sub.min()), int(sub.max())) if sub.size else (0, 0)
+        if (lo == hi and lo > 0) or hi > 4 * sub.size + 1024:
+            prob[b] = edt_prob(d_sub[b])           # the special cases of edt_prob (constant image, sparse huge ids)
+        else:
+            N.dcall(d_sub, "sd_edt_prob_device", ctypes.c_void_p(d_sub[b].data_ptr()), 1, h, w, 1.0, 1.0, 1.0, max(hi, 0),
+                    ctypes.c_void_p(prob[b].data_ptr()))
+        N.dcall(d_u16, "sd_star_dist2d_device", ctypes.c_void_p(d_u16[b].data_ptr()), H, W, int(n_rays), gy, gx, ctypes.c_void_p(dist[b].data_ptr()))
+    dtm = torch.cat([dist, prob[..., None]], dim=-1).contiguous()
+    if has_neg:
+        prob[torch.from_numpy(np.stack(neg)).to(device)] = -1
+    return prob, dtm
+
+
+# ---- scope ---------------------------------------------------------------------------------------------------------------------
+def check_trainable(config):
+    """raise NotImplementedError naming the first setting outside the scope of the native training"""
+    c = config
+    def no(what):
+        raise NotImplementedError("StarDist2D.train on the native kernels does not support %s" % what)
+    if getattr(c, "n_dim", 2) != 2:
+        no("n_dim = %s (2D only)" % c.n_dim)
+    if c.backbone != "unet":
+        no("backbone = %r (U-Net only)" % c.backbone)
+    if c.n_classes is not None:
+        no("n_classes = %r (single class only)" % (c.n_classes,))
+    if c.n_channel_in != 1:
+        no("n_channel_in = %d (one input channel only)" % c.n_channel_in)
+    if c.unet_batch_norm:
+        no("unet_batch_norm = True")
+    if float(getattr(c, "unet_dropout", 0.0)) != 0.0:
+        no("unet_dropout = %r" % c.unet_dropout)
+    if c.train_dist_loss not in ("mae", "mse"):
+        no("train_dist_loss = %r ('mae' or 'mse' only)" % c.train_dist_loss)
+    if c.train_shape_completion:
+        no("train_shape_completion = True")
+    if tuple(c.unet_kernel_size) != (3, 3):
+        no("unet_kernel_size = %s (3x3 only)" % (tuple(c.unet_kernel_size),))
+    if c.unet_n_filter_base % 32 != 0 or c.unet_n_filter_base <= 0:
+        no("unet_n_filter_base = %d (a multiple of 32 only)" % c.unet_n_filter_base)
+    if c.unet_n_filter_base * 2 ** c.unet_n_depth > 512:
+        no("unet_n_filter_base * 2**unet_n_depth = %d (at most 512 channels per layer)" % (c.unet_n_filter_base * 2 ** c.unet_n_depth))
+    if not all(p in (1, 2) for p in c.unet_pool):
+        no("unet_pool = %s (1 or 2 per axis)" % (tuple(c.unet_pool),))
+    if not all(g >= 1 and (g & (g - 1)) == 0 for g in c.grid):
+        no("grid = %s (powers of two only)" % (tuple(c.grid),))
+    if c.net_conv_after_unet % 32 != 0 or c.net_conv_after_unet <= 0:
+        no("net_conv_after_unet = %d (a positive multiple of 32 only)" % c.net_conv_after_unet)
+    for key in ("unet_activation", "unet_last_activation"):
+        if getattr(c, key) not in ("relu", "linear", None):
+            no("%s = %r (relu or linear only)" % (key, getattr(c, key)))
+
+
+# ---- layers --------------------------------------------------------------------------------------------------------------------
+_perm_cache = {}
+
+
+def _pack_perm(kind, ci, co, device):
+    """the packing of sd_conv3_pack_weights_host ('conv3') / sd_convg_pack_weights_host ('convg', 1x1) as a gather on the device:
+    (index into [0, w.flatten()...], mask of the weight positions, the weight-independent rest of the packed array -- the small-channel
+    form of the general kernel appends a tap table)"""
+    key = (kind, ci, co, str(device))
+    p = _perm_cache.get(key)
+    if p is None:
+        L = N.lib()
+        k = 9 if kind == "conv3" else 1
+        outs = []
+        for src in (np.arange(1, co * ci * k + 1, dtype=np.float32), np.zeros(co * ci * k, np.float32)):
+            if kind == "conv3":
+                out = np.zeros(max(int(L.sd_conv3_packed_floats(ci, co, 1)), 0), np.float32)
+                N.check(L.sd_conv3_pack_weights_host(N.ptr(src), ci, co, 1, N.ptr(out)))
+            else:
+                n = int(L.sd_convg_packed_floats(ci, co, 1, 1, 1))
+                if n < 0:
+                    raise ValueError("sd_convg: unsupported 1x1 layer %d -> %d" % (ci, co))
+                out = np.zeros(n, np.float32)
+                N.check(L.sd_convg_pack_weights_host(N.ptr(src), ci, co, 1, 1, 1, N.ptr(out)))
+            outs.append(out)
+        ones, zeros = outs
+        is_w = ones.view(np.uint32) != zeros.view(np.uint32)
+        idx = np.where(is_w, ones, 0).astype(np.int64)
+        p = tuple(torch.from_numpy(a).to(device) for a in (idx, is_w, zeros))
+        _perm_cache[key] = p
+    return p
+
+
+def _packed(w, kind):
+    """packed device form of the kernel w (co, ci, k, k)"""
+    co, ci = int(w.shape[0]), int(w.shape[1])
+    idx, is_w, rest = _pack_perm(kind, ci, co, w.device)
+    flat = torch.cat([w.new_zeros(1), w.reshape(-1)])
+    return torch.where(is_w, flat.index_select(0, idx), rest).contiguous()
+
+
+def _p(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _conv3_fwd(src0, src1, wp, bias, up0, up1, co, relu):
+    B, H, W = int(src0.shape[0]), int(src0.shape[1]) << ((up0 >> 1) & 1), int(src0.shape[2]) << (up0 & 1)
+    c0, c1 = int(src0.shape[3]), (int(src1.shape[3]) if src1 is not None else 0)
+    out = torch.empty((B, H, W, co), dtype=torch.float32, device=src0.device)
+    for b in range(B):
+        N.dcall(src0, "sd_conv3_ndhwc_device", _p(src0[b]), c0, c0, up0, _p(src1[b]) if src1 is not None else None, c1, c1, up1 if src1 is not None else 0,
+                1, H, W, 1, _p(wp), _p(bias), co, int(relu), _p(out[b]))
+    return out
+
+
+class Conv3x3(torch.autograd.Function):
+    """act(conv3x3([UpSampling(src0) | src1]) + bias): tensors (B, H, W, C) float32; up0: the forward kernels' bit mask for src0"""
+
+    @staticmethod
+    def forward(ctx, src0, src1, weight, bias, up0, relu):
+        co = int(weight.shape[0])
+        y = _conv3_fwd(src0, src1, _packed(weight.detach(), "conv3"), bias.detach(), up0, 0, co, relu)
+        ctx.save_for_backward(src0, src1, weight, y)
+        ctx.up0, ctx.relu = up0, relu
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        src0, src1, weight, y = ctx.saved_tensors
+        gy = gy.contiguous()
+        B, H, W, co = (int(v) for v in y.shape)
+        c0, c1 = int(src0.shape[3]), (int(src1.shape[3]) if src1 is not None else 0)
+        if ctx.relu:
+            g = torch.empty_like(gy)
+            N.dcall(gy, "sd_relu_mask_device", _p(gy), _p(y), gy.numel(), _p(g))
+        else:
+            g = gy
+        dw = torch.empty(tuple(weight.shape), dtype=torch.float32, device=g.device)         # (the torch layout, dense)
+        db = torch.empty((co,), dtype=torch.float32, device=g.device)
+        N.dcall(g, "sd_conv_wgrad_ndhwc_device", _p(g), co, _p(src0), c0, ctx.up0, _p(src1), c1, 0, B, H, W, 3, _p(dw), _p(db))
+        d0 = d1 = None
+        if ctx.needs_input_grad[0] or (src1 is not None and ctx.needs_input_grad[1]):
+            # 'same' convolution of g with the flipped, transposed kernel = d(concatenated input)
+            wt = weight.detach().flip(2, 3).transpose(0, 1).contiguous()
+            dcat = _conv3_fwd(g, None, _packed(wt, "conv3"), None, 0, 0, c0 + c1, False)
+            if ctx.up0 or src1 is not None:
+                d0 = torch.empty_like(src0)
+                d1 = torch.empty_like(src1) if src1 is not None else None
+                N.dcall(dcat, "sd_upcat_adjoint_ndhwc_device", _p(dcat), c0, ctx.up0, c1, B, H, W, _p(d0), _p(d1))
+            else:
+                d0 = dcat
+        return d0, d1, dw, db, None, None
+
+
+class MaxPool(torch.autograd.Function):
+    """Keras MaxPooling2D(pool) on (B, H, W, C); the adjoint routes to the first maximum of each window"""
+
+    @staticmethod
+    def forward(ctx, x, py, px):
+        B, H, W, C = (int(v) for v in x.shape)
+        out = torch.empty((B, H // py, W // px, C), dtype=torch.float32, device=x.device)
+        if out.numel():
+            N.dcall(x, "sd_maxpool_ndhwc_device", _p(x), C, B, H, W, 1, py, px, _p(out))
+        ctx.save_for_backward(x)
+        ctx.pool = (py, px)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        g = g.contiguous()
+        B, H, W, C = (int(v) for v in x.shape)
+        gin = torch.empty_like(x)
+        N.dcall(x, "sd_maxpool_adjoint_ndhwc_device", _p(x), _p(g), C, B, H, W, ctx.pool[0], ctx.pool[1], _p(gin))
+        return gin, None, None
+
+
+class HeadsLoss(torch.autograd.Function):
+    """prob = sigmoid(Conv1x1(feat)), dist = Conv1x1(feat) (one 1 + n_rays channel convolution) and the loss of the batch against
+    (prob_true, dist_true_mask): returns the total loss (float64 scalar) and, not differentiable, the losses (prob, dist, total)"""
+
+    @staticmethod
+    def forward(ctx, feat, w_heads, b_heads, prob_true, dtm, loss_args):
+        B, H, W, C = (int(v) for v in feat.shape)
+        co = int(w_heads.shape[0])
+        R = co - 1
+        wp = _packed(w_heads.detach(), "convg")
+        logits = torch.empty((B, H, W, co), dtype=torch.float32, device=feat.device)
+        N.dcall(feat, "sd_convg_ndhwc_device", _p(feat), C, C, B, H, W, 1, 1, 1, 1, 1, 1, 0, 0, 0, B, H, W, _p(wp), _p(b_heads.detach()),
+                None, 0, co, 0, _p(logits), co)
+        prob = torch.sigmoid(logits[..., 0]).contiguous()
+        dist = logits[..., 1:].contiguous()
+        losses = torch.empty(3, dtype=torch.float64, device=feat.device)
+        mse, w_prob, w_dist, reg, want_grad = loss_args
+        # without autograd (validation) the kernel evaluates the losses only
+        gz = torch.empty_like(prob) if want_grad else None
+        gd = torch.empty_like(dist) if want_grad else None
+        N.dcall(prob, "sd_stardist_loss2d_device", _p(prob), _p(dist), _p(prob_true), _p(dtm), B * H * W, R, int(mse), float(w_prob), float(w_dist),
+                float(reg), _p(losses), _p(gz), _p(gd))
+        ctx.save_for_backward(feat, w_heads, gz, gd)
+        ctx.mark_non_differentiable(losses)
+        return losses[2].clone(), losses
+
+    @staticmethod
+    def backward(ctx, gl, _):
+        feat, w_heads, gz, gd = ctx.saved_tensors
+        B, H, W, C = (int(v) for v in feat.shape)
+        co = int(w_heads.shape[0])
+        g = (torch.cat([gz[..., None], gd], dim=-1) * gl.to(torch.float32)).contiguous()
+        dw = torch.empty(tuple(w_heads.shape), dtype=torch.float32, device=g.device)
+        db = torch.empty((co,), dtype=torch.float32, device=g.device)
+        N.dcall(g, "sd_conv_wgrad_ndhwc_device", _p(g), co, _p(feat), C, 0, None, 0, 0, B, H, W, 1, _p(dw), _p(db))
+        wt = _packed(w_heads.detach().transpose(0, 1).contiguous(), "convg")
+        dfeat = torch.empty_like(feat)
+        N.dcall(g, "sd_convg_ndhwc_device", _p(g), co, co, B, H, W, 1, 1, 1, 1, 1, 1, 0, 0, 0, B, H, W, _p(wt), None, None, 0, C, 0, _p(dfeat), C)
+        return dfeat, dw, db, None, None, None
+
+
+def _conv_layer(m, src0, src1=None, up0=0):
+    conv, bn, kind = m.parts()
+    if bn is not None or kind not in (0, 1):
+        raise NotImplementedError("layer %s" % (m,))
+    return Conv3x3.apply(src0, src1, conv.weight, conv.bias, up0, kind == 1)
+
+
+def _up_mask(pool):
+    return (1 if pool[1] == 2 else 0) | (2 if pool[0] == 2 else 0)
+
+
+def train_loss(net, config, x, prob_true, dtm):
+    """total loss (float64 device scalar, differentiable w.r.t. the net's parameters) of one batch and the losses (prob, dist, total) (a
+    float64 device vector): the network of StarDistNet evaluated on the library's exact-f32 kernels.  x (B, H, W, 1), prob_true (B, h, w),
+    dtm (B, h, w, n_rays + 1) float32 device tensors"""
+    for st in net.pre:
+        for m in st["convs"]:
+            x = _conv_layer(m, x)
+        x = MaxPool.apply(x, *st.pool)
+    bb = net.backbone
+    skips = []
+    for blk in bb.down:
+        for m in blk:
+            x = _conv_layer(m, x)
+        skips.append(x)
+        x = MaxPool.apply(x, *bb.pool)
+    for m in bb.middle:
+        x = _conv_layer(m, x)
+    for blk, skip in zip(bb.up, reversed(skips)):
+        x = _conv_layer(blk[0], x, skip, _up_mask(bb.pool))
+        for m in blk[1:]:
+            x = _conv_layer(m, x)
+    feat = _conv_layer(net.features, x)
+    w = torch.cat([net.prob.weight, net.dist.weight], 0)
+    b = torch.cat([net.prob.bias, net.dist.bias], 0)
+    c = config
+    args = (c.train_dist_loss == "mse", c.train_loss_weights[0], c.train_loss_weights[1], c.train_background_reg, torch.is_grad_enabled())
+    return HeadsLoss.apply(feat, w, b, prob_true.contiguous(), dtm.contiguous(), args)
+
+
+# ---- optimiser -----------------------------------------------------------------------------------------------------------------
+class Adam(object):
+    """Keras' Adam (beta_1 0.9, beta_2 0.999, epsilon 1e-7): lr_t = lr sqrt(1 - b2^t) / (1 - b1^t), p -= lr_t m / (sqrt(v) + eps)"""
+
+    def __init__(self, params, lr, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
+        self.params = list(params)
+        self.lr, self.b1, self.b2, self.eps = float(lr), beta_1, beta_2, epsilon
+        self.m = [torch.zeros_like(p) for p in self.params]
+        self.v = [torch.zeros_like(p) for p in self.params]
+        self.t = 0
+
+    @torch.no_grad()
+    def step(self):
+        self.t += 1
+        lr_t = self.lr * math.sqrt(1 - self.b2 ** self.t) / (1 - self.b1 ** self.t)
+        grads = [p.grad for p in self.params]
+        torch._foreach_mul_(self.m, self.b1)
+        torch._foreach_add_(self.m, grads, alpha=1 - self.b1)
+        torch._foreach_mul_(self.v, self.b2)
+        torch._foreach_addcmul_(self.v, grads, grads, value=1 - self.b2)
+        denom = torch._foreach_sqrt(self.v)
+        torch._foreach_add_(denom, self.eps)
+        torch._foreach_addcdiv_(self.params, self.m, denom, value=-lr_t)
+
+
+class ReduceLROnPlateau(object):
+    """Keras' ReduceLROnPlateau on val_loss (mode min)"""
+
+    def __init__(self, factor=0.1, patience=10, min_delta=1e-4, cooldown=0, min_lr=0, verbose=0, monitor="val_loss", mode="auto", **kw):
+        if factor >= 1.0:
+            raise ValueError("ReduceLROnPlateau does not support a factor >= 1.0.")
+        if monitor != "val_loss" or mode not in ("auto", "min"):
+            raise NotImplementedError("ReduceLROnPlateau: only monitor='val_loss', mode 'auto' / 'min'")
+        self.factor, self.patience, self.min_delta, self.cooldown, self.min_lr, self.verbose = factor, patience, min_delta, cooldown, min_lr, verbose
+        self.best, self.wait, self.cooldown_counter = np.inf, 0, 0
+
+    def on_epoch_end(self, epoch, current, opt):
+        if self.cooldown_counter > 0:
+            self.cooldown_counter -= 1
+            self.wait = 0
+        if current < self.best - self.min_delta:
+            self.best, self.wait = current, 0
+        elif not self.cooldown_counter > 0:
+            self.wait += 1
+            if self.wait >= self.patience:
+                old = float(np.float32(opt.lr))
+                if old > np.float32(self.min_lr):
+                    opt.lr = max(old * self.factor, self.min_lr)
+                    if self.verbose:
+                        print("\nEpoch %05d: ReduceLROnPlateau reducing learning rate to %s." % (epoch + 1, opt.lr))
+                    self.cooldown_counter, self.wait = self.cooldown, 0
+
+
+# ---- the loop ------------------------------------------------------------------------------------------------------------------
+def train(model, X, Y, validation_data, augmenter=None, seed=None, epochs=None, steps_per_epoch=None):
+    """StarDist2D.train (see the module docstring); returns the history dict {loss, prob_loss, dist_loss, val_loss, val_prob_loss,
+    val_dist_loss, lr} with one entry per epoch"""
+    import os
+    cfg = model.config
+    check_trainable(cfg)
+    if model.device.type != "cuda":
+        raise RuntimeError("training runs on a HIP device (the model lives on %s)" % model.device)
+    N.require_device()
+    if seed is not None:
+        np.random.seed(seed)
+    if epochs is None:
+        epochs = cfg.train_epochs
+    if steps_per_epoch is None:
+        steps_per_epoch = cfg.train_steps_per_epoch
+    if not isinstance(validation_data, (list, tuple)) or len(validation_data) != 2:
+        raise ValueError("validation_data must be a tuple (X_val, Y_val)")
+    div_by = model._axes_div_by(cfg.axes.replace("C", ""))
+    for p, d, a in zip(cfg.train_patch_size, div_by, cfg.axes.replace("C", "")):
+        if p % d != 0:
+            raise ValueError("'train_patch_size' must be divisible by {d} along axis '{a}'".format(a=a, d=d))
+    data_kwargs = dict(n_rays=cfg.n_rays, patch_size=cfg.train_patch_size, grid=cfg.grid, foreground_prob=cfg.train_foreground_only,
+                       sample_ind_cache=cfg.train_sample_cache)
+    n_data_val = len(validation_data[0])
+    n_take = cfg.train_n_val_patches if cfg.train_n_val_patches is not None else n_data_val
+    dev = model.device
+    data_val = TrainData2D(validation_data[0], validation_data[1], batch_size=n_take, length=1, **data_kwargs)
+    Xv, Yv = data_val.sample(0)
+    bs = int(cfg.train_batch_size)
+    val_batches = []
+    for i in range(0, len(Xv), bs):
+        xv = torch.from_numpy(np.ascontiguousarray(np.stack(Xv[i:i + bs])[..., None], np.float32)).to(dev)
+        val_batches.append((xv,) + targets_device(Yv[i:i + bs], cfg.n_rays, cfg.grid, dev) + (len(Xv[i:i + bs]),))
+    model.data_train = data_train = TrainData2D(X, Y, batch_size=bs, augmenter=augmenter, length=epochs * steps_per_epoch, **data_kwargs)
+
+    net = model.net
+    params = [p for p in net.parameters()]
+    was = [p.requires_grad for p in params]
+    for p in params:
+        p.requires_grad_(True)
+    opt = Adam(params, cfg.train_learning_rate)
+    rlr = ReduceLROnPlateau(**dict(cfg.train_reduce_lr)) if cfg.train_reduce_lr is not None else None
+    names = ("loss", "prob_loss", "dist_loss")
+    history = {k: [] for k in names + tuple("val_" + k for k in names) + ("lr",)}
+    ckpt = lambda name: os.path.join(model.logdir, os.path.splitext(name)[0] + ".npz")
+    best = np.inf
+    net.train()
+    try:
+        step = 0
+        for epoch in range(epochs):
+            acc = torch.zeros(3, dtype=torch.float64, device=dev)
+            for _ in range(steps_per_epoch):
+                x, pt, dtm = data_train.batch_device(step, dev)
+                step += 1
+                for p in params:
+                    p.grad = None
+                loss, losses = train_loss(net, cfg, x, pt, dtm)
+                loss.backward()
+                acc += losses
+                opt.step()
+            tr = (acc / steps_per_epoch).tolist()
+            with torch.no_grad():
+                vacc, nv = torch.zeros(3, dtype=torch.float64, device=dev), 0
+                for xv, ptv, dtmv, n in val_batches:
+                    vacc += train_loss(net, cfg, xv, ptv, dtmv)[1] * n
+                    nv += n
+                va = (vacc / nv).tolist()
+            # Keras reports the total loss as the weighted sum of the outputs' losses
+            for k, v in zip(names, (tr[2], tr[0], tr[1])):
+                history[k].append(v)
+            for k, v in zip(names, (va[2], va[0], va[1])):
+                history["val_" + k].append(v)
+            history["lr"].append(opt.lr)
+            if model.logdir is not None:
+                if cfg.train_checkpoint is not None and va[2] < best:
+                    best = va[2]
+                    model.save_weights_npz(ckpt(cfg.train_checkpoint))
+                if cfg.train_checkpoint_epoch is not None:
+                    model.save_weights_npz(ckpt(cfg.train_checkpoint_epoch))
+            if rlr is not None:
+                rlr.on_epoch_end(epoch, va[2], opt)
+    finally:
+        for p, r in zip(params, was):
+            p.grad = None
+            p.requires_grad_(r)
+        net.eval()
+        # the captured inference graphs hold the packed form of the old kernels; the range fallbacks were decided on them as well
+        model.__dict__.pop("_graphs", None)
+        for mod in net.modules():
+            mod.__dict__.pop("_sd_force_form", None)
+    # csbdeep BaseModel._training_finished: last weights saved, the best ones loaded, the per-epoch file removed
+    if model.logdir is not None:
+        if cfg.train_checkpoint_last is not None:
+            model.save_weights_npz(ckpt(cfg.train_checkpoint_last))
+        if cfg.train_checkpoint is not None and os.path.exists(ckpt(cfg.train_checkpoint)):
+            model.load_weights_npz(ckpt(cfg.train_checkpoint))
+        if cfg.train_checkpoint_epoch is not None and os.path.exists(ckpt(cfg.train_checkpoint_epoch)):
+            os.remove(ckpt(cfg.train_checkpoint_epoch))
+    return history
+
+
+def reference_losses(prob, dist, prob_true, dist_true_mask, dist_loss="mae", loss_weights=(1, 0.2), background_reg=1e-4):
+    """the losses of sd_stardist_loss2d_device as differentiable torch expressions (any dtype; the tests evaluate them in float64):
+    prob (B, h, w) after the sigmoid, dist (B, h, w, n_rays), prob_true (B, h, w), dist_true_mask (B, h, w, n_rays + 1).
+    Returns (prob_loss, dist_loss, total)."""
+    eps = 1e-7
+    m = prob_true >= 0
+    t, p = prob_true[m], prob[m].clamp(eps, 1 - eps)
+    prob_loss = (-(t * torch.log(p + eps) + (1 - t) * torch.log(1 - p + eps))).mean()
+    R = dist.shape[-1]
+    dt, mask = dist_true_mask[..., :R], dist_true_mask[..., R:]
+    e = dt - dist
+    pen = e.abs() if dist_loss == "mae" else e * e
+    per_pixel = (mask * pen).mean(-1) / (mask.mean() + eps)
+    if background_reg > 0:
+        per_pixel = per_pixel + background_reg * ((1 - mask) * dist.abs()).mean(-1)
+    d_loss = per_pixel.mean()
+    return prob_loss, d_loss, loss_weights[0] * prob_loss + loss_weights[1] * d_loss

@@ -6,17 +6,22 @@ line on rank 0.  One "step" = one full `predict_instances()` on one synthetic in
 resident in HBM: network forward (fp32, channels_last) -> threshold/compaction -> score sort ->
 NMS -> label rasteriser -> labels + survivor dict back on the host.
 
-  headline (value, Mpix/s): BASELINE.json configs[1], StarDist2D 32-ray U-Net on a 2048x2048 tile;
-  second leg (value_3d, Mvox/s): configs[2], StarDist3D Rays_GoldenSpiral(96) on a 256^3 volume
-  (runs in the same invocation after the 2D leg; `--skip-3d` drops it).
+  headline (value, Mpix/s): BASELINE.json configs[1], StarDist2D 32-ray U-Net on a 2048x2048 tile.
 
-Every run also reports BASELINE.json configs 4/5 -- `sharded_2d` (one 16384^2 slide) and `sharded_3d` (one 1024^3 volume) through
-predict_instances_sharded: blocks dealt over the ranks, local NMS, one gather of the survivors, cross-tile NMS over the band on rank
-0, write regions rendered by their owners -- with t_predict / t_local_nms / t_exchange / t_final, gathered count and bytes.
+A plain run does what the headline needs and nothing else: set-up (model, head calibration, input), W warm-up and K timed steps,
+`--dump-outputs`, the JSON line (with the stage times and roofline figures of the timed steps themselves).  `--full` adds every other
+leg, in the same invocation after the timed steps:
+  - value_3d (Mvox/s): configs[2], StarDist3D Rays_GoldenSpiral(96) on a 256^3 volume (`--skip-3d` drops it);
+  - the same steps from a host array (`value_host_input*`), the `nms2d_strict` leg, the other convolution forms (`exact_f32*`,
+    `split_bf16x6*`; `--no-split-leg`), the CPU baselines against the compiled reference (`cpu_baseline*`; `--no-cpu-baseline`);
+  - BASELINE.json configs 4/5 -- `sharded_2d` (one 16384^2 slide) and `sharded_3d` (one 1024^3 volume) through
+    predict_instances_sharded: blocks dealt over the ranks, local NMS, one gather of the survivors, cross-tile NMS over the band on
+    rank 0, write regions rendered by their owners -- with t_predict / t_local_nms / t_exchange / t_final, gathered count and bytes
+    (`--no-sharded`).
 
 N = 1: `value` is the 2048^2 tile leg (configs[1]).  N > 1 (one process per GPU, torchrun): `value` is the sharded 16384^2 slide
-(strong scaling of one input, the north star's scaling curve; `scaling: "strong"`), and `value_tiles` carries the weak-scaling figure
-(every rank its own 2048^2 tile, no data-path collective; all ranks' pixels / max-over-ranks time).
+(strong scaling of one input, the north star's scaling curve; `scaling: "strong"`; run with or without `--full`), and `value_tiles`
+carries the weak-scaling figure (every rank its own 2048^2 tile, no data-path collective; all ranks' pixels / max-over-ranks time).
 
 Weights are seeded random (no checkpoints offline).  The two 1x1 heads are re-scaled once, before
 timing, so that the network's own outputs have the candidate statistics of the reference's NMS
@@ -605,13 +610,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=2048)
     ap.add_argument("--size3d", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beside the headline (3D, host-array input, nms2d_strict, other convolution forms, CPU baselines, "
+                         "sharded big inputs); the options below that drop a leg apply to such a run")
     ap.add_argument("--skip-3d", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=2048)
     ap.add_argument("--cpu-sample3d", type=int, default=128)
     ap.add_argument("--cpu-budget3d", type=float, default=75.0, help="run the 3D CPU baseline at full size if the crop predicts at most this many seconds")
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--no-sharded", action="store_true", help="skip the block-sharded big-input legs (configs 4/5; run by default at every N)")
+    ap.add_argument("--no-sharded", action="store_true", help="skip the block-sharded big-input legs (configs 4/5; run with --full, and at N > 1 "
+                                                               "where sharded_2d is the headline)")
     ap.add_argument("--sharded-size", type=int, default=16384)
     ap.add_argument("--sharded-size3d", type=int, default=1024)
     # block sizes (read size incl. context, as in the reference's BlockND.cover), chosen so that the block count divides by 8:
@@ -673,33 +682,32 @@ def main():
     macs = conv_macs_per_input_pixel(model.net, model.config)
     elapsed, net_ms, res, st = run_leg(model, img, args.steps, args.warmup, world, dist_)
     dumped = dump_outputs(args.dump_outputs, res) if args.dump_outputs and rank == 0 else None
-    # second number (SURVEY.md 8d defines the metric host-array-in): the same steps with the image handed over as a host numpy array,
-    # i.e. including the 16.8 MB H2D copy (staged through page-locked memory, stardist_amd/utils.py to_device); `value` stays the
-    # HBM-resident figure the bench contract asks for
-    host2d, host2d_err = guarded(lambda: run_host_legs(model, img_np, args.steps), "host-input leg (2D)")      # an extra leg must never lose the line
-    # the bit-exact-by-construction mode (sd_set_option("nms2d_strict", 1): every pair through the Clipper-exact sweep, no decision from the
-    # area enclosure): same steps, and the instances must be the very same
-    from stardist_amd.lib import _native as _nat
-    strict_steps = max(1, min(args.steps, 10))
+    if args.full:
+        # second number (SURVEY.md 8d defines the metric host-array-in): the same steps with the image handed over as a host numpy array,
+        # i.e. including the 16.8 MB H2D copy (staged through page-locked memory, stardist_amd/utils.py to_device); `value` stays the
+        # HBM-resident figure the bench contract asks for
+        host2d, host2d_err = guarded(lambda: run_host_legs(model, img_np, args.steps), "host-input leg (2D)")      # an extra leg must never lose the line
+        # the bit-exact-by-construction mode (sd_set_option("nms2d_strict", 1): every pair through the Clipper-exact sweep, no decision from the
+        # area enclosure): same steps, and the instances must be the very same
+        from stardist_amd.lib import _native as _nat
+        strict_steps = max(1, min(args.steps, 10))
 
-    def strict_run():
-        with _nat.option("nms2d_strict", 1):
-            return run_leg(model, img, strict_steps, 1, world, dist_)
-    strict, strict_err = guarded(strict_run, "nms2d_strict leg")
-    if strict is None:
-        strict_leg = {"value": None, "error": strict_err}
-    else:
-        el_s, _, res_s, _ = strict
-        strict_leg = {"value": round(world * H * W * strict_steps / el_s / 1e6, 3), "unit": "Mpix/s", "ms_per_step": round(1e3 * el_s / strict_steps, 3),
-                      "instances": len(res_s[1]["prob"]),
-                      "same_result_as_default": bool(np.array_equal(res_s[0], res[0]) and np.array_equal(res_s[1]["points"], res[1]["points"])),
-                      "note": "sd_set_option('nms2d_strict', 1): every 2D pair decided by the Clipper-exact sweep (bit-exact by construction); the default decides "
-                              "pairs far from the threshold from an adversarially validated band around the exact area (DESIGN.md 3.4)"}
+        def strict_run():
+            with _nat.option("nms2d_strict", 1):
+                return run_leg(model, img, strict_steps, 1, world, dist_)
+        strict, strict_err = guarded(strict_run, "nms2d_strict leg")
+        if strict is None:
+            strict_leg = {"value": None, "error": strict_err}
+        else:
+            el_s, _, res_s, _ = strict
+            strict_leg = {"value": round(world * H * W * strict_steps / el_s / 1e6, 3), "unit": "Mpix/s", "ms_per_step": round(1e3 * el_s / strict_steps, 3),
+                          "instances": len(res_s[1]["prob"]),
+                          "same_result_as_default": bool(np.array_equal(res_s[0], res[0]) and np.array_equal(res_s[1]["points"], res[1]["points"])),
+                          "note": "sd_set_option('nms2d_strict', 1): every 2D pair decided by the Clipper-exact sweep (bit-exact by construction); the default decides "
+                                  "pairs far from the threshold from an adversarially validated band around the exact area (DESIGN.md 3.4)"}
     out = None
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
-        p, d = model.predict(img)
-        n_cand = int(((p > model.thresholds.prob)[2:-2, 2:-2]).sum())
         s2 = st.get("nms2d", np.zeros(16, np.int64)) / max(1, args.steps)
         flops = 2.0 * net_macs(model, macs) * H * W
         conv_tf = flops / (net_ms * 1e-3) / 1e12
@@ -780,26 +788,30 @@ def main():
             "config": {"workload": "StarDist2D 32-ray U-Net (depth 3, 32 base filters), %dx%d synthetic fluo tile per GPU, predict_instances "
                                    "(U-Net + select + 2D NMS + polygon raster), seeded random weights, heads calibrated to ~10%% candidates "
                                    "radius 10+-10%%" % (H, W),
-                       "candidates": n_cand, "survivors": len(res[1]["prob"]), "prob_thresh": model.thresholds.prob,
+                       "survivors": len(res[1]["prob"]), "prob_thresh": model.thresholds.prob,
                        "nms_thresh": model.thresholds.nms, "parallelism": "tiles-per-gpu x%d" % world,
                        "nms2d_mode": "default: pairs far from the threshold decided from the area enclosure (exact intersection area +- a band for Clipper's "
                                      "lattice rounding: 0.5 per crossing, max(0.15 per near edge pair, 0.45 per strip), in units of lmax_P + lmax_Q; validated "
                                      "adversarially against the vendored Clipper, DESIGN.md 3.4), the rest by the Clipper-exact sweep; `nms2d_strict` = every "
                                      "pair swept (bit-exact by construction), same instances"},
             "stages_ms": stages, "roofline": dominant, "roofline_convs": roof_conv, "roofline_pair_kernel": roof_pair,
-            "nms2d_strict": strict_leg,
-            "value_host_input": (host_leg_dict(H * W, args.steps, host2d[0], host2d[1], "Mpix/s", ms_per_step) if host2d is not None
-                                 else {"value": None, "error": host2d_err}),
+            "full": args.full,
         }
+        if args.full:
+            p, d = model.predict(img)
+            out["config"]["candidates"] = int(((p > model.thresholds.prob)[2:-2, 2:-2]).sum())
+            out["nms2d_strict"] = strict_leg
+            out["value_host_input"] = (host_leg_dict(H * W, args.steps, host2d[0], host2d[1], "Mpix/s", ms_per_step) if host2d is not None
+                                       else {"value": None, "error": host2d_err})
         if dumped is not None:
             out["dump_outputs"] = {"dir": args.dump_outputs, "leg": "2D tile, last timed step", "dtype": "float32", "arrays": dumped}
-        if not args.no_cpu_baseline and world == 1:      # reported baseline: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported baseline: rank 0 at N=1 only
             try:
                 out["cpu_baseline"] = cpu_baseline_2d(img_np, model, min(args.cpu_sample, H), threads)
                 out["cpu_baseline"]["stage_ratios"] = stage_ratios(out["cpu_baseline"], stages, H * W)
             except Exception as e:   # oracle/_ref must have travelled with the tree
                 out["cpu_baseline"] = {"value": None, "unit": "Mpix/s", "cores": 0, "kind": "reference", "sample": "unavailable: %r" % (e,)}
-    if not args.no_split_leg:
+    if args.full and not args.no_split_leg:
         for key, md in (("exact_f32", "hand"), ("split_bf16x6", "bf16x6")):
             if md == mode:
                 continue
@@ -808,7 +820,8 @@ def main():
                 r["unit"] = "Mpix/s"
                 out[key] = r
     # ---- config 4: one 16384^2 slide (the 2048^2 synthetic tile repeated), blocks 4480 / overlap 128 / context 128, sharded over the ranks
-    if not args.no_sharded:
+    # (at N > 1 the headline, so run without --full as well)
+    if not args.no_sharded and (args.full or world > 1):
         rep = max(1, args.sharded_size // H)
         big, big_err = guarded(lambda: sharded_input(model, synth.s2d_nuclei_image(H, W, seed=0), rep, "YX", args.sharded_block, 128, 128, rank, world, dev),
                                "sharded_2d input")
@@ -930,7 +943,7 @@ def main():
             elif rank == 0:
                 r["unit"] = "Mvox/s"
                 out["sharded_3d"] = r
-    if not args.skip_3d:
+    if args.full and not args.skip_3d:
         _, err3 = guarded(legs_3d, "3D legs")
         if err3 and rank == 0:
             out["error_3d"] = err3

@@ -6,7 +6,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; tag=$1; rtag=$2; O=$R/gpurun_out; mkdir -p $O; cd $R; ulimit -c 0
 ( time timeout 900 python -m pytest tests -m gpu -q -x 2>&1 | tail -8 ) > $O/${tag}_tests.log 2>&1
 timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/${tag}_smoke.log 2>&1
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${tag}_bench.json 2> $O/${tag}_bench.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 timeout 1200 tools/profile_round.sh $rtag > $O/${tag}_profile_stdout.log 2>&1
 timeout 200 python tools/time_predict_sections.py > $O/${tag}_sections.log 2>&1
 timeout 200 python tools/time_predict_sections.py --host-input > $O/${tag}_sections_host.log 2>&1

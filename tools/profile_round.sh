@@ -12,8 +12,8 @@ cd /tmp; export TMPDIR=/tmp; ulimit -c 0
 export SD_PMC_STEPS=3
 python $R/tools/pmc_predict.py > $O/warm.log 2>&1
 # 1. the bench command itself under the kernel trace (its JSON line is kept next to the table: the per-kernel averages must agree with it)
-rm -rf /tmp/prof_kt; (cd $R && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_kt -o kt -- python bench.py --no-cpu-baseline --no-sharded --no-split-leg --steps 5 --warmup 2 > $O/bench_under_trace.log 2>&1)
-db=$(find /tmp/prof_kt -name '*.db' | head -1)
+rm -rf $TMPDIR/prof_kt; (cd $R && timeout 600 rocprofv3 --kernel-trace --stats -d $TMPDIR/prof_kt -o kt -- python bench.py --full --no-cpu-baseline --no-sharded --no-split-leg --steps 5 --warmup 2 > $O/bench_under_trace.log 2>&1)
+db=$(find $TMPDIR/prof_kt -name '*.db' | head -1)
 python $R/tools/rocpd_summary.py $db --md > $O/kernel_stats.md 2>&1
 grep "^{" $O/bench_under_trace.log > $O/bench_under_trace.json
 i=0

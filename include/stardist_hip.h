@@ -485,6 +485,40 @@ int sd_stardist_loss2d_device(const float* d_prob, const float* d_dist, const fl
                               long long n_pix, int n_rays, int dist_loss, double w_prob, double w_dist, double background_reg,
                               double* d_losses, float* d_grad_logit, float* d_grad_dist, void* stream);
 
+/* ---- StarDist3D training (stardist/models/model3d.py train; csrc/train3d.hip) ------------------------------------------------
+ * The pieces of the 3D U-Net / ResNet training step that neither the forward kernels nor the 2D entry points above cover.
+ * Channels-last float32, batch B: [B][D][H][W][C].  The losses are sd_stardist_loss2d_device's with n_pix = B * d * h * w.
+ *
+ * sd_conv3_wgrad_ndhwc_device: weight and bias gradient of a 'same' 3x3x3 convolution with stride 1
+ *     dW[co][ci][kz][ky][kx] = sum_{b,z,y,x} g[b][z][y][x][co] * in[b][z+kz-1][y+ky-1][x+kx-1][ci]      (zero padding)
+ *     db[co] = sum g[..][co]   (d_db may be NULL)
+ * with in = [src0 (c0 channels) | src1 (c1 channels)] and the forward kernels' `up` bit masks (1: x, 2: y, 4: z: that source has half
+ * the resolution along the axis and is read through nearest up-sampling).  Any channel counts (c_in = 1 included).
+ * sd_convg_wgrad_ndhwc_device: the same for any kernel (kz, ky, kx), stride (sz, sy, sx) and padding before the first element
+ * (pz, py, px) -- the convention of sd_convg_ndhwc_device: g is the gradient of the output [B][Do][Ho][Wo][c_out], src the input
+ * [B][D][H][W][c_in]:  dW[co][ci][dz][dy][dx] = sum g[b][zo][yo][xo][co] * src[b][zo*sz - pz + dz][yo*sy - py + dy][xo*sx - px + dx][ci].
+ * Both: exact f32 products on the matrix cores; the output rows are split into chunks that depend on the shape only and the chunk
+ * partials are added in chunk order in float64: repeatable bit for bit.  d_dw has the torch layout [c_out][c_in][kz][ky][kx].
+ * sd_convg_dgrad_ndhwc_device: the data gradient of that convolution (a transposed convolution), d_gin [B][D][H][W][c_in]:
+ *     gin[b][z][y][x][ci] = sum over (dz, dy, dx) with zo = (z + pz - dz) / sz integral and inside [0, Do) (likewise y, x),
+ *                           over co ascending, of g[b][zo][yo][xo][co] * w[co][ci][dz][dy][dx]
+ * one f32 fma chain in that order per element; d_wt is the kernel in the layout [kz][ky][kx][c_out][c_in].
+ * sd_maxpool3d_adjoint_ndhwc_device: adjoint of sd_maxpool_ndhwc_device (pool pz x py x px, stride = pool, 'valid'): each window's
+ * gradient goes to its first maximum in scan order (z, y, x), everything else is zero.  d_in = the pooling's input [B][D][H][W][C].
+ * sd_upcat3d_adjoint_ndhwc_device: adjoint of [UpSampling3D(src0) | src1]: d_gcat [B][D][H][W][c0 + c1] -> d_g1 = its last c1
+ * channels, d_g0 [B][D >> z][H >> y][W >> x][c0] = the sum over each up-sampling window (order dz, dy, dx) of its first c0 channels. */
+int sd_conv3_wgrad_ndhwc_device(const float* d_g, int c_out, const float* d_src0, int c0, int up0, const float* d_src1, int c1, int up1,
+                                int B, int D, int H, int W, float* d_dw, float* d_db, void* stream);
+int sd_convg_wgrad_ndhwc_device(const float* d_g, int c_out, const float* d_src, int c_in, int B, int D, int H, int W, int kz, int ky,
+                                int kx, int sz, int sy, int sx, int pz, int py, int px, int Do, int Ho, int Wo, float* d_dw, float* d_db,
+                                void* stream);
+int sd_convg_dgrad_ndhwc_device(const float* d_g, int c_out, const float* d_wt, int c_in, int B, int D, int H, int W, int kz, int ky,
+                                int kx, int sz, int sy, int sx, int pz, int py, int px, int Do, int Ho, int Wo, float* d_gin, void* stream);
+int sd_maxpool3d_adjoint_ndhwc_device(const float* d_in, const float* d_gout, int n_channels, int B, int D, int H, int W, int pz, int py,
+                                      int px, float* d_gin, void* stream);
+int sd_upcat3d_adjoint_ndhwc_device(const float* d_gcat, int c0, int up0, int c1, int B, int D, int H, int W, float* d_g0, float* d_g1,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,11 @@ SIGNATURES = {
     "sd_upcat_adjoint_ndhwc_device": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sd_stardist_loss2d_device": (_i, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                        _vp, _vp, _vp, _vp]),
+    "sd_conv3_wgrad_ndhwc_device": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sd_convg_wgrad_ndhwc_device": (_i, [_vp, _i, _vp, _i] + [_i] * 16 + [_vp, _vp, _vp]),
+    "sd_convg_dgrad_ndhwc_device": (_i, [_vp, _i, _vp, _i] + [_i] * 16 + [_vp, _vp]),
+    "sd_maxpool3d_adjoint_ndhwc_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sd_upcat3d_adjoint_ndhwc_device": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "_LIB_non_maximum_suppression_2d": (None, [_vp, _vp, _i, _i, _f, _i, _i, _i, _vp]),
     "_LIB_polygon_to_label": (None, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "_LIB_star_dist": (None, [_vp, _i, _i, _i, _i, _i, _vp]),

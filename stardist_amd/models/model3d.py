@@ -134,6 +134,22 @@ class StarDist3D(StarDistBase):
         r = non_maximum_suppression_3d_sparse(dist, prob, points, rays, nms_thresh=nms_thresh, **nms_kwargs)
         return r[0], r[1], r[2], r[3]
 
+    def train(self, X, Y, validation_data, classes="auto", augmenter=None, seed=None, epochs=None, steps_per_epoch=None, workers=1):
+        """model3d.py train on the library's own kernels (stardist_amd/training3d.py): U-Net or ResNet backbone, one input channel,
+        single class, no batch norm / dropout, 3x3x3 kernels, filter counts in multiples of 32 (at most 512 per layer), 'mae' / 'mse'
+        distance loss, grid a power of two per axis, unet_pool 1 or 2 per axis, relu / linear activations, at least two convolutions
+        per ResNet block -- any other configuration raises NotImplementedError naming the setting.
+        X: input volumes (3D, no channel axis), Y: label volumes (negative values switch the losses off there), validation_data:
+        (X_val, Y_val).  With a model folder, weights_best.npz / weights_last.npz are written there and the best weights are loaded at
+        the end.  classes: single-class models only, so anything but 'auto' / None is ignored with the reference's warning; workers:
+        accepted for the reference's signature, the host part of the data pipeline runs in the calling thread.
+        Returns the history dict (per epoch: loss, prob_loss, dist_loss, val_loss, val_prob_loss, val_dist_loss, lr)."""
+        import warnings
+        from ..training3d import train3d
+        if classes not in ("auto", None):
+            warnings.warn("Ignoring given classes as n_classes is set to None")
+        return train3d(self, X, Y, validation_data, augmenter=augmenter, seed=seed, epochs=epochs, steps_per_epoch=steps_per_epoch)
+
     def _axes_div_by(self, query_axes):
         """model3d.py:677-690"""
         if self.config.backbone == "unet":

@@ -84,6 +84,7 @@ def grid_divisible_patch_size(patch_size, grid):
 class TrainData2D(object):
     """StarDistData2D (shape_completion=False) on top of csbdeep's RollingSequence: sample(i) is what its __getitem__(i) draws (image and
     label patches after the augmenter), batch_device(i) adds the targets, computed on the device"""
+    _nd = 2
 
     def __init__(self, X, Y, batch_size, n_rays, length, patch_size=(256, 256), grid=(1, 1), augmenter=None, foreground_prob=0,
                  sample_ind_cache=True, maxfilter_patch_size=None):
@@ -94,10 +95,11 @@ class TrainData2D(object):
         self.length = 2 ** 63 - 1 if length is None else int(length)
         self.index_map = {}
         patch_size = grid_divisible_patch_size(patch_size, grid)
-        if len(patch_size) != 2 or X[0].ndim != 2:
-            raise ValueError("2D images with one channel (no channel axis) expected")
+        nd = self._nd
+        if len(patch_size) != nd or X[0].ndim != nd:
+            raise ValueError("%dD images with one channel (no channel axis) expected" % nd)
         Y = [np.asarray(y) for y in Y]
-        if not all(y.ndim == 2 and x.ndim == 2 and x.shape == y.shape for x, y in zip(X, Y)):
+        if not all(y.ndim == nd and x.ndim == nd and x.shape == y.shape for x, y in zip(X, Y)):
             raise ValueError("images and masks should have corresponding shapes/dimensions")
         if not all(x.shape >= tuple(patch_size) for x in X):
             raise ValueError("Some images are too small for given patch_size {patch_size}".format(patch_size=patch_size))
@@ -503,9 +505,29 @@ class ReduceLROnPlateau(object):
 def train(model, X, Y, validation_data, augmenter=None, seed=None, epochs=None, steps_per_epoch=None):
     """StarDist2D.train (see the module docstring); returns the history dict {loss, prob_loss, dist_loss, val_loss, val_prob_loss,
     val_dist_loss, lr} with one entry per epoch"""
-    import os
     cfg = model.config
     check_trainable(cfg)
+    epochs, steps_per_epoch = begin_training(model, validation_data, seed, epochs, steps_per_epoch)
+    data_kwargs = dict(n_rays=cfg.n_rays, patch_size=cfg.train_patch_size, grid=cfg.grid, foreground_prob=cfg.train_foreground_only,
+                       sample_ind_cache=cfg.train_sample_cache)
+    n_data_val = len(validation_data[0])
+    n_take = cfg.train_n_val_patches if cfg.train_n_val_patches is not None else n_data_val
+    dev = model.device
+    data_val = TrainData2D(validation_data[0], validation_data[1], batch_size=n_take, length=1, **data_kwargs)
+    Xv, Yv = data_val.sample(0)
+    bs = int(cfg.train_batch_size)
+    val_batches = []
+    for i in range(0, len(Xv), bs):
+        xv = torch.from_numpy(np.ascontiguousarray(np.stack(Xv[i:i + bs])[..., None], np.float32)).to(dev)
+        val_batches.append((xv,) + targets_device(Yv[i:i + bs], cfg.n_rays, cfg.grid, dev) + (len(Xv[i:i + bs]),))
+    model.data_train = data_train = TrainData2D(X, Y, batch_size=bs, augmenter=augmenter, length=epochs * steps_per_epoch, **data_kwargs)
+    return fit(model, data_train, val_batches, train_loss, epochs, steps_per_epoch)
+
+
+def begin_training(model, validation_data, seed, epochs, steps_per_epoch):
+    """the checks and settings both train loops start with: a HIP device, np.random.seed(seed), epochs / steps_per_epoch from the config
+    when not given, validation_data a pair, train_patch_size divisible by what the network needs.  Returns (epochs, steps_per_epoch)."""
+    cfg = model.config
     if model.device.type != "cuda":
         raise RuntimeError("training runs on a HIP device (the model lives on %s)" % model.device)
     N.require_device()
@@ -521,20 +543,15 @@ def train(model, X, Y, validation_data, augmenter=None, seed=None, epochs=None, 
     for p, d, a in zip(cfg.train_patch_size, div_by, cfg.axes.replace("C", "")):
         if p % d != 0:
             raise ValueError("'train_patch_size' must be divisible by {d} along axis '{a}'".format(a=a, d=d))
-    data_kwargs = dict(n_rays=cfg.n_rays, patch_size=cfg.train_patch_size, grid=cfg.grid, foreground_prob=cfg.train_foreground_only,
-                       sample_ind_cache=cfg.train_sample_cache)
-    n_data_val = len(validation_data[0])
-    n_take = cfg.train_n_val_patches if cfg.train_n_val_patches is not None else n_data_val
-    dev = model.device
-    data_val = TrainData2D(validation_data[0], validation_data[1], batch_size=n_take, length=1, **data_kwargs)
-    Xv, Yv = data_val.sample(0)
-    bs = int(cfg.train_batch_size)
-    val_batches = []
-    for i in range(0, len(Xv), bs):
-        xv = torch.from_numpy(np.ascontiguousarray(np.stack(Xv[i:i + bs])[..., None], np.float32)).to(dev)
-        val_batches.append((xv,) + targets_device(Yv[i:i + bs], cfg.n_rays, cfg.grid, dev) + (len(Xv[i:i + bs]),))
-    model.data_train = data_train = TrainData2D(X, Y, batch_size=bs, augmenter=augmenter, length=epochs * steps_per_epoch, **data_kwargs)
+    return epochs, steps_per_epoch
 
+
+def fit(model, data_train, val_batches, loss_fn, epochs, steps_per_epoch):
+    """the epoch loop of both train functions: Adam steps on loss_fn(net, config, *data_train.batch_device(step, device)), the
+    validation losses of val_batches [(x, prob_true, dist_true_mask, n)] after each epoch, ReduceLROnPlateau, the checkpoints; returns
+    the history dict"""
+    import os
+    cfg, dev = model.config, model.device
     net = model.net
     params = [p for p in net.parameters()]
     was = [p.requires_grad for p in params]
@@ -556,7 +573,7 @@ def train(model, X, Y, validation_data, augmenter=None, seed=None, epochs=None, 
                 step += 1
                 for p in params:
                     p.grad = None
-                loss, losses = train_loss(net, cfg, x, pt, dtm)
+                loss, losses = loss_fn(net, cfg, x, pt, dtm)
                 loss.backward()
                 acc += losses
                 opt.step()
@@ -564,7 +581,7 @@ def train(model, X, Y, validation_data, augmenter=None, seed=None, epochs=None, 
             with torch.no_grad():
                 vacc, nv = torch.zeros(3, dtype=torch.float64, device=dev), 0
                 for xv, ptv, dtmv, n in val_batches:
-                    vacc += train_loss(net, cfg, xv, ptv, dtmv)[1] * n
+                    vacc += loss_fn(net, cfg, xv, ptv, dtmv)[1] * n
                     nv += n
                 va = (vacc / nv).tolist()
             # Keras reports the total loss as the weighted sum of the outputs' losses

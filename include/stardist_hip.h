@@ -125,6 +125,11 @@ int sd_clip_pairs_device(const int32_t* d_xa, const int32_t* d_ya, const int32_t
 int sd_area_bounds_pairs_device(const int32_t* d_xa, const int32_t* d_ya, const int32_t* d_xb, const int32_t* d_yb, int n_pairs,
                                 int n_verts, float* d_out_area, float* d_out_band, int32_t* d_out_info, void* stream);
 
+/* Test probe of the 2D NMS's per-polygon pass for n_verts <= 32 (stardist_amd/csrc/poly_pass.h), exactly as the NMS launches it:
+ * d_props (n_polys) records of 32 bytes (area_bounds.h PolyProps; n_verts 3..32) and / or d_prep (n_polys) PolyPrep<32> records, each
+ * may be NULL.  Bytes of a PolyPrep record that the preparation does not define are left as they were. */
+int sd_poly_pass_device(const int32_t* d_x, const int32_t* d_y, int n_polys, int n_verts, void* d_props, void* d_prep, void* stream);
+
 /* ---- star-convex distances (training targets; same native module) --------------------------
  * replaces stardist.lib.stardist2d.c_star_dist (stardist2d.cpp:55-124)
  * src (H, W) uint16 labels; dst (ceil(H/gy), ceil(W/gx), n_rays) float32. */

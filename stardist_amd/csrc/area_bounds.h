@@ -33,7 +33,7 @@
 //        into, and raised NEAR_W from 0.125 to 0.15: both changes are monotone (the band only grows: pairs only LEAVE the shortcut for
 //        the exact sweep, earlier evidence stays valid); the weights are EMPIRICAL.  (3) A polygon whose OWN vertex lies within half a step of one of its own edges
 //        is re-ordered by Clipper on its own (found by the adversarial search of round 5): such polygons are not "robustly simple"
-//        (k_poly_props) and are never decided here.
+//        (poly_pass.h props_pair) and are never decided here.
 //        Evidence for the band: 2.0 x 10^9 GPU pairs of eleven families against the exact sweep (round 6; worst 0.25 B), 18 M CPU pairs against the
 //        vendored Clipper (0.27 B), and an annealing ADVERSARY linked to the vendored Clipper (test infrastructure, DESIGN.md 3.4:
 //        4.8 x 10^9 evaluations over NMS-realisable (worst 0.42 B) and free integer polygons (worst 0.53 B); profiles/r05_area_band_adversary.txt).
@@ -59,95 +59,10 @@ __device__ __forceinline__ int half_max_i(int v) { for (int o = 16; o; o >>= 1) 
 constexpr float NEAR_W = 0.15f, STRIP_W = 0.45f;   // band weights of an edge pair within one lattice step / of a strip (mechanism 2); the numpy statement under tests/ and the adversarial search tool of the test infrastructure carry the same values
 constexpr int WINDOW = 2047;        // largest |relative coordinate| for which every predicate's products stay below 2^24
 
-// Per polygon (two polygons per wave, lane & 31 = edge): longest edge, L1 perimeter, orientation, integer bounding box and whether the
-// polygon is ROBUSTLY SIMPLE once zero-length edges are dropped: no two edges share a point except cyclic neighbours at their common
-// vertex, no fold-back between neighbours, at least three edges, and no vertex within half a lattice step (along its scan line) of an edge
-// it does not end.  vx / vy: [n][R] (R <= 32).
-static __global__ void __launch_bounds__(256) k_poly_props(const int* __restrict__ vx, const int* __restrict__ vy, int n, int R, PolyProps* __restrict__ out) {
-  const int lane = threadIdx.x & 63, half = lane >> 5, l = lane & 31, hb = half << 5;
-  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int cand = 2 * wave + half;
-  const bool cv = cand < n;                     // (uniform within a half)
-  const bool valid = cv && l < R;
-  int X = 0, Y = 0;
-  if (valid) { X = vx[(size_t)cand * R + l]; Y = vy[(size_t)cand * R + l]; }
-  const int x0 = __shfl(X, hb), y0 = __shfl(Y, hb);
-  const int xmin = half_min_i(valid ? X : 0x7fffffff), xmax = half_max_i(valid ? X : (int)0x80000000);
-  const int ymin = half_min_i(valid ? Y : 0x7fffffff), ymax = half_max_i(valid ? Y : (int)0x80000000);
-  const bool small = cv && (long long)xmax - xmin <= WINDOW && (long long)ymax - ymin <= WINDOW;
-  const int ln = (l + 1 >= R) ? 0 : l + 1;
-  const int rx = valid && small ? X - x0 : 0, ry = valid && small ? Y - y0 : 0;           // |.| <= WINDOW
-  const int rbx = __shfl(rx, hb + ln), rby = __shfl(ry, hb + ln);
-  const float ax = (float)rx, ay = (float)ry, bx = (float)rbx, by = (float)rby;
-  const float ex = bx - ax, ey = by - ay;
-  const bool deg = !valid || (ex == 0.f && ey == 0.f);
-  const unsigned long long bal = __ballot(!deg);
-  const unsigned int m32 = (unsigned int)(half ? (bal >> 32) : bal);
-  const int count = __popc(m32);
-  int nxt = -1;                                   // the next edge of non-zero length
-  if (m32) { const unsigned int above = (l >= 31) ? 0u : (m32 & ~((2u << l) - 1u)); nxt = above ? __ffs((int)above) - 1 : __ffs((int)m32) - 1; }
-  const int area2 = half_sum_i(valid ? rx * rby - ry * rbx : 0);                            // exact: |terms| < 2^23, 32 of them
-  bool bad = false;
-  // the vertices and the successor table of the half's polygon through LDS: the loop reads them with half-uniform addresses (broadcast
-  // reads) instead of five cross-lane shuffles per iteration
-  __shared__ float2 sv[4][2][32];
-  __shared__ int sn[4][2][32];
-  const int wv = threadIdx.x >> 6;
-  sv[wv][half][l] = make_float2(ax, ay); sn[wv][half][l] = nxt;
-  __builtin_amdgcn_wave_barrier();                  // (a wave's LDS accesses are processed in order)
-  // every UNORDERED pair of edges {l, k} once: lane l meets k = l + dd (cyclically) for dd = 1 .. R / 2 (the pairs at distance R / 2 of an even
-  // R twice) and evaluates the symmetric edge-against-edge test once and the vertex-against-edge rule in both directions -- half the
-  // iterations of a loop over every k.  A lane's findings are OR-ed over the polygon's lanes below.
-  for (int dd = 1; dd <= (R >> 1); ++dd) {
-    int k = l + dd; if (k >= R) k -= R;
-    if (!valid) k = 0;
-    const int kn = (k + 1 >= R) ? 0 : k + 1;
-    const float2 c2 = sv[wv][half][k], d2 = sv[wv][half][kn];
-    const float cx = c2.x, cy = c2.y, dx = d2.x, dy = d2.y;
-    const int nxt_k = sn[wv][half][k];
-    const bool degk = ((m32 >> k) & 1u) == 0u;
-    const float fx = dx - cx, fy = dy - cy;
-    // ROBUSTLY simple (round 5): a vertex must not lie, along its scan line, within HALF a lattice step of an edge it is not an end point
-    // of -- there Clipper's rounded abscissae tie and the polygon's OWN edges can be re-ordered, which changes the area it returns by
-    // more than any strip between the two polygons (found by the adversarial search of DESIGN.md 3.4: a polygon of area 80 whose
-    // spike comes within half a step of a vertex is returned with 68.5).  Exact in float: relative coordinates <= WINDOW.
-    //   my vertex a against edge k = (c -> d) ...
-    if (valid && small && !degk && !((cx == ax && cy == ay) || (dx == ax && dy == ay)) && ay >= fminf(cy, dy) && ay <= fmaxf(cy, dy)) {
-      if (fy == 0.f) { if (ax >= fminf(cx, dx) && ax <= fmaxf(cx, dx)) bad = true; }
-      else if (2.f * fabsf((cx - ax) * fy + (ay - cy) * fx) <= fabsf(fy)) bad = true;            // |x_edge(ay) - ax| <= 1/2
-    }
-    //   ... and vertex c (the start of edge k) against my edge (a -> b)
-    if (valid && small && !deg && !((ax == cx && ay == cy) || (bx == cx && by == cy)) && cy >= fminf(ay, by) && cy <= fmaxf(ay, by)) {
-      if (ey == 0.f) { if (cx >= fminf(ax, bx) && cx <= fmaxf(ax, bx)) bad = true; }
-      else if (2.f * fabsf((ax - cx) * ey + (cy - ay) * ex) <= fabsf(ey)) bad = true;
-    }
-    if (deg || degk || !valid) continue;
-    if (k == nxt || nxt_k == l) {
-      // cyclic neighbours: they share one vertex; anything more is a fold-back (when BOTH hold there are only two edges: count < 3)
-      const float cr = ex * fy - ey * fx, dt = ex * fx + ey * fy;
-      if (cr == 0.f && dt < 0.f) bad = true;
-      continue;
-    }
-    const float o1 = ex * (cy - ay) - ey * (cx - ax), o2 = ex * (dy - ay) - ey * (dx - ax);
-    const float o3 = fx * (ay - cy) - fy * (ax - cx), o4 = fx * (by - cy) - fy * (bx - cx);
-    bool inter = (sgnf(o1) * sgnf(o2) <= 0.f) && (sgnf(o3) * sgnf(o4) <= 0.f);
-    if (o1 == 0.f && o2 == 0.f)                     // collinear: overlap of the two intervals
-      inter = fmaxf(fminf(ax, bx), fminf(cx, dx)) <= fminf(fmaxf(ax, bx), fmaxf(cx, dx)) &&
-              fmaxf(fminf(ay, by), fminf(cy, dy)) <= fminf(fmaxf(ay, by), fmaxf(cy, dy));
-    if (inter) bad = true;
-  }
-  const unsigned long long badm = __ballot(bad);
-  const bool anybad = (unsigned int)(half ? (badm >> 32) : badm) != 0u;
-  const float lmax = half_max(deg ? 0.f : sqrtf(ex * ex + ey * ey));
-  const float perim = half_sum(deg ? 0.f : fabsf(ex) + fabsf(ey));
-  if (cv && l == 0) {
-    PolyProps p;
-    p.lmax = lmax * (1.f + 1e-6f); p.perim = perim;
-    p.flags = ((small && !anybad && count >= 3 && area2 != 0) ? PP_PLAIN : 0) | (area2 > 0 ? PP_POS : 0) | (area2 < 0 ? PP_NEG : 0);
-    p.xmin = xmin; p.xmax = xmax; p.ymin = ymin; p.ymax = ymax; p.pad = 0;
-    out[cand] = p;
-  }
-}
+// The per-polygon record PolyProps -- longest edge, L1 perimeter, orientation, integer bounding box and whether the polygon is ROBUSTLY
+// SIMPLE once zero-length edges are dropped (no two edges share a point except cyclic neighbours at their common vertex, no fold-back
+// between neighbours, at least three edges, and no vertex within half a lattice step (along its scan line) of an edge it does not end) --
+// is written by the build phase's per-polygon pass (poly_pass.h props_pair).
 
 struct Enclosure { float area, band; int crossings, near; bool usable; };
 

@@ -2,6 +2,7 @@
 // Clipper-equivalent area of sd_clip_pairs_device on the same polygons.
 #include "common.h"
 #include "area_bounds.h"
+#include "poly_pass.h"
 #include "../../include/stardist_hip.h"
 
 namespace {
@@ -34,11 +35,23 @@ extern "C" int sd_area_bounds_pairs_device(const int32_t* d_xa, const int32_t* d
   sdarea::PolyProps* pa = (sdarea::PolyProps*)A.take((size_t)n_pairs * sizeof(sdarea::PolyProps));
   sdarea::PolyProps* pb = (sdarea::PolyProps*)A.take((size_t)n_pairs * sizeof(sdarea::PolyProps));
   if (!pa || !pb) return -1;
-  hipLaunchKernelGGL(sdarea::k_poly_props, dim3(sd::div_up(n_pairs, 8)), dim3(256), 0, s, d_xa, d_ya, n_pairs, R, pa);
-  hipLaunchKernelGGL(sdarea::k_poly_props, dim3(sd::div_up(n_pairs, 8)), dim3(256), 0, s, d_xb, d_yb, n_pairs, R, pb);
+  if (sdpass::launch_poly_pass(d_xa, d_ya, n_pairs, R, pa, nullptr, s) || sdpass::launch_poly_pass(d_xb, d_yb, n_pairs, R, pb, nullptr, s)) {
+    sd::set_error("sd_area_bounds_pairs: launch failed");
+    return -1;
+  }
   const int blocks = sd::div_up(n_pairs, 8) < 2048 ? sd::div_up(n_pairs, 8) : 2048;
   hipLaunchKernelGGL(k_area_probe, dim3(blocks), dim3(256), 0, s, d_xa, d_ya, d_xb, d_yb, n_pairs, R, pa, pb, d_out_area, d_out_band, d_out_info);
   SD_LAUNCH_CHECK();
+  SD_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int sd_poly_pass_device(const int32_t* d_x, const int32_t* d_y, int n_polys, int n_verts, void* d_props, void* d_prep, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n_polys <= 0 || (!d_props && !d_prep)) return 0;
+  const int R = n_verts;
+  if (R < (d_props ? 3 : 1) || R > 32) { sd::set_error("sd_poly_pass: n_verts=%d unsupported (%d..32)", R, d_props ? 3 : 1); return -1; }
+  if (sdpass::launch_poly_pass(d_x, d_y, n_polys, R, (sdarea::PolyProps*)d_props, d_prep, s)) { sd::set_error("sd_poly_pass: launch failed"); return -1; }
   SD_CHECK(hipStreamSynchronize(s));
   return 0;
 }

@@ -27,6 +27,7 @@
 #include "clip_sweep.h"
 #include "clip_beam.h"
 #include "area_bounds.h"
+#include "poly_pass.h"
 #include "../../include/stardist_hip.h"
 #include <hipcub/hipcub.hpp>
 #include <math.h>
@@ -511,8 +512,8 @@ __global__ void __launch_bounds__(256) k_round_emit(const int* __restrict__ K, c
   flush();
 }
 
-// ---- prepared polygons: Clipper::AddPath once per candidate (clip_beam.h), one thread per candidate, working arrays
-// lane-interleaved in LDS
+// ---- prepared polygons for n_rays > 32: Clipper::AddPath once per candidate (clip_beam.h), one thread per candidate, working arrays
+// lane-interleaved in LDS (n_rays <= 32: poly_pass.h)
 template <int MAXV, int S>
 __global__ void __launch_bounds__(S) k_prepare(const int* __restrict__ vx, const int* __restrict__ vy, int N, int R,
                                                sdclip::PolyPrep<MAXV>* __restrict__ prep) {
@@ -889,10 +890,15 @@ template <int MAXV, int SPREP>
 struct BeamPath {
   typedef sdclip::PolyPrep<MAXV> Prep;
   static int prepare(const int* vx, const int* vy, int N, int R, void* prep, hipStream_t s) {
-    const size_t lds = sdclip::PrepWork<sdclip::LdsStorage<SPREP>, MAXV>::lds_bytes() + 64;
-    hipLaunchKernelGGL((k_prepare<MAXV, SPREP>), dim3(sd::div_up(N, SPREP)), dim3(SPREP), lds, s, vx, vy, N, R, (Prep*)prep);
-    SD_LAUNCH_CHECK();
-    return 0;
+    if constexpr (MAXV == 32) {                     // n_rays <= 32: the per-polygon pass (poly_pass.h), prepared polygons only
+      if (sdpass::launch_poly_pass(vx, vy, N, R, nullptr, prep, s)) { sd::set_error("sd_nms2d: launch of the per-polygon pass failed"); return -1; }
+      return 0;
+    } else {
+      const size_t lds = sdclip::PrepWork<sdclip::LdsStorage<SPREP>, MAXV>::lds_bytes() + 64;
+      hipLaunchKernelGGL((k_prepare<MAXV, SPREP>), dim3(sd::div_up(N, SPREP)), dim3(SPREP), lds, s, vx, vy, N, R, (Prep*)prep);
+      SD_LAUNCH_CHECK();
+      return 0;
+    }
   }
   // tier 1 (K = 8): all pairs of the round; capacity spills -> q.spill
   static int tier1(const int2* pairs, const unsigned int* idx, const unsigned long long* nPairs, const unsigned int* first, const void* prep, const float* area,
@@ -1021,23 +1027,20 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
     props = (sdarea::PolyProps*)A.take((size_t)N * sizeof(sdarea::PolyProps));
     if (!props) return -1;
   }
-  // The helper stream's two kernels are enqueued once the LAST read-back of the grid set-up is behind us (launch_side below): k_poly_props
-  // fills every wave slot of the chip, and an 8-byte device -> host copy of the caller's stream issued while it runs waits for a slot
-  // until it drains (measured: 0.69 ms for that copy, the neighbour-list kernel started 0.7 ms late; profiles/r05_step_timeline_2d.txt).
+  // The helper stream's work is enqueued once the LAST read-back of the grid set-up is behind us (launch_side below): it fills every
+  // wave slot of the chip, and an 8-byte device -> host copy of the caller's stream issued while it runs waits for a slot until it drains
+  // (measured: 0.69 ms for that copy, the neighbour-list kernel started 0.7 ms late; profiles/r05_step_timeline_2d.txt).
+  // n_rays <= 32: ONE pass writes the properties and the prepared polygons (poly_pass.h); more rays: k_prepare alone (no shortcut).
   auto launch_side = [&]() -> int {
     SD_CHECK(hipEventRecord(evFork, s));
     SD_CHECK(hipStreamWaitEvent(side, evFork, 0));
-    if (areaBounds) {
-      hipLaunchKernelGGL(sdarea::k_poly_props, dim3(sd::div_up(N, 8)), dim3(256), 0, side, vx, vy, N, R, props);
-      SD_LAUNCH_CHECK();
-    }
-    SD_CHECK(hipEventRecord(evProps, side));
     int rc;
-    if (R <= 32) rc = BeamPath<32, 64>::prepare(vx, vy, N, R, prep, side);
+    if (R <= 32) rc = sdpass::launch_poly_pass(vx, vy, N, R, props, prep, side);
     else if (R <= 64) rc = BeamPath<64, 64>::prepare(vx, vy, N, R, prep, side);
     else if (R <= 128) rc = BeamPath<128, 32>::prepare(vx, vy, N, R, prep, side);
     else rc = BeamPath<256, 16>::prepare(vx, vy, N, R, prep, side);
-    if (rc) return -1;
+    if (rc) { sd::set_error("sd_nms2d: launch of the per-polygon pass failed"); return -1; }
+    SD_CHECK(hipEventRecord(evProps, side));
     SD_CHECK(hipEventRecord(evPrep, side));
     SD_CHECK(hipEventRecord(evJoin, side));
     return 0;

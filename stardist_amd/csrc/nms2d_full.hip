@@ -9,6 +9,7 @@
 #include "clip_sweep.h"
 #include "clip_sweep_full.h"
 #include "clip_beam.h"
+#include "poly_pass.h"
 #include <stdlib.h>
 #include "../../include/stardist_hip.h"
 
@@ -179,7 +180,10 @@ extern "C" int sd_prepare_polys_device(const int32_t* d_x, const int32_t* d_y, i
   if (R < 1 || R > 256) { sd::set_error("sd_prepare_polys: n_verts=%d unsupported (1..256)", R); return -1; }
   const size_t rec = R <= 32 ? sizeof(sdclip::PolyPrep<32>) : R <= 64 ? sizeof(sdclip::PolyPrep<64>) : R <= 128 ? sizeof(sdclip::PolyPrep<128>) : sizeof(sdclip::PolyPrep<256>);
   if ((int64_t)(rec * (size_t)n_polys) > out_bytes) { sd::set_error("sd_prepare_polys: output buffer too small (%zu bytes per polygon)", rec); return -1; }
-  if (R <= 32) return launch_prepare_probe<32, 64>(d_x, d_y, n_polys, R, d_out, s);
+  if (R <= 32) {                                   // the production pass of the 2D NMS (poly_pass.h)
+    if (sdpass::launch_poly_pass(d_x, d_y, n_polys, R, nullptr, d_out, s)) { sd::set_error("sd_prepare_polys: launch failed"); return -1; }
+    return 0;
+  }
   if (R <= 64) return launch_prepare_probe<64, 64>(d_x, d_y, n_polys, R, d_out, s);
   if (R <= 128) return launch_prepare_probe<128, 32>(d_x, d_y, n_polys, R, d_out, s);
   return launch_prepare_probe<256, 16>(d_x, d_y, n_polys, R, d_out, s);

@@ -479,7 +479,16 @@ int sd_label_overlap_device(const int32_t* d_true, const int32_t* d_pred, long l
  * (m = the last channel of d_dist_true_mask [n_pix][n_rays + 1]; pen = |.| for dist_loss 0 (mae), square for 1 (mse)); d_losses (device,
  * 3 doubles) = {prob_loss, dist_loss, w_prob * prob_loss + w_dist * dist_loss}; d_grad_logit [n_pix] = d total / d (logit of prob)
  * (zero where prob is clipped or masked), d_grad_dist [n_pix][n_rays] = d total / d dist; both NULL: the losses only (evaluation without
- * a backward pass).  float64 sums in a fixed order. */
+ * a backward pass).  float64 sums in a fixed order.
+ * sd_stardist_loss2d_metrics_device: sd_stardist_loss2d_device (the same losses and gradients, bit for bit; gradient buffers both NULL:
+ * the losses only) that also evaluates the metrics the reference compiles its model with (base.py kld, relevant_mae, relevant_mse,
+ * dist_iou_metric) over the same pixels; d_metrics (device, 4 doubles) =
+ *     kld             = mean over pixels with prob_true >= 0 of bce(tc, pc) - bce(tc, tc),  tc = clip(prob_true, e, 1), pc = clip(prob, e, 1)
+ *     relevant_mae    = mean over pixels of m mean_r |t_r - d_r|   / (mean(m) + e)
+ *     relevant_mse    = mean over pixels of m mean_r (t_r - d_r)^2 / (mean(m) + e)
+ *     dist_iou_metric = mean over pixels of m inter / (union + e)   / (mean(m) + e)
+ * with bce the cross entropy of prob_loss above, inter = mean_r min(t_r, d+_r)^2, union = mean_r max(t_r, d+_r)^2, d+ = max(0, d).  These
+ * are the values of one batch; Keras averages kld over batches and the other three over pixels. */
 int sd_conv_wgrad_ndhwc_device(const float* d_g, int c_out, const float* d_src0, int c0, int up0, const float* d_src1, int c1, int up1,
                                int B, int H, int W, int k, float* d_dw, float* d_db, void* stream);
 int sd_relu_mask_device(const float* d_dy, const float* d_y, long long n, float* d_out, void* stream);
@@ -489,6 +498,9 @@ int sd_upcat_adjoint_ndhwc_device(const float* d_gcat, int c0, int up0, int c1, 
 int sd_stardist_loss2d_device(const float* d_prob, const float* d_dist, const float* d_prob_true, const float* d_dist_true_mask,
                               long long n_pix, int n_rays, int dist_loss, double w_prob, double w_dist, double background_reg,
                               double* d_losses, float* d_grad_logit, float* d_grad_dist, void* stream);
+int sd_stardist_loss2d_metrics_device(const float* d_prob, const float* d_dist, const float* d_prob_true, const float* d_dist_true_mask,
+                                      long long n_pix, int n_rays, int dist_loss, double w_prob, double w_dist, double background_reg,
+                                      double* d_losses, float* d_grad_logit, float* d_grad_dist, double* d_metrics, void* stream);
 
 /* ---- StarDist3D training (stardist/models/model3d.py train; csrc/train3d.hip) ------------------------------------------------
  * The pieces of the 3D U-Net / ResNet training step that neither the forward kernels nor the 2D entry points above cover.

@@ -12,6 +12,8 @@
 //     as torch's CPU max-pool routes it) and UpSampling + Concatenate (a fixed-order sum over each 2x2 window).
 //   * sd_stardist_loss2d_device: the two losses of the 2D model and their gradients in three passes -- per-block float64 partial sums
 //     over fixed pixel ranges, one block that adds them in order, then the per-pixel gradients.
+//   * sd_stardist_loss2d_metrics_device: the same passes, the first two also summing the reference's Keras metrics (kld, relevant_mae,
+//     relevant_mse, dist_iou_metric) over the loads the losses make; the losses and gradients are those of the entry above, bit for bit.
 #include "common.h"
 #include "stardist_hip.h"
 
@@ -206,6 +208,7 @@ __global__ void k_upcat_adjoint(const float* __restrict__ gcat, int c0, int c1, 
 constexpr int LOSS_THREADS = 256;
 constexpr int LOSS_PIX_PER_BLOCK = 4096;
 constexpr int LOSS_TERMS = 5;        // unmasked pixels, sum BCE, sum dist mask, sum mean_rays(mask * pen), sum mean_rays((1 - mask) |d|)
+constexpr int METRIC_TERMS = 4;      // the metrics pass adds: sum kld, sum m mean_r |e|, sum m mean_r e^2, sum m iou
 constexpr double K_EPS = 1e-7;       // Keras' epsilon()
 
 __device__ __forceinline__ double bce_clipped(double t, double p) {
@@ -213,48 +216,78 @@ __device__ __forceinline__ double bce_clipped(double t, double p) {
   return -(t * log(pc + K_EPS) + (1.0 - t) * log(1.0 - pc + K_EPS));
 }
 
+// METRICS adds the sums of the Keras metrics the reference compiles its model with (base.py:68-104, 351-353) over the same loads:
+//     [5] kld: bce(tc, pc) - bce(tc, tc) over the pixels with prob_true >= 0   (tc = clip(prob_true, e, 1), pc = clip(prob, e, 1))
+//     [6] m mean_r |t_r - d_r|   [7] m mean_r (t_r - d_r)^2   [8] m inter / (union + e),  inter / union = mean_r min / max(t_r, d+_r)^2
+// (d+ = max(0, d)); METRICS = false is the losses' pass alone.
+template <bool METRICS>
 __global__ __launch_bounds__(LOSS_THREADS) void k_loss_partials(const float* __restrict__ prob, const float* __restrict__ dist,
                                                                 const float* __restrict__ pt, const float* __restrict__ dtm, long long n_pix,
                                                                 int R, int mse, double* __restrict__ part) {
-  __shared__ double sh[LOSS_TERMS][LOSS_THREADS];
-  double acc[LOSS_TERMS] = {0, 0, 0, 0, 0};
+  constexpr int T = METRICS ? LOSS_TERMS + METRIC_TERMS : LOSS_TERMS;
+  __shared__ double sh[T][LOSS_THREADS];
+  double acc[T] = {};
   const long long p0 = (long long)blockIdx.x * LOSS_PIX_PER_BLOCK;
   const long long p1 = min(n_pix, p0 + LOSS_PIX_PER_BLOCK);
   for (long long p = p0 + threadIdx.x; p < p1; p += LOSS_THREADS) {
     const double t = pt[p];
-    if (t >= 0) { acc[0] += 1.0; acc[1] += bce_clipped(t, (double)prob[p]); }
+    if (t >= 0) {
+      acc[0] += 1.0; acc[1] += bce_clipped(t, (double)prob[p]);
+      if constexpr (METRICS) {
+        const double tc = fmin(fmax(t, K_EPS), 1.0), pc = fmin(fmax((double)prob[p], K_EPS), 1.0);
+        acc[5] += bce_clipped(tc, pc) - bce_clipped(tc, tc);
+      }
+    }
     const float* tr = dtm + p * (R + 1);
     const float* d = dist + p * R;
     const double m = tr[R];
     acc[2] += m;
     double sa = 0, sr = 0;
+    double ma = 0, ms = 0, in = 0, un = 0;
     for (int r = 0; r < R; ++r) {
       const double e = (double)((float)tr[r] - d[r]);
       sa += m * (mse ? e * e : fabs(e));
       sr += (1.0 - m) * fabs((double)d[r]);
+      if constexpr (METRICS) {
+        const double tt = tr[r], dp = fmax(0.0, (double)d[r]);
+        const double lo = fmin(tt, dp), hi = fmax(tt, dp);
+        ma += fabs(e);
+        ms += e * e;
+        in += lo * lo;
+        un += hi * hi;
+      }
     }
     acc[3] += sa / R;
     acc[4] += sr / R;
+    if constexpr (METRICS) {
+      acc[6] += m * (ma / R);
+      acc[7] += m * (ms / R);
+      acc[8] += m * ((in / R) / (un / R + K_EPS));
+    }
   }
 #pragma unroll
-  for (int k = 0; k < LOSS_TERMS; ++k) sh[k][threadIdx.x] = acc[k];
+  for (int k = 0; k < T; ++k) sh[k][threadIdx.x] = acc[k];
   __syncthreads();
   for (int s = LOSS_THREADS / 2; s > 0; s >>= 1) {
     if ((int)threadIdx.x < s)
 #pragma unroll
-      for (int k = 0; k < LOSS_TERMS; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + s];
+      for (int k = 0; k < T; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + s];
     __syncthreads();
   }
-  if (threadIdx.x < LOSS_TERMS) part[(size_t)blockIdx.x * LOSS_TERMS + threadIdx.x] = sh[threadIdx.x][0];
+  if (threadIdx.x < T) part[(size_t)blockIdx.x * T + threadIdx.x] = sh[threadIdx.x][0];
 }
 
-// one thread: the block partials in block order -> losses {prob, dist, total} and the two scale factors of the gradients
+// one thread: the block partials in block order -> losses {prob, dist, total} and the two scale factors of the gradients; METRICS: also
+// the metrics {kld, relevant_mae, relevant_mse, dist_iou_metric} of the batch (Keras' per-pixel means over n_pix, the kld over the
+// unmasked pixels)
+template <bool METRICS>
 __global__ void k_loss_finish(const double* __restrict__ part, int n_blocks, long long n_pix, double w_prob, double w_dist, double reg,
-                              double* __restrict__ losses, double* __restrict__ scal) {
+                              double* __restrict__ losses, double* __restrict__ scal, double* __restrict__ metrics) {
+  constexpr int T = METRICS ? LOSS_TERMS + METRIC_TERMS : LOSS_TERMS;
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double s[LOSS_TERMS] = {0, 0, 0, 0, 0};
+  double s[T] = {};
   for (int b = 0; b < n_blocks; ++b)
-    for (int k = 0; k < LOSS_TERMS; ++k) s[k] += part[(size_t)b * LOSS_TERMS + k];
+    for (int k = 0; k < T; ++k) s[k] += part[(size_t)b * T + k];
   const double prob_loss = s[1] / s[0];
   const double norm = s[2] / (double)n_pix + K_EPS;                // K.mean(mask) + K.epsilon()
   const double dist_loss = (s[3] / norm + (reg > 0 ? reg * s[4] : 0.0)) / (double)n_pix;
@@ -264,6 +297,10 @@ __global__ void k_loss_finish(const double* __restrict__ part, int n_blocks, lon
   scal[0] = w_prob / s[0];
   scal[1] = w_dist / ((double)n_pix * norm);
   scal[2] = reg > 0 ? w_dist * reg / (double)n_pix : 0.0;
+  if constexpr (METRICS) {
+    metrics[0] = s[5] / s[0];
+    for (int k = 1; k < METRIC_TERMS; ++k) metrics[k] = (s[5 + k] / (double)n_pix) / norm;
+  }
 }
 
 __global__ void k_loss_grad(const float* __restrict__ prob, const float* __restrict__ dist, const float* __restrict__ pt,
@@ -380,29 +417,57 @@ extern "C" int sd_upcat_adjoint_ndhwc_device(const float* d_gcat, int c0, int up
   return 0;
 }
 
-extern "C" int sd_stardist_loss2d_device(const float* d_prob, const float* d_dist, const float* d_prob_true, const float* d_dist_true_mask,
-                                         long long n_pix, int n_rays, int dist_loss, double w_prob, double w_dist, double background_reg,
-                                         double* d_losses, float* d_grad_logit, float* d_grad_dist, void* stream_) {
-  hipStream_t s = (hipStream_t)stream_;
-  if (!d_prob || !d_dist || !d_prob_true || !d_dist_true_mask || !d_losses || n_pix <= 0 || n_rays <= 0 ||
-      (dist_loss != 0 && dist_loss != 1) || (!d_grad_logit) != (!d_grad_dist)) {
-    sd::set_error("sd_stardist_loss2d: dist_loss 0 (mae) or 1 (mse), positive sizes, inputs and d_losses given, both gradient buffers or neither");
-    return -1;
-  }
+namespace {
+
+// the passes of both loss entry points (the arguments checked by the caller)
+template <bool METRICS>
+int loss2d_passes(const float* d_prob, const float* d_dist, const float* d_prob_true, const float* d_dist_true_mask, long long n_pix, int n_rays,
+                  int dist_loss, double w_prob, double w_dist, double background_reg, double* d_losses, float* d_grad_logit, float* d_grad_dist,
+                  double* d_metrics, hipStream_t s) {
+  constexpr int T = METRICS ? LOSS_TERMS + METRIC_TERMS : LOSS_TERMS;
   const int n_blocks = sd::div_up(n_pix, LOSS_PIX_PER_BLOCK);
   sd::Arena& A = sd::arena();
   if (A.begin(s)) return -1;
-  double* part = A.take_n<double>((size_t)n_blocks * LOSS_TERMS);
+  double* part = A.take_n<double>((size_t)n_blocks * T);
   double* scal = A.take_n<double>(4);
   if (!part || !scal) return -1;
-  hipLaunchKernelGGL(k_loss_partials, dim3(n_blocks), dim3(LOSS_THREADS), 0, s, d_prob, d_dist, d_prob_true, d_dist_true_mask, n_pix, n_rays,
-                     dist_loss, part);
+  hipLaunchKernelGGL(k_loss_partials<METRICS>, dim3(n_blocks), dim3(LOSS_THREADS), 0, s, d_prob, d_dist, d_prob_true, d_dist_true_mask, n_pix,
+                     n_rays, dist_loss, part);
   SD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, s, part, n_blocks, n_pix, w_prob, w_dist, background_reg, d_losses, scal);
+  hipLaunchKernelGGL(k_loss_finish<METRICS>, dim3(1), dim3(64), 0, s, part, n_blocks, n_pix, w_prob, w_dist, background_reg, d_losses, scal,
+                     d_metrics);
   SD_LAUNCH_CHECK();
   if (!d_grad_logit) return 0;                   // losses only
   hipLaunchKernelGGL(k_loss_grad, dim3(grid_for(n_pix * (n_rays + 1))), dim3(256), 0, s, d_prob, d_dist, d_prob_true, d_dist_true_mask, n_pix,
                      n_rays, dist_loss, scal, d_grad_logit, d_grad_dist);
   SD_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int sd_stardist_loss2d_device(const float* d_prob, const float* d_dist, const float* d_prob_true, const float* d_dist_true_mask,
+                                         long long n_pix, int n_rays, int dist_loss, double w_prob, double w_dist, double background_reg,
+                                         double* d_losses, float* d_grad_logit, float* d_grad_dist, void* stream_) {
+  if (!d_prob || !d_dist || !d_prob_true || !d_dist_true_mask || !d_losses || n_pix <= 0 || n_rays <= 0 ||
+      (dist_loss != 0 && dist_loss != 1) || (!d_grad_logit) != (!d_grad_dist)) {
+    sd::set_error("sd_stardist_loss2d: dist_loss 0 (mae) or 1 (mse), positive sizes, inputs and d_losses given, both gradient buffers or neither");
+    return -1;
+  }
+  return loss2d_passes<false>(d_prob, d_dist, d_prob_true, d_dist_true_mask, n_pix, n_rays, dist_loss, w_prob, w_dist, background_reg, d_losses,
+                              d_grad_logit, d_grad_dist, nullptr, (hipStream_t)stream_);
+}
+
+extern "C" int sd_stardist_loss2d_metrics_device(const float* d_prob, const float* d_dist, const float* d_prob_true,
+                                                 const float* d_dist_true_mask, long long n_pix, int n_rays, int dist_loss, double w_prob,
+                                                 double w_dist, double background_reg, double* d_losses, float* d_grad_logit, float* d_grad_dist,
+                                                 double* d_metrics, void* stream_) {
+  if (!d_prob || !d_dist || !d_prob_true || !d_dist_true_mask || !d_losses || !d_metrics || n_pix <= 0 || n_rays <= 0 ||
+      (dist_loss != 0 && dist_loss != 1) || (!d_grad_logit) != (!d_grad_dist)) {
+    sd::set_error("sd_stardist_loss2d_metrics: dist_loss 0 (mae) or 1 (mse), positive sizes, inputs, d_losses and d_metrics given, both "
+                  "gradient buffers or neither");
+    return -1;
+  }
+  return loss2d_passes<true>(d_prob, d_dist, d_prob_true, d_dist_true_mask, n_pix, n_rays, dist_loss, w_prob, w_dist, background_reg, d_losses,
+                             d_grad_logit, d_grad_dist, d_metrics, (hipStream_t)stream_);
 }

@@ -97,6 +97,8 @@ SIGNATURES = {
     "sd_upcat_adjoint_ndhwc_device": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sd_stardist_loss2d_device": (_i, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                        _vp, _vp, _vp, _vp]),
+    "sd_stardist_loss2d_metrics_device": (_i, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, ctypes.c_double, ctypes.c_double,
+                                               ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
     "sd_conv3_wgrad_ndhwc_device": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sd_convg_wgrad_ndhwc_device": (_i, [_vp, _i, _vp, _i] + [_i] * 16 + [_vp, _vp, _vp]),
     "sd_convg_dgrad_ndhwc_device": (_i, [_vp, _i, _vp, _i] + [_i] * 16 + [_vp, _vp]),

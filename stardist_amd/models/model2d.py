@@ -135,7 +135,10 @@ class StarDist2D(StarDistBase):
         Y_val).  With a model folder, weights_best.npz / weights_last.npz are written there and the best weights are loaded at the end.
         classes: single-class models only, so anything but 'auto' / None is ignored with the reference's warning; workers: accepted for the
         reference's signature, the host part of the data pipeline runs in the calling thread.
-        Returns the history dict (per epoch: loss, prob_loss, dist_loss, val_loss, val_prob_loss, val_dist_loss, lr)."""
+        Returns a History (training.History: a dict of per-epoch lists, also reachable as .history, with .epoch and .params) with the
+        keys of the reference's Keras history: loss, prob_loss, dist_loss, prob_kld, dist_relevant_mae, dist_relevant_mse,
+        dist_dist_iou_metric, the same seven with a val_ prefix, and lr.  prob_kld averages over batches, the dist_ metrics over
+        pixels, as Keras' Mean does."""
         import warnings
         from ..training import train
         if classes not in ("auto", None):

@@ -11,7 +11,8 @@ stardist/models/base.py:34-60, 315-325 and the data generator StarDistData2D wit
                itself (StarDistBase._net_forward) is not involved.
   backward     csrc/train2d.hip: weight / bias gradients (sd_conv_wgrad_ndhwc_device), ReLU / max-pool / up-sampling adjoints; the data
                gradient of a 3x3 layer is the forward kernel on the flipped, transposed kernel.
-  loss         sd_stardist_loss2d_device: both losses and their gradients in one call.
+  loss         sd_stardist_loss2d_device: both losses and their gradients in one call; in train(), sd_stardist_loss2d_metrics_device,
+               which adds the reference's Keras metrics (kld, relevant_mae, relevant_mse, dist_iou_metric) in the same passes.
   optimiser    Keras' Adam (epsilon 1e-7) and ReduceLROnPlateau on val_loss, as torch element-wise updates.
 Scope: U-Net backbone, one input channel, no classes, no batch norm / dropout, 'mae' / 'mse' distance loss, no shape completion;
 check_trainable() names the first setting outside it."""
@@ -369,7 +370,9 @@ class MaxPool(torch.autograd.Function):
 
 class HeadsLoss(torch.autograd.Function):
     """prob = sigmoid(Conv1x1(feat)), dist = Conv1x1(feat) (one 1 + n_rays channel convolution) and the loss of the batch against
-    (prob_true, dist_true_mask): returns the total loss (float64 scalar) and, not differentiable, the losses (prob, dist, total)"""
+    (prob_true, dist_true_mask): returns the total loss (float64 scalar) and, not differentiable, the losses (prob, dist, total).
+    loss_args = (mse, w_prob, w_dist, reg, want_grad, metrics_out): a float64 device tensor of 4 as metrics_out receives the batch's
+    metrics (kld, relevant_mae, relevant_mse, dist_iou_metric) from the same kernel passes; None: the losses alone"""
 
     @staticmethod
     def forward(ctx, feat, w_heads, b_heads, prob_true, dtm, loss_args):
@@ -383,12 +386,19 @@ class HeadsLoss(torch.autograd.Function):
         prob = torch.sigmoid(logits[..., 0]).contiguous()
         dist = logits[..., 1:].contiguous()
         losses = torch.empty(3, dtype=torch.float64, device=feat.device)
-        mse, w_prob, w_dist, reg, want_grad = loss_args
+        mse, w_prob, w_dist, reg, want_grad, metrics_out = loss_args
         # without autograd (validation) the kernel evaluates the losses only
         gz = torch.empty_like(prob) if want_grad else None
         gd = torch.empty_like(dist) if want_grad else None
-        N.dcall(prob, "sd_stardist_loss2d_device", _p(prob), _p(dist), _p(prob_true), _p(dtm), B * H * W, R, int(mse), float(w_prob), float(w_dist),
-                float(reg), _p(losses), _p(gz), _p(gd))
+        args = (_p(prob), _p(dist), _p(prob_true), _p(dtm), B * H * W, R, int(mse), float(w_prob), float(w_dist), float(reg), _p(losses), _p(gz),
+                _p(gd))
+        if metrics_out is None:
+            N.dcall(prob, "sd_stardist_loss2d_device", *args)
+        else:
+            if not (metrics_out.dtype == torch.float64 and metrics_out.device == feat.device and metrics_out.numel() == 4
+                    and metrics_out.is_contiguous()):
+                raise ValueError("metrics_out: a contiguous float64 tensor of 4 on the device of the batch")
+            N.dcall(prob, "sd_stardist_loss2d_metrics_device", *args, _p(metrics_out))
         ctx.save_for_backward(feat, w_heads, gz, gd)
         ctx.mark_non_differentiable(losses)
         return losses[2].clone(), losses
@@ -419,10 +429,11 @@ def _up_mask(pool):
     return (1 if pool[1] == 2 else 0) | (2 if pool[0] == 2 else 0)
 
 
-def train_loss(net, config, x, prob_true, dtm):
+def train_loss(net, config, x, prob_true, dtm, metrics_out=None):
     """total loss (float64 device scalar, differentiable w.r.t. the net's parameters) of one batch and the losses (prob, dist, total) (a
     float64 device vector): the network of StarDistNet evaluated on the library's exact-f32 kernels.  x (B, H, W, 1), prob_true (B, h, w),
-    dtm (B, h, w, n_rays + 1) float32 device tensors"""
+    dtm (B, h, w, n_rays + 1) float32 device tensors.  metrics_out (a float64 device tensor of 4, optional) receives the batch's
+    metrics (kld, relevant_mae, relevant_mse, dist_iou_metric)"""
     for st in net.pre:
         for m in st["convs"]:
             x = _conv_layer(m, x)
@@ -444,7 +455,8 @@ def train_loss(net, config, x, prob_true, dtm):
     w = torch.cat([net.prob.weight, net.dist.weight], 0)
     b = torch.cat([net.prob.bias, net.dist.bias], 0)
     c = config
-    args = (c.train_dist_loss == "mse", c.train_loss_weights[0], c.train_loss_weights[1], c.train_background_reg, torch.is_grad_enabled())
+    args = (c.train_dist_loss == "mse", c.train_loss_weights[0], c.train_loss_weights[1], c.train_background_reg, torch.is_grad_enabled(),
+            metrics_out)
     return HeadsLoss.apply(feat, w, b, prob_true.contiguous(), dtm.contiguous(), args)
 
 
@@ -502,9 +514,41 @@ class ReduceLROnPlateau(object):
 
 
 # ---- the loop ------------------------------------------------------------------------------------------------------------------
+LOSS_NAMES = ("loss", "prob_loss", "dist_loss")
+METRIC_NAMES = ("prob_kld", "dist_relevant_mae", "dist_relevant_mse", "dist_dist_iou_metric")
+HISTORY_KEYS = LOSS_NAMES + METRIC_NAMES + tuple("val_" + k for k in LOSS_NAMES + METRIC_NAMES) + ("lr",)
+
+
+class History(dict):
+    """what Keras' Model.fit returns, as the dict of its per-epoch values: hist["val_loss"] and hist.history["val_loss"] are the same
+    list; .epoch the epoch indices, .params {verbose, epochs, steps}"""
+
+    def __init__(self, epochs, steps):
+        super(History, self).__init__((k, []) for k in HISTORY_KEYS)
+        self.epoch = []
+        self.params = {"verbose": 1, "epochs": int(epochs), "steps": int(steps)}
+
+    @property
+    def history(self):
+        return self
+
+
+def keras_epoch_metrics(values, n_pix):
+    """the epoch values of the four metrics from their per-batch values (n_batches, 4) (kld, relevant_mae, relevant_mse,
+    dist_iou_metric) and the batches' pixel counts, by Keras' Mean rules: kld is one scalar per batch, so every batch counts once; the
+    three distance metrics are one value per pixel, so every batch counts with its pixels.  Returns a float64 tensor of 4 (on the
+    device of `values`)."""
+    values = torch.as_tensor(values, dtype=torch.float64)
+    w = torch.as_tensor(n_pix, dtype=torch.float64).to(values.device)
+    if values.ndim != 2 or values.shape[1] != 4 or w.shape != values.shape[:1]:
+        raise ValueError("values (n_batches, 4) and one pixel count per batch expected")
+    kld = values[:, 0].mean()
+    dist = (values[:, 1:] * w[:, None]).sum(0) / w.sum()
+    return torch.cat([kld[None], dist])
+
+
 def train(model, X, Y, validation_data, augmenter=None, seed=None, epochs=None, steps_per_epoch=None):
-    """StarDist2D.train (see the module docstring); returns the history dict {loss, prob_loss, dist_loss, val_loss, val_prob_loss,
-    val_dist_loss, lr} with one entry per epoch"""
+    """StarDist2D.train (see the module docstring); returns the History (a dict) of HISTORY_KEYS with one entry per epoch"""
     cfg = model.config
     check_trainable(cfg)
     epochs, steps_per_epoch = begin_training(model, validation_data, seed, epochs, steps_per_epoch)
@@ -547,9 +591,10 @@ def begin_training(model, validation_data, seed, epochs, steps_per_epoch):
 
 
 def fit(model, data_train, val_batches, loss_fn, epochs, steps_per_epoch):
-    """the epoch loop of both train functions: Adam steps on loss_fn(net, config, *data_train.batch_device(step, device)), the
-    validation losses of val_batches [(x, prob_true, dist_true_mask, n)] after each epoch, ReduceLROnPlateau, the checkpoints; returns
-    the history dict"""
+    """the epoch loop of both train functions: Adam steps on loss_fn(net, config, *data_train.batch_device(step, device), metrics_out=...),
+    the validation losses and metrics of val_batches [(x, prob_true, dist_true_mask, n)] after each epoch, ReduceLROnPlateau, the
+    checkpoints; returns the History.  The losses are averaged as before (training: over steps; validation: weighted by images), the
+    metrics by Keras' rules (keras_epoch_metrics); one host synchronisation per epoch."""
     import os
     cfg, dev = model.config, model.device
     net = model.net
@@ -559,8 +604,7 @@ def fit(model, data_train, val_batches, loss_fn, epochs, steps_per_epoch):
         p.requires_grad_(True)
     opt = Adam(params, cfg.train_learning_rate)
     rlr = ReduceLROnPlateau(**dict(cfg.train_reduce_lr)) if cfg.train_reduce_lr is not None else None
-    names = ("loss", "prob_loss", "dist_loss")
-    history = {k: [] for k in names + tuple("val_" + k for k in names) + ("lr",)}
+    history = History(epochs, steps_per_epoch)
     ckpt = lambda name: os.path.join(model.logdir, os.path.splitext(name)[0] + ".npz")
     best = np.inf
     net.train()
@@ -568,28 +612,33 @@ def fit(model, data_train, val_batches, loss_fn, epochs, steps_per_epoch):
         step = 0
         for epoch in range(epochs):
             acc = torch.zeros(3, dtype=torch.float64, device=dev)
-            for _ in range(steps_per_epoch):
+            met, met_pix = torch.empty((steps_per_epoch, 4), dtype=torch.float64, device=dev), []
+            for i in range(steps_per_epoch):
                 x, pt, dtm = data_train.batch_device(step, dev)
                 step += 1
                 for p in params:
                     p.grad = None
-                loss, losses = loss_fn(net, cfg, x, pt, dtm)
+                loss, losses = loss_fn(net, cfg, x, pt, dtm, metrics_out=met[i])
                 loss.backward()
                 acc += losses
+                met_pix.append(pt.numel())
                 opt.step()
-            tr = (acc / steps_per_epoch).tolist()
             with torch.no_grad():
                 vacc, nv = torch.zeros(3, dtype=torch.float64, device=dev), 0
-                for xv, ptv, dtmv, n in val_batches:
-                    vacc += loss_fn(net, cfg, xv, ptv, dtmv)[1] * n
+                vmet, vmet_pix = torch.empty((len(val_batches), 4), dtype=torch.float64, device=dev), []
+                for j, (xv, ptv, dtmv, n) in enumerate(val_batches):
+                    vacc += loss_fn(net, cfg, xv, ptv, dtmv, metrics_out=vmet[j])[1] * n
                     nv += n
-                va = (vacc / nv).tolist()
+                    vmet_pix.append(ptv.numel())
+                ep = torch.cat([acc / steps_per_epoch, keras_epoch_metrics(met, met_pix), vacc / nv, keras_epoch_metrics(vmet, vmet_pix)]).tolist()
+            tr, va = ep[:7], ep[7:]
             # Keras reports the total loss as the weighted sum of the outputs' losses
-            for k, v in zip(names, (tr[2], tr[0], tr[1])):
+            for k, v in zip(LOSS_NAMES + METRIC_NAMES, [tr[2], tr[0], tr[1]] + tr[3:]):
                 history[k].append(v)
-            for k, v in zip(names, (va[2], va[0], va[1])):
+            for k, v in zip(LOSS_NAMES + METRIC_NAMES, [va[2], va[0], va[1]] + va[3:]):
                 history["val_" + k].append(v)
             history["lr"].append(opt.lr)
+            history.epoch.append(epoch)
             if model.logdir is not None:
                 if cfg.train_checkpoint is not None and va[2] < best:
                     best = va[2]
@@ -635,3 +684,25 @@ def reference_losses(prob, dist, prob_true, dist_true_mask, dist_loss="mae", los
         per_pixel = per_pixel + background_reg * ((1 - mask) * dist.abs()).mean(-1)
     d_loss = per_pixel.mean()
     return prob_loss, d_loss, loss_weights[0] * prob_loss + loss_weights[1] * d_loss
+
+
+def reference_metrics(prob, dist, prob_true, dist_true_mask):
+    """the metrics of sd_stardist_loss2d_metrics_device as torch expressions (the tests evaluate them in float64; shapes as in
+    reference_losses, any number of spatial axes): the values of one batch of the reference's kld, relevant_mae, relevant_mse and
+    dist_iou_metric (base.py:68-104, 335-353), Keras' mean taken over each metric's values.  Returns (kld, mae, mse, iou)."""
+    eps = 1e-7
+    bce = lambda t, p: -(t * torch.log(p.clamp(eps, 1 - eps) + eps) + (1 - t) * torch.log(1 - p.clamp(eps, 1 - eps) + eps))
+    m = prob_true >= 0
+    tc, pc = prob_true[m].clamp(eps, 1), prob[m].clamp(eps, 1)
+    kld = (bce(tc, pc) - bce(tc, tc)).mean()
+    R = dist.shape[-1]
+    dt, mask = dist_true_mask[..., :R], dist_true_mask[..., R:]
+    norm = mask.mean() + eps
+    e = dt - dist
+    mae = ((mask * e.abs()).mean(-1) / norm).mean()
+    mse = ((mask * e * e).mean(-1) / norm).mean()
+    dp = dist.clamp_min(0)
+    inter = torch.minimum(dt, dp).square().mean(-1)
+    union = torch.maximum(dt, dp).square().mean(-1)
+    iou = ((mask[..., 0] * (inter / (union + eps))) / norm).mean()
+    return kld, mae, mse, iou

@@ -17,7 +17,8 @@ losses of stardist/models/base.py:34-60, 315-325 and the data generator StarDist
                of strided convolutions, the 3D max-pool and up-sampling adjoints; the data gradient of a stride-1 3x3x3 layer is the
                forward kernel on the flipped, transposed kernel; ReLU adjoints by sd_relu_mask_device (a ResNet block's Add + ReLU: one
                mask on the block output, the result feeds both branches).
-  loss         sd_stardist_loss2d_device with n_pix = B * d * h * w (the 3D model uses the same losses).
+  loss         sd_stardist_loss2d_device with n_pix = B * d * h * w (the 3D model uses the same losses and metrics; in train3d()
+               sd_stardist_loss2d_metrics_device, the metrics per voxel).
   optimiser    training.Adam / ReduceLROnPlateau, the epoch loop and checkpoints of training.fit.
 Scope: check_trainable3d() names the first setting outside it."""
 
@@ -379,10 +380,10 @@ def _up_mask(pool):
     return (1 if pool[2] == 2 else 0) | (2 if pool[1] == 2 else 0) | (4 if pool[0] == 2 else 0)
 
 
-def train_loss3d(net, config, x, prob_true, dtm):
+def train_loss3d(net, config, x, prob_true, dtm, metrics_out=None):
     """total loss (float64 device scalar, differentiable w.r.t. the net's parameters) of one batch and the losses (prob, dist, total) (a
     float64 device vector): the U-Net or ResNet of StarDistNet evaluated on the library's exact-f32 kernels.  x (B, D, H, W, 1),
-    prob_true (B, d, h, w), dtm (B, d, h, w, n_rays + 1) float32 device tensors"""
+    prob_true (B, d, h, w), dtm (B, d, h, w, n_rays + 1) float32 device tensors; metrics_out as in training.train_loss"""
     if config.backbone == "unet":
         for st in net.pre:
             for m in st["convs"]:
@@ -410,7 +411,8 @@ def train_loss3d(net, config, x, prob_true, dtm):
     b = torch.cat([net.prob.bias, net.dist.bias], 0)
     B, d, h, wd, C = (int(v) for v in feat.shape)
     c = config
-    args = (c.train_dist_loss == "mse", c.train_loss_weights[0], c.train_loss_weights[1], c.train_background_reg, torch.is_grad_enabled())
+    args = (c.train_dist_loss == "mse", c.train_loss_weights[0], c.train_loss_weights[1], c.train_background_reg, torch.is_grad_enabled(),
+            metrics_out)
     # the 1x1x1 heads and the losses are per voxel: batch and z fold into one axis
     return HeadsLoss.apply(feat.reshape(B * d, h, wd, C), w, b, prob_true.reshape(B * d, h, wd).contiguous(),
                            dtm.reshape(B * d, h, wd, -1).contiguous(), args)
@@ -418,8 +420,7 @@ def train_loss3d(net, config, x, prob_true, dtm):
 
 # ---- the loop ------------------------------------------------------------------------------------------------------------------
 def train3d(model, X, Y, validation_data, augmenter=None, seed=None, epochs=None, steps_per_epoch=None):
-    """StarDist3D.train (see the module docstring); returns the history dict {loss, prob_loss, dist_loss, val_loss, val_prob_loss,
-    val_dist_loss, lr} with one entry per epoch"""
+    """StarDist3D.train (see the module docstring); returns the History (a dict) of training.HISTORY_KEYS with one entry per epoch"""
     from .rays3d import rays_from_json
     cfg = model.config
     check_trainable3d(cfg)

@@ -6,7 +6,10 @@
   * losses and their gradients (sd_stardist_loss2d_device): 1e-6 relative;
   * one step of the 2D_demo topology: every parameter's gradient within 1e-4 (norm-wise) of float64 autograd of StarDistNet;
   * the targets equal stardist_targets(); no library convolution / GEMM in a step; two seeded runs give the same bits;
-  * the reference's test_model scenarios (train, save, reload, predict) and convergence on synthetic discs."""
+  * the reference's test_model scenarios (train, save, reload, predict) and convergence on synthetic discs.
+The shapes here are small: each kernel's work partition is a single iteration.  test_gpu_training_scale.py checks the same kernels at
+training shapes (several tiles per weight-gradient chunk, ragged chunks, grid-stride loops past 2^24 elements), exactly on ternary
+data, and one step of the 2D_demo topology at B = 8."""
 import copy
 import os
 

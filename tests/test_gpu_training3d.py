@@ -8,7 +8,10 @@
   * one step of a small U-Net and a small ResNet: every parameter's gradient within 1e-4 (norm-wise) of float64 autograd of StarDistNet;
   * no library convolution / GEMM in a step; two seeded runs give the same bits;
   * the reference's test_model3D scenarios in scope (train, predict with and without tiles, save, reload), test_foreground_warning,
-    and convergence on synthetic anisotropic balls."""
+    and convergence on synthetic anisotropic balls.
+The shapes here are small: each kernel's work partition is a single iteration.  test_gpu_training_scale.py checks the same kernels at
+the 3D_demo's training shape (ragged voxel-row chunks, k_dgrad3 and the adjoints past 2^24 elements), exactly on ternary data, and
+one step of the 3D_demo configuration."""
 import copy
 import os
 

@@ -5,7 +5,8 @@
   * with the metrics on, the losses and both gradients are those of sd_stardist_loss2d_device bit for bit (with gradients and without);
   * StarDist2D.train: the validation metrics of the history equal reference_metrics of the trained network in float64 over the
     validation batches (a short last batch), combined by Keras' rules; the keys and the History object;
-  * StarDist3D.train: the same keys, all finite, two seeded runs give the same history."""
+  * StarDist3D.train: the same keys, all finite, two seeded runs give the same history.
+test_gpu_training_scale.py checks the metrics and losses past 2^24 gradient elements, with empty and all-foreground distance masks."""
 import copy
 
 import numpy as np

@@ -457,7 +457,7 @@ int sd_convg_ndhwc_device(const float* d_src, int c_in, int src_stride, int D, i
 int sd_label_overlap_device(const int32_t* d_true, const int32_t* d_pred, long long n, long long cap, int64_t* d_keys, int64_t* d_counts,
                             long long* h_count, int32_t* h_minmax, void* stream);
 
-/* ---- training (2D): backward pass and losses (csrc/train2d.hip) ---------------------------------------------------------------
+/* ---- training (2D): backward pass and losses (csrc/train2d.hip; the two pooling / up-sampling adjoints: csrc/train3d.hip) ------
  * The reference trains its Keras model with StarDist2D.train (stardist/models/model2d.py) on the losses of base.py:34-60, 315-325; these
  * entry points are the pieces of that step the forward kernels above do not cover.  Channels-last float32, batch B (2D: [B][H][W][C]).
  *
@@ -473,6 +473,8 @@ int sd_label_overlap_device(const int32_t* d_true, const int32_t* d_pred, long l
  * to its first maximum in scan order (y, then x), everything else is zero.  d_in = the pooling's input [B][H][W][C], d_gout [B][H/py][W/px][C].
  * sd_upcat_adjoint_ndhwc_device: adjoint of [UpSampling(src0) | src1]: d_gcat [B][H][W][c0 + c1] -> d_g1 = its last c1 channels
  * [B][H][W][c1], d_g0 [B][H >> y][W >> x][c0] = the sum over each up-sampling window (order dy, then dx) of its first c0 channels.
+ * These two check their own arguments and then are sd_maxpool3d_adjoint_ndhwc_device / sd_upcat3d_adjoint_ndhwc_device (below) with
+ * D = 1, pz = 1 and up bit 4 clear: one kernel per operation serves both models.
  * sd_stardist_loss2d_device: the 2D model's losses and their gradients over n_pix pixels (batch and space flattened):
  *     prob_loss = mean over pixels with prob_true >= 0 of -(t log(pc + e) + (1 - t) log(1 - pc + e)),  pc = clip(prob, e, 1 - e), e = 1e-7
  *     dist_loss = mean over pixels of  mean_r(m * pen(t_r - d_r)) / (mean(m) + e) + reg * mean_r((1 - m) |d_r|)
@@ -503,7 +505,8 @@ int sd_stardist_loss2d_metrics_device(const float* d_prob, const float* d_dist, 
                                       double* d_losses, float* d_grad_logit, float* d_grad_dist, double* d_metrics, void* stream);
 
 /* ---- StarDist3D training (stardist/models/model3d.py train; csrc/train3d.hip) ------------------------------------------------
- * The pieces of the 3D U-Net / ResNet training step that neither the forward kernels nor the 2D entry points above cover.
+ * The pieces of the 3D U-Net / ResNet training step that neither the forward kernels nor the 2D entry points above cover, and the
+ * max-pool / up-sampling adjoint kernels of both models (2D tensors are the D = 1 case).
  * Channels-last float32, batch B: [B][D][H][W][C].  The losses are sd_stardist_loss2d_device's with n_pix = B * d * h * w.
  *
  * sd_conv3_wgrad_ndhwc_device: weight and bias gradient of a 'same' 3x3x3 convolution with stride 1

@@ -8,8 +8,8 @@
 //     8 x 32 tile it stages the gradient tile and the input tile (3x3: plus its halo) in LDS once and runs all taps on them.  The pixels are
 //     split into a number of chunks that depends on the shape only; each chunk writes its partial sums to the workspace and
 //     k_wgrad_reduce adds them in chunk order (float64).  No atomics: two calls give the same bits.
-//   * k_relu_mask, k_maxpool_adjoint, k_upcat_adjoint: the adjoints of ReLU, MaxPooling (first maximum of each window in scan order,
-//     as torch's CPU max-pool routes it) and UpSampling + Concatenate (a fixed-order sum over each 2x2 window).
+//   * k_relu_mask: the adjoint of ReLU.  Those of MaxPooling2D and UpSampling2D + Concatenate (sd_maxpool_adjoint_ndhwc_device,
+//     sd_upcat_adjoint_ndhwc_device) are the depth-1 case of the 3D kernels and live next to them in train3d.hip.
 //   * sd_stardist_loss2d_device: the two losses of the 2D model and their gradients in three passes -- per-block float64 partial sums
 //     over fixed pixel ranges, one block that adds them in order, then the per-pixel gradients.
 //   * sd_stardist_loss2d_metrics_device: the same passes, the first two also summing the reference's Keras metrics (kld, relevant_mae,
@@ -150,58 +150,6 @@ __global__ void k_wgrad_reduce(const float* __restrict__ ws, const float* __rest
 __global__ void k_relu_mask(const float* __restrict__ dy, const float* __restrict__ y, long long n, float* __restrict__ out) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
     out[i] = y[i] > 0.f ? dy[i] : 0.f;
-}
-
-// one thread per INPUT element: the gradient of its window's output goes to the window's first maximum (scan order y, then x; a NaN
-// counts as a maximum, as in torch's CPU max-pool); elements of a window that is not the maximum, and rows / columns beyond the last
-// whole window, get zero
-__global__ void k_maxpool_adjoint(const float* __restrict__ x, const float* __restrict__ gout, int C, int H, int W, int py, int px,
-                                  long long n, float* __restrict__ gin) {
-  const int Ho = H / py, Wo = W / px;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C);
-    long long r = i / C;
-    const int xx = (int)(r % W); r /= W;
-    const int yy = (int)(r % H);
-    const long long b = r / H;
-    const int oy = yy / py, ox = xx / px;
-    float v = 0.f;
-    if (oy < Ho && ox < Wo) {
-      int by = oy * py, bx = ox * px;
-      float m = x[((b * H + by) * W + bx) * C + c];
-      for (int dy = 0; dy < py; ++dy)
-        for (int dx = 0; dx < px; ++dx) {
-          const float u = x[((b * H + oy * py + dy) * W + ox * px + dx) * C + c];
-          if (u > m || (u != u && m == m)) { m = u; by = oy * py + dy; bx = ox * px + dx; }
-        }
-      if (by == yy && bx == xx) v = gout[((b * Ho + oy) * Wo + ox) * C + c];
-    }
-    gin[i] = v;
-  }
-}
-
-// gcat [B][H][W][c0 + c1] -> g1 = its last c1 channels, g0 [B][H >> sy][W >> sx][c0] = the sum over each up-sampling window of its
-// first c0 channels (window order: dy, then dx)
-__global__ void k_upcat_adjoint(const float* __restrict__ gcat, int c0, int c1, int sy, int sx, int H, int W, long long n0, long long n1,
-                                float* __restrict__ g0, float* __restrict__ g1) {
-  const int C = c0 + c1, H0 = H >> sy, W0 = W >> sx;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n0 + n1; i += (long long)gridDim.x * blockDim.x) {
-    if (i < n0) {
-      const int c = (int)(i % c0);
-      long long r = i / c0;
-      const int x = (int)(r % W0); r /= W0;
-      const int y = (int)(r % H0);
-      const long long b = r / H0;
-      float s = 0.f;
-      for (int dy = 0; dy <= sy; ++dy)
-        for (int dx = 0; dx <= sx; ++dx) s += gcat[((b * H + (y << sy) + dy) * W + (x << sx) + dx) * C + c];
-      g0[i] = s;
-    } else {
-      const long long j = i - n0;
-      const int c = (int)(j % c1);
-      g1[j] = gcat[(j / c1) * C + c0 + c];
-    }
-  }
 }
 
 // ---- losses -------------------------------------------------------------------------------------------------------------------
@@ -385,34 +333,6 @@ extern "C" int sd_relu_mask_device(const float* d_dy, const float* d_y, long lon
   if (n <= 0) return 0;
   if (!d_dy || !d_y || !d_out) { sd::set_error("sd_relu_mask: null pointer"); return -1; }
   hipLaunchKernelGGL(k_relu_mask, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream_, d_dy, d_y, n, d_out);
-  SD_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int sd_maxpool_adjoint_ndhwc_device(const float* d_in, const float* d_gout, int n_channels, int B, int H, int W, int py, int px,
-                                               float* d_gin, void* stream_) {
-  if (!d_in || !d_gout || !d_gin || n_channels <= 0 || B < 0 || H < 0 || W < 0 || py < 1 || px < 1) {
-    sd::set_error("sd_maxpool_adjoint_ndhwc: invalid arguments");
-    return -1;
-  }
-  const long long n = (long long)B * H * W * n_channels;
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(k_maxpool_adjoint, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream_, d_in, d_gout, n_channels, H, W, py, px, n, d_gin);
-  SD_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int sd_upcat_adjoint_ndhwc_device(const float* d_gcat, int c0, int up0, int c1, int B, int H, int W, float* d_g0, float* d_g1,
-                                             void* stream_) {
-  if (!d_gcat || !d_g0 || c0 <= 0 || c1 < 0 || (c1 > 0 && !d_g1) || B < 0 || H < 0 || W < 0 || (up0 & ~3) || ((up0 & 1) && (W & 1)) ||
-      ((up0 & 2) && (H & 1))) {
-    sd::set_error("sd_upcat_adjoint_ndhwc: up bits 1 (x) / 2 (y) over even sizes");
-    return -1;
-  }
-  const int sx = up0 & 1, sy = (up0 >> 1) & 1;
-  const long long n0 = (long long)B * (H >> sy) * (W >> sx) * c0, n1 = (long long)B * H * W * c1;
-  if (n0 + n1 == 0) return 0;
-  hipLaunchKernelGGL(k_upcat_adjoint, dim3(grid_for(n0 + n1)), dim3(256), 0, (hipStream_t)stream_, d_gcat, c0, c1, sy, sx, H, W, n0, n1, d_g0, d_g1);
   SD_LAUNCH_CHECK();
   return 0;
 }

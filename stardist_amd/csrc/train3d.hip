@@ -1,5 +1,6 @@
 // train3d.hip -- the backward pass of StarDist3D training (stardist/models/model3d.py train; the U-Net and ResNet graphs of
-// model3d.py:370-452).  Everything the 2D backward (train2d.hip) does not already cover for the 3D shapes and the ResNet layers:
+// model3d.py:370-452): what the 2D backward (train2d.hip) does not already cover for the 3D shapes and the ResNet layers, and the
+// max-pool and up-sampling adjoints of both models:
 //
 //   * k_wgrad3: weight gradient of a 3D convolution as a GEMM on the f32 matrix cores (v_mfma_f32_32x32x2_f32, exact f32 products)
 //         dW[co][n] = sum_{b,zo,yo,xo} g[b][zo][yo][xo][co] * in[b][zo*sz - pz + dz][yo*sy - py + dy][xo*sx - px + dx][ci]
@@ -18,8 +19,9 @@
 //         gin[b][z][y][x][ci] = sum_{taps, in order} sum_{co, ascending} g[b][zo][yo][xo][co] * w[co][ci][dz][dy][dx]
 //     over the taps with z = zo*sz - pz + dz (etc.) for an output voxel inside the output -- one fixed f32 fma chain per element.
 //     The stride-1 3x3x3 layers do not come here: their data gradient is the forward kernel on the flipped, transposed kernel.
-//   * k_maxpool3_adjoint, k_upcat3_adjoint: the adjoints of MaxPooling3D (first maximum of each window in scan order z, y, x) and
-//     UpSampling3D + Concatenate (a fixed-order sum over each window: dz, dy, dx).
+//   * k_maxpool3_adjoint, k_upcat3_adjoint: the adjoints of MaxPooling (first maximum of each window in scan order z, y, x) and
+//     UpSampling + Concatenate (a fixed-order sum over each window: dz, dy, dx), for both models: the 2D entry points
+//     (sd_maxpool_adjoint_ndhwc_device, sd_upcat_adjoint_ndhwc_device) check their own arguments and run these kernels with D = 1.
 //
 // The losses are those of the 2D model (stardist/models/base.py:34-60, 315-325 -- the 3D model compiles the same ones): the 3D step
 // calls sd_stardist_loss2d_device of train2d.hip with n_pix = B * d * h * w, and there is no second loss kernel.
@@ -165,7 +167,8 @@ __global__ void k_dgrad3(Dgrad3Params P) {
 }
 
 // one thread per INPUT element: the gradient of its window's output goes to the window's first maximum (scan order z, y, x; a NaN
-// counts as a maximum, as in train2d.hip); elements beyond the last whole window get zero
+// counts as a maximum, as in torch's CPU max-pool); elements of a window that is not the maximum, and planes / rows / columns beyond
+// the last whole window, get zero.  A 2D pooling is D = 1, pz = 1: the scan is y, x.
 __global__ void k_maxpool3_adjoint(const float* __restrict__ x, const float* __restrict__ gout, int C, int D, int H, int W, int pz, int py,
                                    int px, long long n, float* __restrict__ gin) {
   const int Do = D / pz, Ho = H / py, Wo = W / px;
@@ -195,7 +198,7 @@ __global__ void k_maxpool3_adjoint(const float* __restrict__ x, const float* __r
 }
 
 // gcat [B][D][H][W][c0 + c1] -> g1 = its last c1 channels, g0 [B][D >> sz][H >> sy][W >> sx][c0] = the sum over each up-sampling
-// window of its first c0 channels (window order: dz, dy, dx)
+// window of its first c0 channels (window order: dz, dy, dx; 2D is D = 1, sz = 0: dy, dx)
 __global__ void k_upcat3_adjoint(const float* __restrict__ gcat, int c0, int c1, int sz, int sy, int sx, int D, int H, int W, long long n0,
                                  long long n1, float* __restrict__ g0, float* __restrict__ g1) {
   const int C = c0 + c1, D0 = D >> sz, H0 = H >> sy, W0 = W >> sx;
@@ -341,4 +344,24 @@ extern "C" int sd_upcat3d_adjoint_ndhwc_device(const float* d_gcat, int c0, int 
                      d_g0, d_g1);
   SD_LAUNCH_CHECK();
   return 0;
+}
+
+// the 2D adjoints: the 3D kernels on one plane per sample (D = 1, pz = 1, up bit 4 clear)
+extern "C" int sd_maxpool_adjoint_ndhwc_device(const float* d_in, const float* d_gout, int n_channels, int B, int H, int W, int py, int px,
+                                               float* d_gin, void* stream_) {
+  if (!d_in || !d_gout || !d_gin || n_channels <= 0 || B < 0 || H < 0 || W < 0 || py < 1 || px < 1) {
+    sd::set_error("sd_maxpool_adjoint_ndhwc: invalid arguments");
+    return -1;
+  }
+  return sd_maxpool3d_adjoint_ndhwc_device(d_in, d_gout, n_channels, B, 1, H, W, 1, py, px, d_gin, stream_);
+}
+
+extern "C" int sd_upcat_adjoint_ndhwc_device(const float* d_gcat, int c0, int up0, int c1, int B, int H, int W, float* d_g0, float* d_g1,
+                                             void* stream_) {
+  if (!d_gcat || !d_g0 || c0 <= 0 || c1 < 0 || (c1 > 0 && !d_g1) || B < 0 || H < 0 || W < 0 || (up0 & ~3) || ((up0 & 1) && (W & 1)) ||
+      ((up0 & 2) && (H & 1))) {
+    sd::set_error("sd_upcat_adjoint_ndhwc: up bits 1 (x) / 2 (y) over even sizes");
+    return -1;
+  }
+  return sd_upcat3d_adjoint_ndhwc_device(d_gcat, c0, up0, c1, B, 1, H, W, d_g0, d_g1, stream_);
 }

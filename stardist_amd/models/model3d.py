@@ -135,7 +135,7 @@ class StarDist3D(StarDistBase):
         return r[0], r[1], r[2], r[3]
 
     def train(self, X, Y, validation_data, classes="auto", augmenter=None, seed=None, epochs=None, steps_per_epoch=None, workers=1):
-        """model3d.py train on the library's own kernels (stardist_amd/training3d.py): U-Net or ResNet backbone, one input channel,
+        """model3d.py train on the library's own kernels (stardist_amd/training3d.py on the layers of stardist_amd/training.py): U-Net or ResNet backbone, one input channel,
         single class, no batch norm / dropout, 3x3x3 kernels, filter counts in multiples of 32 (at most 512 per layer), 'mae' / 'mse'
         distance loss, grid a power of two per axis, unet_pool 1 or 2 per axis, relu / linear activations, at least two convolutions
         per ResNet block -- any other configuration raises NotImplementedError naming the setting.

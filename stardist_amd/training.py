@@ -1,21 +1,25 @@
-"""StarDist2D training on the library's own kernels (the reference's StarDist2D.train, stardist/models/model2d.py, with the losses of
-stardist/models/base.py:34-60, 315-325 and the data generator StarDistData2D without shape completion).
+"""Training on the library's own kernels: StarDist2D.train (the reference's stardist/models/model2d.py train, with the losses of
+stardist/models/base.py:34-60, 315-325 and the data generator StarDistData2D without shape completion), and everything StarDist3D.train
+(training3d.py) shares with it.  The layers, the U-Net walk, the loop and the scope checks are written once for images (B, H, W, C) and
+volumes (B, D, H, W, C): an image is the D = 1, kz = 1 case of the same native calls.
 
   patches      sample_patches / get_valid_inds (stardist/sample_patches.py), StarDistDataBase.get_valid_inds (base.py:129-224) and
                csbdeep's RollingSequence.batch / utils.choice, restated with the same np.random draws in the same order: np.random.seed(s)
                gives the reference's patches.  The augmenter runs on the host, as there.
   targets      one upload of the batch's label patches; prob (edt_prob of the grid-subsampled labels) and dist (star_dist with the grid) on
                the device by sd_edt_prob_device / sd_star_dist2d_device: equal to stardist_targets() bit for bit.
-  forward      the exact-f32 kernels of inference (sd_conv3_ndhwc_device per sample, sd_maxpool_ndhwc_device and the 1x1 heads on
-               sd_convg_ndhwc_device with the batch on the depth axis) over the parameters of the model's StarDistNet; inference
-               itself (StarDistBase._net_forward) is not involved.
-  backward     csrc/train2d.hip: weight / bias gradients (sd_conv_wgrad_ndhwc_device), ReLU / max-pool / up-sampling adjoints; the data
-               gradient of a 3x3 layer is the forward kernel on the flipped, transposed kernel.
+  forward      the exact-f32 kernels of inference (sd_conv3_ndhwc_device per sample; sd_maxpool_ndhwc_device, for images with the batch
+               on the depth axis; the 1x1 heads on sd_convg_ndhwc_device with every axis before (h, w) on the depth axis) over the
+               parameters of the model's StarDistNet; inference itself (StarDistBase._net_forward) is not involved.
+  backward     weight / bias gradients by sd_conv_wgrad_ndhwc_device (3x3, and the heads) or sd_conv3_wgrad_ndhwc_device (3x3x3): two
+               partitions of the same sum, each for its shapes; the ReLU adjoint (csrc/train2d.hip); the max-pool and up-sampling
+               adjoints (sd_maxpool3d_adjoint_ndhwc_device, sd_upcat3d_adjoint_ndhwc_device of csrc/train3d.hip, D = 1 for images);
+               the data gradient of a 3x3 / 3x3x3 layer is the forward kernel on the flipped, transposed kernel.
   loss         sd_stardist_loss2d_device: both losses and their gradients in one call; in train(), sd_stardist_loss2d_metrics_device,
                which adds the reference's Keras metrics (kld, relevant_mae, relevant_mse, dist_iou_metric) in the same passes.
   optimiser    Keras' Adam (epsilon 1e-7) and ReduceLROnPlateau on val_loss, as torch element-wise updates.
-Scope: U-Net backbone, one input channel, no classes, no batch norm / dropout, 'mae' / 'mse' distance loss, no shape completion;
-check_trainable() names the first setting outside it."""
+Scope (2D): U-Net backbone, one input channel, no classes, no batch norm / dropout, 'mae' / 'mse' distance loss, no shape completion;
+check_trainable() names the first setting outside it (the settings common to every backbone first, then the U-Net's)."""
 import ctypes
 import math
 import random
@@ -175,25 +179,40 @@ class TrainData2D(object):
         return x, prob, dtm
 
 
+def _upload_labels(Y, grid, device):
+    """the start of both targets functions for the label arrays Y (one shape): (lab, neg, d_lab, d_u16) = the stacked labels on the
+    host with negative ids clipped to 0, the masks of negative labels on the grid (None if there are none), ONE int32 upload of lab
+    and its 2-byte copy (star_dist reads the labels as unsigned short: the reference's geom2d / geom3d cast with astype(np.uint16))"""
+    Y = [np.asarray(y) for y in Y]
+    on_grid = tuple(slice(None, None, int(g)) for g in grid)
+    neg = [y[on_grid] < 0 for y in Y]
+    if any(m.any() for m in neg):
+        Y = [np.maximum(y, 0) for y in Y]
+    else:
+        neg = None
+    lab = np.stack(Y)
+    if lab.size and int(lab.max()) >= 2 ** 31:
+        raise ValueError("label ids must fit int32")
+    d_lab = torch.from_numpy(np.ascontiguousarray(lab, np.int32)).to(device)
+    return lab, neg, d_lab, d_lab.to(torch.uint16).contiguous()
+
+
+def _finish_targets(prob, dist, neg):
+    """the end of both: (prob_true, dist_true_mask) from the device tensors prob and dist, prob_true = -1 where the label is negative"""
+    dtm = torch.cat([dist, prob[..., None]], dim=-1).contiguous()
+    if neg is not None:
+        prob[torch.from_numpy(np.stack(neg)).to(prob.device)] = -1
+    return prob, dtm
+
+
 def targets_device(Y, n_rays, grid, device):
     """the targets of StarDistData2D.__getitem__ (model2d.py:63-104, shape_completion=False) for the label images Y (one shape) from ONE
     upload: prob_true (B, h, w) (-1 where the label is negative) and dist_true_mask (B, h, w, n_rays + 1) on `device`"""
     from .utils import edt_prob
-    Y = [np.asarray(y) for y in Y]
     gy, gx = int(grid[0]), int(grid[1])
-    neg = [y[::gy, ::gx] < 0 for y in Y]
-    has_neg = any(m.any() for m in neg)
-    if has_neg:
-        Y = [np.maximum(y, 0) for y in Y]
-    lab = np.stack(Y)
-    if lab.size and int(lab.max()) >= 2 ** 31:
-        raise ValueError("label ids must fit int32")
+    lab, neg, d_lab, d_u16 = _upload_labels(Y, grid, device)
     B, H, W = lab.shape
-    d_lab = torch.from_numpy(np.ascontiguousarray(lab, np.int32)).to(device)
     d_sub = d_lab[:, ::gy, ::gx].contiguous()
-    # star_dist reads the labels as unsigned short (the reference's geom2d casts with astype(np.uint16)): a 2-byte copy whatever the
-    # dtype of the labels given (the upload above is int32)
-    d_u16 = d_lab.to(torch.uint16).contiguous()
     h, w = int(d_sub.shape[1]), int(d_sub.shape[2])
     prob = torch.empty((B, h, w), dtype=torch.float32, device=device)
     dist = torch.empty((B, h, w, n_rays), dtype=torch.float32, device=device)
@@ -203,78 +222,99 @@ def targets_device(Y, n_rays, grid, device):
         if (lo == hi and lo > 0) or hi > 4 * sub.size + 1024:
             prob[b] = edt_prob(d_sub[b])           # the special cases of edt_prob (constant image, sparse huge ids)
         else:
-            N.dcall(d_sub, "sd_edt_prob_device", ctypes.c_void_p(d_sub[b].data_ptr()), 1, h, w, 1.0, 1.0, 1.0, max(hi, 0),
-                    ctypes.c_void_p(prob[b].data_ptr()))
-        N.dcall(d_u16, "sd_star_dist2d_device", ctypes.c_void_p(d_u16[b].data_ptr()), H, W, int(n_rays), gy, gx, ctypes.c_void_p(dist[b].data_ptr()))
-    dtm = torch.cat([dist, prob[..., None]], dim=-1).contiguous()
-    if has_neg:
-        prob[torch.from_numpy(np.stack(neg)).to(device)] = -1
-    return prob, dtm
+            N.dcall(d_sub, "sd_edt_prob_device", _p(d_sub[b]), 1, h, w, 1.0, 1.0, 1.0, max(hi, 0), _p(prob[b]))
+        N.dcall(d_u16, "sd_star_dist2d_device", _p(d_u16[b]), H, W, int(n_rays), gy, gx, _p(dist[b]))
+    return _finish_targets(prob, dist, neg)
 
 
 # ---- scope ---------------------------------------------------------------------------------------------------------------------
-def check_trainable(config):
-    """raise NotImplementedError naming the first setting outside the scope of the native training"""
+def _multiple_of_32(c, key, no, wording="a positive multiple of 32 only"):
+    v = getattr(c, key)
+    if v % 32 != 0 or v <= 0:
+        no("%s = %d (%s)" % (key, v, wording))
+
+
+def _relu_or_linear(c, key, no):
+    if getattr(c, key) not in ("relu", "linear", None):
+        no("%s = %r (relu or linear only)" % (key, getattr(c, key)))
+
+
+def check_scope(config, nd, backbones):
+    """the checks of check_trainable (nd = 2) and check_trainable3d (nd = 3): raise NotImplementedError naming the first setting outside
+    the scope of the native training -- the settings common to every backbone, then those of the U-Net.  Returns the function that
+    raises, for the checks of another backbone."""
     c = config
+
     def no(what):
-        raise NotImplementedError("StarDist2D.train on the native kernels does not support %s" % what)
-    if getattr(c, "n_dim", 2) != 2:
-        no("n_dim = %s (2D only)" % c.n_dim)
-    if c.backbone != "unet":
-        no("backbone = %r (U-Net only)" % c.backbone)
+        raise NotImplementedError("StarDist%dD.train on the native kernels does not support %s" % (nd, what))
+    if getattr(c, "n_dim", nd) != nd:
+        no("n_dim = %s (%dD only)" % (c.n_dim, nd))
+    if c.backbone not in backbones:
+        no("backbone = %r (%s only)" % (c.backbone, "U-Net" if backbones == ("unet",) else " or ".join(backbones)))
     if c.n_classes is not None:
         no("n_classes = %r (single class only)" % (c.n_classes,))
     if c.n_channel_in != 1:
         no("n_channel_in = %d (one input channel only)" % c.n_channel_in)
-    if c.unet_batch_norm:
-        no("unet_batch_norm = True")
-    if float(getattr(c, "unet_dropout", 0.0)) != 0.0:
-        no("unet_dropout = %r" % c.unet_dropout)
     if c.train_dist_loss not in ("mae", "mse"):
         no("train_dist_loss = %r ('mae' or 'mse' only)" % c.train_dist_loss)
-    if c.train_shape_completion:
+    if getattr(c, "train_shape_completion", False):
         no("train_shape_completion = True")
-    if tuple(c.unet_kernel_size) != (3, 3):
-        no("unet_kernel_size = %s (3x3 only)" % (tuple(c.unet_kernel_size),))
-    if c.unet_n_filter_base % 32 != 0 or c.unet_n_filter_base <= 0:
-        no("unet_n_filter_base = %d (a multiple of 32 only)" % c.unet_n_filter_base)
-    if c.unet_n_filter_base * 2 ** c.unet_n_depth > 512:
-        no("unet_n_filter_base * 2**unet_n_depth = %d (at most 512 channels per layer)" % (c.unet_n_filter_base * 2 ** c.unet_n_depth))
-    if not all(p in (1, 2) for p in c.unet_pool):
-        no("unet_pool = %s (1 or 2 per axis)" % (tuple(c.unet_pool),))
-    if not all(g >= 1 and (g & (g - 1)) == 0 for g in c.grid):
-        no("grid = %s (powers of two only)" % (tuple(c.grid),))
-    if c.net_conv_after_unet % 32 != 0 or c.net_conv_after_unet <= 0:
-        no("net_conv_after_unet = %d (a positive multiple of 32 only)" % c.net_conv_after_unet)
-    for key in ("unet_activation", "unet_last_activation"):
-        if getattr(c, key) not in ("relu", "linear", None):
-            no("%s = %r (relu or linear only)" % (key, getattr(c, key)))
+    grid = tuple(int(g) for g in c.grid)
+    if not all(g >= 1 and (g & (g - 1)) == 0 for g in grid):
+        no("grid = %s (powers of two only)" % (grid,))
+    if c.backbone == "unet":
+        if c.unet_batch_norm:
+            no("unet_batch_norm = True")
+        if float(getattr(c, "unet_dropout", 0.0)) != 0.0:
+            no("unet_dropout = %r" % c.unet_dropout)
+        if tuple(c.unet_kernel_size) != (3,) * nd:
+            no("unet_kernel_size = %s (%s only)" % (tuple(c.unet_kernel_size), "x".join("3" * nd)))
+        # (the wording of the 2D message is older than the 3D one's)
+        _multiple_of_32(c, "unet_n_filter_base", no, *(("a multiple of 32 only",) if nd == 2 else ()))
+        if c.unet_n_filter_base * 2 ** c.unet_n_depth > 512:
+            no("unet_n_filter_base * 2**unet_n_depth = %d (at most 512 channels per layer)" % (c.unet_n_filter_base * 2 ** c.unet_n_depth))
+        if not all(p in (1, 2) for p in c.unet_pool):
+            no("unet_pool = %s (1 or 2 per axis)" % (tuple(c.unet_pool),))
+        _multiple_of_32(c, "net_conv_after_unet", no)
+        _relu_or_linear(c, "unet_activation", no)
+        _relu_or_linear(c, "unet_last_activation", no)
+    return no
 
 
-# ---- layers --------------------------------------------------------------------------------------------------------------------
+def check_trainable(config):
+    """raise NotImplementedError naming the first setting outside the scope of the native training"""
+    check_scope(config, 2, ("unet",))
+
+
+# ---- layers: tensors (B, H, W, C) or (B, D, H, W, C), float32; without a depth axis D = 1 and kz = 1 ----------------------------------
 _perm_cache = {}
 
 
-def _pack_perm(kind, ci, co, device):
-    """the packing of sd_conv3_pack_weights_host ('conv3') / sd_convg_pack_weights_host ('convg', 1x1) as a gather on the device:
-    (index into [0, w.flatten()...], mask of the weight positions, the weight-independent rest of the packed array -- the small-channel
-    form of the general kernel appends a tap table)"""
-    key = (kind, ci, co, str(device))
+def _pack_perm(kind, ci, co, k3, device):
+    """the packing of sd_conv3_pack_weights_host (kind 'conv3', kz = k3[0]) / sd_convg_pack_weights_host ('convg', kernel k3) as a gather
+    on the device: (index into [0, w.flatten()...], mask of the weight positions, the weight-independent rest of the packed array --
+    the small-channel form of the general kernel appends a tap table)"""
+    key = (kind, ci, co, k3, str(device))
     p = _perm_cache.get(key)
     if p is None:
         L = N.lib()
-        k = 9 if kind == "conv3" else 1
+        n_w = co * ci * int(np.prod(k3))
+        if n_w >= 2 ** 24:
+            raise ValueError("layer too large for the packing map (%d weights)" % n_w)
         outs = []
-        for src in (np.arange(1, co * ci * k + 1, dtype=np.float32), np.zeros(co * ci * k, np.float32)):
+        for src in (np.arange(1, n_w + 1, dtype=np.float32), np.zeros(n_w, np.float32)):
             if kind == "conv3":
-                out = np.zeros(max(int(L.sd_conv3_packed_floats(ci, co, 1)), 0), np.float32)
-                N.check(L.sd_conv3_pack_weights_host(N.ptr(src), ci, co, 1, N.ptr(out)))
-            else:
-                n = int(L.sd_convg_packed_floats(ci, co, 1, 1, 1))
+                n = int(L.sd_conv3_packed_floats(ci, co, k3[0]))
                 if n < 0:
-                    raise ValueError("sd_convg: unsupported 1x1 layer %d -> %d" % (ci, co))
+                    raise ValueError("sd_conv3: unsupported layer %d -> %d" % (ci, co))
                 out = np.zeros(n, np.float32)
-                N.check(L.sd_convg_pack_weights_host(N.ptr(src), ci, co, 1, 1, 1, N.ptr(out)))
+                N.check(L.sd_conv3_pack_weights_host(N.ptr(src), ci, co, k3[0], N.ptr(out)))
+            else:
+                n = int(L.sd_convg_packed_floats(ci, co, *k3))
+                if n < 0:
+                    raise ValueError("sd_convg: unsupported layer %d -> %d, kernel %s" % (ci, co, k3))
+                out = np.zeros(n, np.float32)
+                N.check(L.sd_convg_pack_weights_host(N.ptr(src), ci, co, *k3, N.ptr(out)))
             outs.append(out)
         ones, zeros = outs
         is_w = ones.view(np.uint32) != zeros.view(np.uint32)
@@ -285,9 +325,9 @@ def _pack_perm(kind, ci, co, device):
 
 
 def _packed(w, kind):
-    """packed device form of the kernel w (co, ci, k, k)"""
+    """packed device form of the kernel w (co, ci, [kz,] ky, kx)"""
     co, ci = int(w.shape[0]), int(w.shape[1])
-    idx, is_w, rest = _pack_perm(kind, ci, co, w.device)
+    idx, is_w, rest = _pack_perm(kind, ci, co, _dhw(w.shape[2:]), w.device)
     flat = torch.cat([w.new_zeros(1), w.reshape(-1)])
     return torch.where(is_w, flat.index_select(0, idx), rest).contiguous()
 
@@ -296,33 +336,44 @@ def _p(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
-def _conv3_fwd(src0, src1, wp, bias, up0, up1, co, relu):
-    B, H, W = int(src0.shape[0]), int(src0.shape[1]) << ((up0 >> 1) & 1), int(src0.shape[2]) << (up0 & 1)
-    c0, c1 = int(src0.shape[3]), (int(src1.shape[3]) if src1 is not None else 0)
-    out = torch.empty((B, H, W, co), dtype=torch.float32, device=src0.device)
+def _dhw(extents):
+    """the two or three extents as (D, H, W) integers, D = 1 when there is no depth axis"""
+    return (1,) * (3 - len(extents)) + tuple(int(v) for v in extents)
+
+
+def _conv3_fwd(src0, src1, wp, bias, up0, co, relu, res=None):
+    """the convolution on the forward kernel, one call per sample; up0: src0 is read through the up-sampling bits (1 x, 2 y, 4 z)"""
+    nd = src0.ndim - 2
+    B, (D, H, W) = int(src0.shape[0]), (n << ((up0 >> i) & 1) for n, i in zip(_dhw(src0.shape[1:-1]), (2, 1, 0)))
+    c0, c1 = int(src0.shape[-1]), (int(src1.shape[-1]) if src1 is not None else 0)
+    out = torch.empty((B,) + (D, H, W)[3 - nd:] + (co,), dtype=torch.float32, device=src0.device)
     for b in range(B):
-        N.dcall(src0, "sd_conv3_ndhwc_device", _p(src0[b]), c0, c0, up0, _p(src1[b]) if src1 is not None else None, c1, c1, up1 if src1 is not None else 0,
-                1, H, W, 1, _p(wp), _p(bias), co, int(relu), _p(out[b]))
+        args = [_p(src0[b]), c0, c0, up0, _p(src1[b]) if src1 is not None else None, c1, c1, 0, D, H, W, 3 if nd == 3 else 1, _p(wp), _p(bias)]
+        if res is None:
+            N.dcall(src0, "sd_conv3_ndhwc_device", *args, co, int(relu), _p(out[b]))
+        else:
+            N.dcall(src0, "sd_conv3_res_ndhwc_device", *args, _p(res[b]), co, co, int(relu), _p(out[b]))
     return out
 
 
-class Conv3x3(torch.autograd.Function):
-    """act(conv3x3([UpSampling(src0) | src1]) + bias): tensors (B, H, W, C) float32; up0: the forward kernels' bit mask for src0"""
+class Conv3(torch.autograd.Function):
+    """act(conv3([UpSampling(src0) | src1]) + bias (+ res)) for a 3x3 or 3x3x3 kernel (by the rank of the weight); up0: the forward
+    kernels' bit mask for src0 (1 x, 2 y, 4 z); res: the residual of a ResNet block's Add, added before the activation (or None)"""
 
     @staticmethod
-    def forward(ctx, src0, src1, weight, bias, up0, relu):
+    def forward(ctx, src0, src1, weight, bias, res, up0, relu):
         co = int(weight.shape[0])
-        y = _conv3_fwd(src0, src1, _packed(weight.detach(), "conv3"), bias.detach(), up0, 0, co, relu)
+        y = _conv3_fwd(src0, src1, _packed(weight.detach(), "conv3"), bias.detach(), up0, co, relu, res)
         ctx.save_for_backward(src0, src1, weight, y)
-        ctx.up0, ctx.relu = up0, relu
+        ctx.up0, ctx.relu, ctx.has_res = up0, relu, res is not None
         return y
 
     @staticmethod
     def backward(ctx, gy):
         src0, src1, weight, y = ctx.saved_tensors
         gy = gy.contiguous()
-        B, H, W, co = (int(v) for v in y.shape)
-        c0, c1 = int(src0.shape[3]), (int(src1.shape[3]) if src1 is not None else 0)
+        B, co, (D, H, W) = int(y.shape[0]), int(y.shape[-1]), _dhw(y.shape[1:-1])
+        c0, c1 = int(src0.shape[-1]), (int(src1.shape[-1]) if src1 is not None else 0)
         if ctx.relu:
             g = torch.empty_like(gy)
             N.dcall(gy, "sd_relu_mask_device", _p(gy), _p(y), gy.numel(), _p(g))
@@ -330,42 +381,49 @@ class Conv3x3(torch.autograd.Function):
             g = gy
         dw = torch.empty(tuple(weight.shape), dtype=torch.float32, device=g.device)         # (the torch layout, dense)
         db = torch.empty((co,), dtype=torch.float32, device=g.device)
-        N.dcall(g, "sd_conv_wgrad_ndhwc_device", _p(g), co, _p(src0), c0, ctx.up0, _p(src1), c1, 0, B, H, W, 3, _p(dw), _p(db))
+        # two partitions of the same sum, each for its shapes: the LDS-tiled kernel for images, taps spread over waves for volumes
+        if weight.ndim == 4:
+            N.dcall(g, "sd_conv_wgrad_ndhwc_device", _p(g), co, _p(src0), c0, ctx.up0, _p(src1), c1, 0, B, H, W, 3, _p(dw), _p(db))
+        else:
+            N.dcall(g, "sd_conv3_wgrad_ndhwc_device", _p(g), co, _p(src0), c0, ctx.up0, _p(src1), c1, 0, B, D, H, W, _p(dw), _p(db))
         d0 = d1 = None
         if ctx.needs_input_grad[0] or (src1 is not None and ctx.needs_input_grad[1]):
             # 'same' convolution of g with the flipped, transposed kernel = d(concatenated input)
-            wt = weight.detach().flip(2, 3).transpose(0, 1).contiguous()
-            dcat = _conv3_fwd(g, None, _packed(wt, "conv3"), None, 0, 0, c0 + c1, False)
+            wt = weight.detach().flip(*range(2, weight.ndim)).transpose(0, 1).contiguous()
+            dcat = _conv3_fwd(g, None, _packed(wt, "conv3"), None, 0, c0 + c1, False)
             if ctx.up0 or src1 is not None:
                 d0 = torch.empty_like(src0)
                 d1 = torch.empty_like(src1) if src1 is not None else None
-                N.dcall(dcat, "sd_upcat_adjoint_ndhwc_device", _p(dcat), c0, ctx.up0, c1, B, H, W, _p(d0), _p(d1))
+                N.dcall(dcat, "sd_upcat3d_adjoint_ndhwc_device", _p(dcat), c0, ctx.up0, c1, B, D, H, W, _p(d0), _p(d1))
             else:
                 d0 = dcat
-        return d0, d1, dw, db, None, None
+        return d0, d1, dw, db, (g if ctx.has_res else None), None, None
 
 
 class MaxPool(torch.autograd.Function):
-    """Keras MaxPooling2D(pool) on (B, H, W, C); the adjoint routes to the first maximum of each window"""
+    """Keras MaxPooling2D / MaxPooling3D(pool) on (B, H, W, C) / (B, D, H, W, C); the adjoint routes to the first maximum of each
+    window (scan order z, y, x)"""
 
     @staticmethod
-    def forward(ctx, x, py, px):
-        B, H, W, C = (int(v) for v in x.shape)
-        out = torch.empty((B, H // py, W // px, C), dtype=torch.float32, device=x.device)
+    def forward(ctx, x, *pool):
+        C = int(x.shape[-1])
+        pz, py, px = _dhw(pool)
+        out = torch.empty((x.shape[0],) + tuple(int(n) // p for n, p in zip(x.shape[1:-1], pool)) + (C,), dtype=torch.float32, device=x.device)
         if out.numel():
-            N.dcall(x, "sd_maxpool_ndhwc_device", _p(x), C, B, H, W, 1, py, px, _p(out))
+            # images: the whole batch in one call, the batch on the depth axis (pz = 1); volumes: one call per sample
+            for xb, ob in ([(x, out)] if x.ndim == 4 else zip(x, out)):
+                N.dcall(x, "sd_maxpool_ndhwc_device", _p(xb), C, *(int(v) for v in xb.shape[:3]), pz, py, px, _p(ob))
         ctx.save_for_backward(x)
-        ctx.pool = (py, px)
+        ctx.pool = (pz, py, px)
         return out
 
     @staticmethod
     def backward(ctx, g):
         x, = ctx.saved_tensors
         g = g.contiguous()
-        B, H, W, C = (int(v) for v in x.shape)
         gin = torch.empty_like(x)
-        N.dcall(x, "sd_maxpool_adjoint_ndhwc_device", _p(x), _p(g), C, B, H, W, ctx.pool[0], ctx.pool[1], _p(gin))
-        return gin, None, None
+        N.dcall(x, "sd_maxpool3d_adjoint_ndhwc_device", _p(x), _p(g), int(x.shape[-1]), int(x.shape[0]), *_dhw(x.shape[1:-1]), *ctx.pool, _p(gin))
+        return (gin,) + (None,) * (x.ndim - 2)
 
 
 class HeadsLoss(torch.autograd.Function):
@@ -418,15 +476,61 @@ class HeadsLoss(torch.autograd.Function):
         return dfeat, dw, db, None, None, None
 
 
-def _conv_layer(m, src0, src1=None, up0=0):
+def _conv_layer(conv, kind, src0, src1=None, up0=0, res=None):
+    """one stride-1 3x3 / 3x3x3 convolution of the network with its activation (kind 0 linear, 1 relu)"""
+    if kind not in (0, 1):
+        raise NotImplementedError("activation of layer %s" % (conv,))
+    if any(int(k) != 3 for k in conv.kernel_size) or any(int(v) != 1 for v in conv.stride):
+        raise NotImplementedError("layer %s" % (conv,))
+    return Conv3.apply(src0, src1, conv.weight, conv.bias, res, up0, kind == 1)
+
+
+def _convact(m, src0, src1=None, up0=0):
     conv, bn, kind = m.parts()
-    if bn is not None or kind not in (0, 1):
-        raise NotImplementedError("layer %s" % (m,))
-    return Conv3x3.apply(src0, src1, conv.weight, conv.bias, up0, kind == 1)
+    if bn is not None:
+        raise NotImplementedError("layer %s with batch norm" % (m,))
+    return _conv_layer(conv, kind, src0, src1, up0)
 
 
 def _up_mask(pool):
-    return (1 if pool[1] == 2 else 0) | (2 if pool[0] == 2 else 0)
+    """the forward kernels' up-sampling bits (1 x, 2 y, 4 z) of UpSampling(pool)"""
+    return sum(bit for p, bit in zip(reversed(pool), (1, 2, 4)) if p == 2)
+
+
+def unet_forward(net, x):
+    """the U-Net of StarDistNet (the grid stem net.pre, the down levels, the middle, the up levels on their skips) on the layers above"""
+    for st in net.pre:
+        for m in st["convs"]:
+            x = _convact(m, x)
+        x = MaxPool.apply(x, *st.pool)
+    bb = net.backbone
+    skips = []
+    for blk in bb.down:
+        for m in blk:
+            x = _convact(m, x)
+        skips.append(x)
+        x = MaxPool.apply(x, *bb.pool)
+    for m in bb.middle:
+        x = _convact(m, x)
+    for blk, skip in zip(bb.up, reversed(skips)):
+        x = _convact(blk[0], x, skip, _up_mask(bb.pool))
+        for m in blk[1:]:
+            x = _convact(m, x)
+    return x
+
+
+def heads_loss(net, config, x, prob_true, dtm, metrics_out):
+    """the feature convolution, the two heads as one 1x1 convolution and the losses on the backbone's output x: what train_loss
+    returns.  The heads and the losses are per pixel: every axis before the last two spatial ones folds into one."""
+    feat = _convact(net.features, x)
+    w = torch.cat([net.prob.weight, net.dist.weight], 0)
+    b = torch.cat([net.prob.bias, net.dist.bias], 0)
+    h, wd, C = (int(v) for v in feat.shape[-3:])
+    c = config
+    args = (c.train_dist_loss == "mse", c.train_loss_weights[0], c.train_loss_weights[1], c.train_background_reg, torch.is_grad_enabled(),
+            metrics_out)
+    return HeadsLoss.apply(feat.reshape(-1, h, wd, C), w, b, prob_true.reshape(-1, h, wd).contiguous(),
+                           dtm.reshape(-1, h, wd, dtm.shape[-1]).contiguous(), args)
 
 
 def train_loss(net, config, x, prob_true, dtm, metrics_out=None):
@@ -434,30 +538,7 @@ def train_loss(net, config, x, prob_true, dtm, metrics_out=None):
     float64 device vector): the network of StarDistNet evaluated on the library's exact-f32 kernels.  x (B, H, W, 1), prob_true (B, h, w),
     dtm (B, h, w, n_rays + 1) float32 device tensors.  metrics_out (a float64 device tensor of 4, optional) receives the batch's
     metrics (kld, relevant_mae, relevant_mse, dist_iou_metric)"""
-    for st in net.pre:
-        for m in st["convs"]:
-            x = _conv_layer(m, x)
-        x = MaxPool.apply(x, *st.pool)
-    bb = net.backbone
-    skips = []
-    for blk in bb.down:
-        for m in blk:
-            x = _conv_layer(m, x)
-        skips.append(x)
-        x = MaxPool.apply(x, *bb.pool)
-    for m in bb.middle:
-        x = _conv_layer(m, x)
-    for blk, skip in zip(bb.up, reversed(skips)):
-        x = _conv_layer(blk[0], x, skip, _up_mask(bb.pool))
-        for m in blk[1:]:
-            x = _conv_layer(m, x)
-    feat = _conv_layer(net.features, x)
-    w = torch.cat([net.prob.weight, net.dist.weight], 0)
-    b = torch.cat([net.prob.bias, net.dist.bias], 0)
-    c = config
-    args = (c.train_dist_loss == "mse", c.train_loss_weights[0], c.train_loss_weights[1], c.train_background_reg, torch.is_grad_enabled(),
-            metrics_out)
-    return HeadsLoss.apply(feat, w, b, prob_true.contiguous(), dtm.contiguous(), args)
+    return heads_loss(net, config, unet_forward(net, x), prob_true, dtm, metrics_out)
 
 
 # ---- optimiser -----------------------------------------------------------------------------------------------------------------
@@ -549,23 +630,33 @@ def keras_epoch_metrics(values, n_pix):
 
 def train(model, X, Y, validation_data, augmenter=None, seed=None, epochs=None, steps_per_epoch=None):
     """StarDist2D.train (see the module docstring); returns the History (a dict) of HISTORY_KEYS with one entry per epoch"""
+    def data(cfg):
+        return TrainData2D, dict(n_rays=cfg.n_rays), lambda Y, dev: targets_device(Y, cfg.n_rays, cfg.grid, dev)
+    return run_training(model, X, Y, validation_data, augmenter, seed, epochs, steps_per_epoch, check_trainable, data, train_loss)
+
+
+def run_training(model, X, Y, validation_data, augmenter, seed, epochs, steps_per_epoch, check, data, loss_fn):
+    """the body of train and train3d: check(config) for the scope, begin_training, the validation patches drawn once and cut into
+    batches with their targets, the training generator, fit.  data(config) gives (the TrainData class, its keyword arguments beyond
+    the patch settings, targets(Y, device) -> (prob_true, dist_true_mask)); loss_fn is train_loss or train_loss3d."""
     cfg = model.config
-    check_trainable(cfg)
+    check(cfg)
     epochs, steps_per_epoch = begin_training(model, validation_data, seed, epochs, steps_per_epoch)
-    data_kwargs = dict(n_rays=cfg.n_rays, patch_size=cfg.train_patch_size, grid=cfg.grid, foreground_prob=cfg.train_foreground_only,
+    Data, data_kwargs, targets = data(cfg)
+    data_kwargs = dict(data_kwargs, patch_size=cfg.train_patch_size, grid=cfg.grid, foreground_prob=cfg.train_foreground_only,
                        sample_ind_cache=cfg.train_sample_cache)
     n_data_val = len(validation_data[0])
     n_take = cfg.train_n_val_patches if cfg.train_n_val_patches is not None else n_data_val
     dev = model.device
-    data_val = TrainData2D(validation_data[0], validation_data[1], batch_size=n_take, length=1, **data_kwargs)
+    data_val = Data(validation_data[0], validation_data[1], batch_size=n_take, length=1, **data_kwargs)
     Xv, Yv = data_val.sample(0)
     bs = int(cfg.train_batch_size)
     val_batches = []
     for i in range(0, len(Xv), bs):
         xv = torch.from_numpy(np.ascontiguousarray(np.stack(Xv[i:i + bs])[..., None], np.float32)).to(dev)
-        val_batches.append((xv,) + targets_device(Yv[i:i + bs], cfg.n_rays, cfg.grid, dev) + (len(Xv[i:i + bs]),))
-    model.data_train = data_train = TrainData2D(X, Y, batch_size=bs, augmenter=augmenter, length=epochs * steps_per_epoch, **data_kwargs)
-    return fit(model, data_train, val_batches, train_loss, epochs, steps_per_epoch)
+        val_batches.append((xv,) + targets(Yv[i:i + bs], dev) + (len(Xv[i:i + bs]),))
+    model.data_train = data_train = Data(X, Y, batch_size=bs, augmenter=augmenter, length=epochs * steps_per_epoch, **data_kwargs)
+    return fit(model, data_train, val_batches, loss_fn, epochs, steps_per_epoch)
 
 
 def begin_training(model, validation_data, seed, epochs, steps_per_epoch):

@@ -2,15 +2,15 @@
 cases of test_gpu_training_scale.py still reach the regimes they were chosen for (several tiles per chunk, a ragged last chunk, the
 2^24-float workspace cap) after a change to the partition or to the cases.
 
-  wgrad2d_partition  sd_conv_wgrad_ndhwc_device, stardist_amd/csrc/train2d.hip:354-367 (8 x 32-pixel tiles, WG_TH / WG_TW :24)
-  wgrad3_partition   wgrad3_launch, stardist_amd/csrc/train3d.hip:230-245 (128 columns per workgroup, WG3_COLS :34)
+  wgrad2d_partition  sd_conv_wgrad_ndhwc_device, stardist_amd/csrc/train2d.hip:300-315 (8 x 32-pixel tiles, WG_TH / WG_TW :24)
+  wgrad3_partition   wgrad3_launch, stardist_amd/csrc/train3d.hip:232-248 (128 columns per workgroup, WG3_COLS :36)
 """
 
 WG_TH, WG_TW = 8, 32
 WG3_COLS = 128
 WS_CAP = 1 << 24                 # floats of partial sums, at most
 TARGET_WGS = 2048                # workgroups the chunk count aims at
-GRID_CAP = 65536 * 256           # threads of one element-wise launch (grid_for, train2d.hip:335, train3d.hip:224)
+GRID_CAP = 65536 * 256           # threads of one element-wise launch (grid_for, train2d.hip:283, train3d.hip:227)
 
 
 def _div_up(a, b):

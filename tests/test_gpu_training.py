@@ -18,8 +18,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _training_cases import DEV, cat64, discs as _discs, f32 as _f32, randomise as _randomise
+
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
 def _conv_case(c0, c1, co, up, k=3, B=2, H=24, W=40, seed=0):
@@ -32,19 +33,6 @@ def _conv_case(c0, c1, co, up, k=3, B=2, H=24, W=40, seed=0):
     return s0, s1, w, b, gy
 
 
-def _cat64(s0, s1, up):
-    x = s0.permute(0, 3, 1, 2)
-    if up:
-        x = F.interpolate(x, scale_factor=2.0, mode="nearest")
-    if s1 is not None:
-        x = torch.cat([x, s1.permute(0, 3, 1, 2)], 1)
-    return x
-
-
-def _f32(t):
-    return None if t is None else t.float().to(DEV).contiguous()
-
-
 def _wgrad(g, s0, s1, co, up, k):
     from stardist_amd.lib import _native as N
     from stardist_amd.training import _p
@@ -54,6 +42,10 @@ def _wgrad(g, s0, s1, co, up, k):
     db = torch.empty((co,), dtype=torch.float32, device=DEV)
     N.dcall(g, "sd_conv_wgrad_ndhwc_device", _p(g), co, _p(s0), c0, 3 if up else 0, _p(s1), c1, 0, B, H, W, k, _p(dw), _p(db))
     return dw, db
+
+
+def _cat64(s0, s1, up):
+    return cat64(s0, s1, 3 if up else 0)
 
 
 CASES = [(1, 0, 32, 0, 3), (32, 0, 32, 0, 3), (64, 0, 64, 0, 3), (64, 32, 32, 1, 3), (128, 0, 33, 0, 1)]
@@ -78,7 +70,7 @@ def test_weight_gradient(c0, c1, co, up, k):
 
 @pytest.mark.parametrize("c0, c1, co, up, k", [c for c in CASES if c[0] != 1 and c[4] == 3])      # (the heads': test_network_gradient)
 def test_data_gradient(c0, c1, co, up, k):
-    from stardist_amd.training import Conv3x3, HeadsLoss  # noqa: F401
+    from stardist_amd.training import Conv3, HeadsLoss  # noqa: F401
     s0, s1, w, b, gy = _conv_case(c0, c1, co, up, k)
     # float64 reference: relu(conv(cat(up(s0), s1))) backward
     a0 = s0.clone().requires_grad_(True)
@@ -95,7 +87,7 @@ def test_data_gradient(c0, c1, co, up, k):
     if up:
         sc0 = F.avg_pool2d(sc0, 2) * 4
     t0, t1 = _f32(s0).requires_grad_(True), (_f32(s1).requires_grad_(True) if s1 is not None else None)
-    out = Conv3x3.apply(t0, t1, _f32(w), _f32(b), 3 if up else 0, True)
+    out = Conv3.apply(t0, t1, _f32(w), _f32(b), None, 3 if up else 0, True)
     out.backward(_f32(gy))
     e0 = (t0.grad.double().cpu() - a0.grad).abs() / sc0.permute(0, 2, 3, 1).clamp_min(1e-300)
     assert float(e0.max()) <= 1e-5, float(e0.max())
@@ -104,7 +96,7 @@ def test_data_gradient(c0, c1, co, up, k):
         assert float(e1.max()) <= 1e-5, float(e1.max())
     g0 = t0.grad.clone()
     t0.grad = None
-    Conv3x3.apply(t0, t1, _f32(w), _f32(b), 3 if up else 0, True).backward(_f32(gy))
+    Conv3.apply(t0, t1, _f32(w), _f32(b), None, 3 if up else 0, True).backward(_f32(gy))
     assert torch.equal(g0, t0.grad)
 
 
@@ -160,20 +152,6 @@ def test_loss_and_gradients(dist_loss, reg):
         assert abs(float(got[i]) - float(ref[i])) <= 1e-6 * abs(float(ref[i])), (i, float(got[i]), float(ref[i]))
     assert float((gz.double().cpu() - zl.grad).norm() / zl.grad.norm()) <= 1e-6
     assert float((gd.double().cpu() - d64.grad).norm() / d64.grad.norm()) <= 1e-6
-
-
-def _discs(shape, n, seed, rmin=4, rmax=11):
-    rng = np.random.RandomState(seed)
-    y = np.zeros(shape, np.int32)
-    for i in range(1, n + 1):
-        r = rng.randint(rmin, rmax)
-        c = [rng.randint(0, s) for s in shape]
-        sl = tuple(slice(max(0, ci - r), min(s, ci + r + 1)) for ci, s in zip(c, shape))
-        g = np.ogrid[sl]
-        m = sum((gi - ci) ** 2 for gi, ci in zip(g, c)) < r * r
-        y[sl][m] = i
-    x = (y > 0).astype(np.float32) + 0.1 * rng.randn(*shape).astype(np.float32)
-    return x, y
 
 
 @pytest.mark.parametrize("dtype", [np.int32, np.uint16, np.int64])
@@ -237,13 +215,6 @@ def _demo_batch(model, seed=0, B=2, S=128):
     x = torch.from_numpy(np.stack(xs)[..., None]).to(DEV)
     pt, dtm = targets_device(ys, model.config.n_rays, model.config.grid, DEV)
     return x, pt, dtm
-
-
-def _randomise(net, seed):
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for p in net.parameters():
-            p.add_(torch.randn(p.shape, generator=g).to(p.device) * 0.02)
 
 
 def test_network_gradient():

@@ -20,32 +20,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _training_cases import DEV, balls as _balls, cat64 as _cat64, f32 as _f32, randomise as _randomise, up_nearest as _up3
+
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-
-
-def _f32(t):
-    return None if t is None else t.float().to(DEV).contiguous()
-
-
-def _up3(t, up):
-    """(B, C, d, h, w) -> nearest up-sampling by 2 along the axes of the bit mask up (1 x, 2 y, 4 z)"""
-    for axis, bit in ((2, 4), (3, 2), (4, 1)):
-        if up & bit:
-            t = t.repeat_interleave(2, dim=axis)
-    return t
 
 
 def _half(shape, up):
     D, H, W = shape
     return (D >> ((up >> 2) & 1), H >> ((up >> 1) & 1), W >> (up & 1))
-
-
-def _cat64(s0, s1, up):
-    x = _up3(s0.permute(0, 4, 1, 2, 3), up)
-    if s1 is not None:
-        x = torch.cat([x, s1.permute(0, 4, 1, 2, 3)], 1)
-    return x
 
 
 def _conv3_case(c0, c1, co, up, B=2, shape=(6, 8, 10), seed=0):
@@ -147,7 +129,7 @@ def test_general_weight_gradient(k3, s3, ci, co, shape):
 
 @pytest.mark.parametrize("c0, c1, co, up", [c for c in CONV3 if c[0] != 1])
 def test_conv3_data_gradient(c0, c1, co, up):
-    from stardist_amd.training3d import Conv3x3x3
+    from stardist_amd.training import Conv3
     s0, s1, w, b, gy = _conv3_case(c0, c1, co, up)
     a0 = s0.clone().requires_grad_(True)
     a1 = s1.clone().requires_grad_(True) if s1 is not None else None
@@ -163,7 +145,7 @@ def test_conv3_data_gradient(c0, c1, co, up):
         k = tuple(2 if up & bit else 1 for bit in (4, 2, 1))
         sc0 = F.avg_pool3d(sc0, k) * (k[0] * k[1] * k[2])
     t0, t1 = _f32(s0).requires_grad_(True), (_f32(s1).requires_grad_(True) if s1 is not None else None)
-    Conv3x3x3.apply(t0, t1, _f32(w), _f32(b), None, up, True).backward(_f32(gy))
+    Conv3.apply(t0, t1, _f32(w), _f32(b), None, up, True).backward(_f32(gy))
     e0 = (t0.grad.double().cpu() - a0.grad).abs() / sc0.permute(0, 2, 3, 4, 1).clamp_min(1e-300)
     assert float(e0.max()) <= 1e-5, float(e0.max())
     if s1 is not None:
@@ -171,7 +153,7 @@ def test_conv3_data_gradient(c0, c1, co, up):
         assert float(e1.max()) <= 1e-5, float(e1.max())
     g0 = t0.grad.clone()
     t0.grad = None
-    Conv3x3x3.apply(t0, t1, _f32(w), _f32(b), None, up, True).backward(_f32(gy))
+    Conv3.apply(t0, t1, _f32(w), _f32(b), None, up, True).backward(_f32(gy))
     assert torch.equal(g0, t0.grad)
 
 
@@ -206,7 +188,7 @@ def test_strided_data_gradient(k3, s3, ci, co, shape, relu):
 
 @pytest.mark.parametrize("pool, shape", [((2, 2, 2), (8, 10, 12)), ((2, 2, 2), (9, 11, 7)), ((1, 2, 2), (5, 10, 9))])
 def test_maxpool3d_adjoint(pool, shape):
-    from stardist_amd.training3d import MaxPool3
+    from stardist_amd.training import MaxPool
     g = torch.Generator().manual_seed(1)
     x = torch.randint(-2, 3, (2,) + shape + (32,), generator=g).float()        # many ties: the first maximum in scan order takes the gradient
     O = tuple(s // p for s, p in zip(shape, pool))
@@ -215,7 +197,7 @@ def test_maxpool3d_adjoint(pool, shape):
     ref = F.max_pool3d(xc, pool)
     ref.backward(go.permute(0, 4, 1, 2, 3))
     t = x.to(DEV).requires_grad_(True)
-    out = MaxPool3.apply(t, *pool)
+    out = MaxPool.apply(t, *pool)
     assert torch.equal(out.detach().cpu(), ref.detach().permute(0, 2, 3, 4, 1))
     out.backward(go.to(DEV))
     assert torch.equal(t.grad.cpu(), xc.grad.permute(0, 2, 3, 4, 1))
@@ -241,22 +223,6 @@ def test_upcat3d_adjoint(up):
 
 
 # ---- targets and losses
-def _balls(shape, n, seed, rmin=3, rmax=7, aniso=(1, 1, 1)):
-    """label volume of n balls (radius r / aniso per axis, later ones overwrite) and a noisy image of it"""
-    rng = np.random.RandomState(seed)
-    y = np.zeros(shape, np.int32)
-    for i in range(1, n + 1):
-        r = rng.randint(rmin, rmax)
-        c = [rng.randint(0, s) for s in shape]
-        rr = [max(1.0, r / a) for a in aniso]
-        sl = tuple(slice(max(0, int(ci - ri)), min(s, int(ci + ri) + 1)) for ci, ri, s in zip(c, rr, shape))
-        g = np.ogrid[sl]
-        m = sum(((gi - ci) / ri) ** 2 for gi, ci, ri in zip(g, c, rr)) < 1
-        y[sl][m] = i
-    x = (y > 0).astype(np.float32) + 0.1 * rng.randn(*shape).astype(np.float32)
-    return x, y
-
-
 @pytest.mark.parametrize("dtype", [np.int32, np.uint16, np.int64])
 def test_targets_equal_stardist_targets(dtype):
     from stardist_amd.rays3d import Rays_GoldenSpiral
@@ -345,13 +311,6 @@ def _batch(model, shape, seed=0, B=2):
     c = model.config
     pt, dtm = targets_device3d(ys, rays_from_json(c.rays_json), c.grid, c.anisotropy, DEV)
     return x, pt, dtm
-
-
-def _randomise(net, seed):
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for p in net.parameters():
-            p.add_(torch.randn(p.shape, generator=g).to(p.device) * 0.02)
 
 
 SHAPES = {"unet": (8, 32, 24), "resnet": (6, 18, 20)}          # the ResNet's: odd extents after the first stride

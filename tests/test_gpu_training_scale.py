@@ -8,7 +8,7 @@ on the partition formulas (_train_partition.py), that the case lists below still
     is exact and every partial sum an integer below 2^24, so f32 holds it exactly in any order, and the kernels' result must EQUAL the
     exact one.  The CPU references sum in f32 over slabs of fewer than 2^24 terms (exact for the same reason) and add the slabs in
     float64.  Covered: weight / bias gradients (sd_conv_wgrad_ndhwc_device, sd_conv3_wgrad_ndhwc_device, sd_convg_wgrad_ndhwc_device),
-    data gradients through training.Conv3x3, training3d.Conv3x3x3 and training3d.ConvG (with their ReLU masks, the many y == 0 ties of
+    data gradients through training.Conv3 (3x3 and 3x3x3 kernels) and training3d.ConvG (with their ReLU masks, the many y == 0 ties of
     integer data included), the max-pool, up-sampling / concatenation and ReLU adjoints.  Output buffers start as NaN (the kernels'
     own, and those the autograd functions allocate), so an element no thread writes fails.
   * one random-float case per weight-gradient family, with the bounds of the smaller tests (1e-5 of sum |terms|);
@@ -28,8 +28,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _training_cases import DEV, discs as _discs, randomise
+
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # ---- the cases (plain tuples, importable without a GPU: test_cpu_training_partition.py checks their regimes) ---------------------
@@ -55,8 +56,8 @@ WGRAD3 = [
     ("conv3", 2, (48, 48, 48), 64, 64, (3, 3, 3), (1, 1, 1)),      # 63 rows per chunk, the last of 9
     ("convg", 2, (47, 50, 46), 32, 64, (3, 3, 3), (2, 2, 2)),      # odd extents
 ]
-# data gradients: 2D Conv3x3 (B, H, W, c0, c1, c_out, up); 3D ConvG (B, (D, H, W), c_in, c_out, kernel, stride);
-# 3D Conv3x3x3 (B, (D, H, W), c0, c1, c_out, up)
+# data gradients: Conv3 on images (B, H, W, c0, c1, c_out, up); 3D ConvG (B, (D, H, W), c_in, c_out, kernel, stride);
+# Conv3 on volumes (B, (D, H, W), c0, c1, c_out, up)
 DGRAD2D = [(8, 256, 256, 64, 32, 32, 1)]
 DGRAD3G = [(2, (48, 96, 96), 32, 64, (3, 3, 3), (1, 2, 2))]
 DGRAD3 = [(1, (48, 96, 96), 64, 32, 32, 7)]
@@ -343,7 +344,7 @@ def test_wgrad3_random_floats(case):
 # ---- data gradients ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", DGRAD2D, ids=str)
 def test_conv3x3_backward_exact(case):
-    from stardist_amd.training import Conv3x3
+    from stardist_amd.training import Conv3
     B, H, W, c0, c1, co, up = case
     s0, s1 = _tern((B, H >> up, W >> up, c0), 11), _tern((B, H, W, c1), 12)
     w, b = _tern((co, c0 + c1, 3, 3), 13), _tern((co,), 14)
@@ -361,7 +362,7 @@ def test_conv3x3_backward_exact(case):
         t0, t1 = s0.to(DEV).requires_grad_(True), s1.to(DEV).requires_grad_(True)
         tw.grad = tb.grad = None
         with _nan_empty():
-            out = Conv3x3.apply(t0, t1, tw, tb, 3 if up else 0, True)
+            out = Conv3.apply(t0, t1, tw, tb, None, 3 if up else 0, True)
             out.backward(tgy)
         grads.append([t0.grad, t1.grad, tw.grad, tb.grad])
     _same(out.detach(), y, "forward")
@@ -400,7 +401,7 @@ def test_convg_backward_exact(case, relu):
 
 @pytest.mark.parametrize("case", DGRAD3, ids=str)
 def test_conv3x3x3_backward_exact(case):
-    from stardist_amd.training3d import Conv3x3x3
+    from stardist_amd.training import Conv3
     B, shape, c0, c1, co, up = case
     half = tuple(n >> ((up >> bit) & 1) for n, bit in zip(shape, (2, 1, 0)))
     s0, s1 = _tern((B,) + half + (c0,), 31), _tern((B,) + shape + (c1,), 32)
@@ -419,7 +420,7 @@ def test_conv3x3x3_backward_exact(case):
         t0, t1 = s0.to(DEV).requires_grad_(True), s1.to(DEV).requires_grad_(True)
         tw.grad = tb.grad = None
         with _nan_empty():
-            out = Conv3x3x3.apply(t0, t1, tw, tb, None, up, True)
+            out = Conv3.apply(t0, t1, tw, tb, None, up, True)
             out.backward(tgy)
         grads.append([t0.grad, t1.grad, tw.grad, tb.grad])
     _same(out.detach(), y, "forward")
@@ -577,28 +578,12 @@ def test_losses_at_scale(R, bshape, dist_loss, reg, mask_kind, metrics):
 
 
 # ---- one step of the demo configurations ---------------------------------------------------------------------------------------
-def _discs(shape, n, seed, rmin=4, rmax=11):
-    rng = np.random.RandomState(seed)
-    y = np.zeros(shape, np.int32)
-    for i in range(1, n + 1):
-        r = rng.randint(rmin, rmax)
-        c = [rng.randint(0, s) for s in shape]
-        sl = tuple(slice(max(0, ci - r), min(s, ci + r + 1)) for ci, s in zip(c, shape))
-        g = np.ogrid[sl]
-        m = sum(((gi - ci) / 1.0) ** 2 for gi, ci in zip(g, c)) < r * r
-        y[sl][m] = i
-    x = (y > 0).astype(np.float32) + 0.1 * rng.randn(*shape).astype(np.float32)
-    return x, y
-
-
 def _randomise(net, seed):
     """the smaller tests' perturbation of the initial weights, and a prob head scaled down: at these shapes the initial networks' logits
     reach saturated probabilities, where the float32 sigmoid of the training step (as in Keras) alone moves every parameter's gradient
     by ~1 % from the float64 one (torch's float32 CPU autograd of the same network shows the same); the step is compared away from it"""
-    g = torch.Generator().manual_seed(seed)
+    randomise(net, seed)
     with torch.no_grad():
-        for p in net.parameters():
-            p.add_(torch.randn(p.shape, generator=g).to(p.device) * 0.02)
         net.prob.weight.mul_(0.1)
         net.prob.bias.zero_()
 

@@ -539,6 +539,25 @@ int sd_maxpool3d_adjoint_ndhwc_device(const float* d_in, const float* d_gout, in
 int sd_upcat3d_adjoint_ndhwc_device(const float* d_gcat, int c0, int up0, int c1, int B, int D, int H, int W, float* d_g0, float* d_g1,
                                     void* stream);
 
+/* ---- image normalisation (csbdeep.utils.normalize / normalize_mi_ma; csrc/normalize.hip) --------------------------------------
+ * d_x: a contiguous array of n_seg interleaved segments of n elements each (element i belongs to segment i % n_seg: a channels-last image
+ * whose statistics are taken over every axis but the last; n_seg = 1: over the whole array).  dtype: 0 = uint8, 1 = uint16, 2 = float32.
+ *
+ * sd_percentiles_device: d_out[seg * n_q + j] = float32(np.percentile(segment seg, h_q[j])) (method 'linear'), bit for bit: exact order
+ *   statistics by radix selection on order-preserving keys (one histogram pass for uint8 / uint16, three for float32), then numpy's
+ *   interpolation between the two neighbouring order statistics.  h_q: n_q percentiles in [0, 100] on the host, 2 <= n_q <= 3.
+ *   interp_f32 (float32 data only): 1 = virtual index, weight and interpolation in float32 -- what numpy >= 2.0 does for float32 data
+ *   and a Python-scalar q; 0 = in float64, rounded to float32 at the end (numpy < 2.0, or q given as float64 array).  Integer data
+ *   always interpolate in float64.  A NaN anywhere in a float32 segment gives NaN for that segment.  1 <= n_seg <= 64, n >= 1.
+ *   Integer counting only: the same bits from call to call.  Nothing is copied to the host and the stream is not synchronised.
+ * sd_normalize_mi_ma_device: d_out[i] = (float32(x[i]) - mi) / (ma - mi + eps) with mi = d_mi[i % n_seg], ma = d_ma[i % n_seg] read from
+ *   device memory, float32 operations in this order with a correctly rounded division; clip != 0: then limited to [0, 1] as np.clip does
+ *   (NaN stays).  d_out may be d_x for float32 input. */
+int sd_percentiles_device(const void* d_x, int dtype, long long n, int n_seg, const double* h_q, int n_q, int interp_f32, float* d_out,
+                          void* stream);
+int sd_normalize_mi_ma_device(const void* d_x, int dtype, long long n, int n_seg, const float* d_mi, const float* d_ma, float eps, int clip,
+                              float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -559,9 +559,17 @@ class StarDistBase(object):
             raise ValueError("entry of n_tiles > 1 only allowed for axes '%s'" % axes_net.replace("C", ""))
         n_tiles = tuple(nt.get(a, 1) for a in axes_net)
         _permute_axes = self._make_permute_axes(axes, axes_net)
-        if normalizer is not None:
+        if normalizer is not None and self.device.type == "cuda" and callable(getattr(normalizer, "before_device", None)) \
+                and "C" not in axes_net[:-1] and (N.is_torch(img) or (isinstance(img, np.ndarray) and
+                                                                      img.dtype in (np.uint8, np.uint16, np.float32))):
+            # a normaliser of stardist_amd.utils on a HIP device: the RAW image goes up (a uint16 image is half the bytes of its float32
+            # form) and is normalised there (csrc/normalize.hip: same values as the host's), with no host synchronisation.  A host image of
+            # any other dtype has no kernel: it is normalised on the host below and uploaded once, as float32
+            x = img if N.is_torch(img) else to_device(img, self.device)
+            x = normalizer.before_device(_permute_axes(x.to(self.device)), axes_net)
+        elif normalizer is not None:
             # csbdeep Normalizer protocol: .before(x, axes) on the host array
-            x_host = _permute_axes(np.asarray(img))
+            x_host = _permute_axes(np.asarray(img.cpu() if N.is_torch(img) else img))
             x_host = normalizer.before(x_host, axes_net)
             x = to_device(x_host, self.device)
         else:
@@ -941,12 +949,15 @@ class StarDistBase(object):
         overlapped with the step on image k (the reference reads block k + 1 while it works on block k only in its big-image loop,
         stardist/big.py:312-326; a plain loop over predict_instances pays the host -> device copy of every input in front of its step).
         A helper thread copies the next array into page-locked memory (numpy copy: releases the GIL) and enqueues the device copy on
-        its own stream; the step waits for that copy's event only.  Images that need host-side preparation (a `normalizer`, `scale`)
-        and device tensors are passed through unchanged.  Results are those of predict_instances(img, **kwargs), image by image."""
+        its own stream; the step waits for that copy's event only.  Images that need host-side preparation (`scale`, a `normalizer`
+        without `before_device`) and device tensors are passed through unchanged; a normaliser of stardist_amd.utils works on the
+        uploaded raw image.  Results are those of predict_instances(img, **kwargs), image by image."""
         import queue
         import threading
         import torch
-        if self.device.type != "cuda" or kwargs.get("normalizer") is not None or kwargs.get("scale") is not None:
+        nrm = kwargs.get("normalizer")
+        if self.device.type != "cuda" or (nrm is not None and not callable(getattr(nrm, "before_device", None))) \
+                or kwargs.get("scale") is not None:
             for img in imgs:
                 yield self.predict_instances(img, **kwargs)
             return

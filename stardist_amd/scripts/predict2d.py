@@ -23,7 +23,7 @@ Prediction script for a 2D stardist model, usage: stardist-predict2d -i input.ti
 
     from stardist_amd.models import StarDist2D, pretrained
     from stardist_amd.scripts._io import imread, imwrite
-    from stardist_amd.utils import normalize
+    from stardist_amd.utils import normalize, to_device
 
     if pathlib.Path(args.model).is_dir():
         p = pathlib.Path(args.model).resolve()
@@ -53,7 +53,11 @@ Prediction script for a 2D stardist model, usage: stardist-predict2d -i input.ti
             raise ValueError("dimension of input (%d) not the same as length of given axes (%d)" % (img.ndim, len(axes)))
         if args.verbose:
             print("loaded image of size %s\nnormalizing..." % (img.shape,))
-        img = normalize(img, *args.pnorm)
+        if model.device.type == "cuda" and str(img.dtype) in ("uint8", "uint16", "float32"):
+            # the raw image goes up and is normalised on the device (same values as the host's: csrc/normalize.hip)
+            img = normalize(to_device(img, model.device), *args.pnorm)
+        else:
+            img = normalize(img, *args.pnorm)
         n_tiles = args.n_tiles
         if n_tiles is not None and len(n_tiles) != img.ndim:          # the option names the spatial axes only
             sp = iter(n_tiles)

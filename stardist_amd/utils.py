@@ -30,8 +30,110 @@ def _raise(e):
     raise e
 
 
+def _is_device_tensor(x):
+    return type(x).__module__.startswith("torch") and hasattr(x, "is_cuda") and x.is_cuda
+
+
+# element type codes of sd_percentiles_device / sd_normalize_mi_ma_device
+_DEVICE_DTYPE_CODE = {"torch.uint8": 0, "torch.uint16": 1, "torch.float32": 2}
+_NUMPY_2 = int(np.__version__.split(".")[0]) >= 2
+
+
+def _device_segments(x, axis):
+    """number of interleaved segments of a device tensor for statistics over `axis`, or None where the kernels do not apply: 1 for
+    axis=None (or every axis), the size of the last axis for "every axis but the last" """
+    if str(x.dtype) not in _DEVICE_DTYPE_CODE or x.numel() == 0:
+        return None
+    if axis is None:
+        return 1
+    try:
+        ax = sorted(set(a % x.dim() for a in ((axis,) if np.isscalar(axis) else tuple(axis))))
+    except (TypeError, ZeroDivisionError):
+        return None
+    if ax == list(range(x.dim())):
+        return 1
+    if x.dim() >= 2 and ax == list(range(x.dim() - 1)):
+        return int(x.shape[-1]) if 1 <= int(x.shape[-1]) <= 64 else None
+    return None
+
+
+def _interp_mode(x, q):
+    """how np.percentile interpolates for this data and this q (sd_percentiles_device's interp_f32), or None if q is not a plain scalar:
+    numpy >= 2.0 divides a Python-scalar q by 100 in the dtype of float data, so for float32 data the virtual index, the weight and the
+    interpolation are float32; a numpy float64 or integer scalar is no such weak scalar (np.float64 IS a Python float by inheritance,
+    hence the exact types) and makes everything float64, as integer data do.  Other q (np.float32, float16, arrays) go to the host."""
+    if type(q) in (int, float):
+        return 1 if (_NUMPY_2 and str(x.dtype) == "torch.float32") else 0
+    if type(q) is np.float64 or (isinstance(q, np.integer) and not isinstance(q, np.bool_)):
+        return 0
+    return None
+
+
+def _percentiles_device(x, qs, n_seg, interp):
+    """(n_seg, len(qs)) float32 device tensor of np.percentile values of the contiguous device tensor x (csrc/normalize.hip)"""
+    import ctypes
+    import torch
+    from .lib import _native as N
+    out = torch.empty((n_seg, len(qs)), dtype=torch.float32, device=x.device)
+    q = (ctypes.c_double * len(qs))(*[float(v) for v in qs])
+    N.dcall(x, "sd_percentiles_device", ctypes.c_void_p(x.data_ptr()), _DEVICE_DTYPE_CODE[str(x.dtype)], x.numel() // n_seg, n_seg,
+            ctypes.cast(q, ctypes.c_void_p), len(qs), interp, ctypes.c_void_p(out.data_ptr()))
+    return out
+
+
+def _rescale_device(x, mi, ma, n_seg, clip, eps):
+    """float32 device tensor (x - mi) / (ma - mi + eps) of the contiguous device tensor x; mi, ma: contiguous float32 device tensors of
+    n_seg values"""
+    import ctypes
+    import torch
+    from .lib import _native as N
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if x.numel():
+        N.dcall(x, "sd_normalize_mi_ma_device", ctypes.c_void_p(x.data_ptr()), _DEVICE_DTYPE_CODE[str(x.dtype)], x.numel() // n_seg, n_seg,
+                ctypes.c_void_p(mi.data_ptr()), ctypes.c_void_p(ma.data_ptr()), float(np.float32(eps)), int(bool(clip)),
+                ctypes.c_void_p(out.data_ptr()))
+    return out
+
+
+def _bound_device(v, x):
+    """a normalisation bound (scalar, numpy array or tensor) as (contiguous float32 device tensor, n_seg), or None if its shape is neither
+    one value nor one value per entry of x's last axis"""
+    import torch
+    if np.isscalar(v):
+        return torch.tensor([np.float32(v)], dtype=torch.float32, device=x.device), 1
+    if not _is_device_tensor(v):
+        if type(v).__module__.startswith("torch"):
+            v = v.numpy()
+        v = torch.as_tensor(np.ascontiguousarray(np.asarray(v).astype(np.float32, copy=False)), device=x.device)
+    if v.dim() > x.dim():
+        return None
+    if v.dtype != torch.float32:
+        v = v.to(torch.float32)
+    if v.numel() == 1:
+        return v.reshape(1).contiguous(), 1
+    if x.dim() >= 2 and v.numel() == x.shape[-1] and v.shape[-1] == x.shape[-1]:
+        return v.reshape(-1).contiguous(), int(x.shape[-1])
+    return None
+
+
+def _via_host(fn, x, *args, **kwargs):
+    """the host function on a device tensor (dtypes and axes the kernels do not cover): same values, device tensor out"""
+    import torch
+    args = [a.cpu().numpy() if type(a).__module__.startswith("torch") else a for a in args]
+    return torch.as_tensor(np.ascontiguousarray(fn(x.cpu().numpy(), *args, **kwargs)), device=x.device)
+
+
 def normalize_mi_ma(x, mi, ma, clip=False, eps=1e-20, dtype=np.float32):
-    """csbdeep.utils.normalize_mi_ma (csbdeep>=0.8.0, caller side of predict_instances)."""
+    """csbdeep.utils.normalize_mi_ma (csbdeep>=0.8.0, caller side of predict_instances).  numpy in -> numpy out.  A tensor on a HIP device
+    in -> a float32 tensor on that device out, with the values of the host expression bit for bit: one fused kernel
+    (csrc/normalize.hip) for uint8 / uint16 / float32 data with one bound, or one per entry of the last axis; anything else through the
+    host expression."""
+    if _is_device_tensor(x):
+        if dtype is np.float32 and str(x.dtype) in _DEVICE_DTYPE_CODE and np.isscalar(eps):
+            lo, hi = _bound_device(mi, x), _bound_device(ma, x)
+            if lo is not None and hi is not None and lo[1] == hi[1] and 1 <= lo[1] <= 64:
+                return _rescale_device(x.contiguous(), lo[0], hi[0], lo[1], clip, eps)
+        return _via_host(normalize_mi_ma, x, mi, ma, clip=clip, eps=eps, dtype=dtype)
     if dtype is not None:
         x = x.astype(dtype, copy=False)
         mi = dtype(mi) if np.isscalar(mi) else mi.astype(dtype, copy=False)
@@ -43,11 +145,140 @@ def normalize_mi_ma(x, mi, ma, clip=False, eps=1e-20, dtype=np.float32):
     return x
 
 
+def _normalize_device(x, pmin, pmax, axis, clip, eps, dtype):
+    """(normalised float32 tensor, mi, ma) of a device tensor through the two kernels, mi / ma as (n_seg,) float32 device tensors; None
+    where they do not apply.  Nothing is copied to the host: the bounds stay on the device and the rescale reads them there."""
+    if dtype is not np.float32 or not np.isscalar(eps):
+        return None
+    n_seg = _device_segments(x, axis)
+    mode_lo, mode_hi = _interp_mode(x, pmin), _interp_mode(x, pmax)
+    if n_seg is None or mode_lo is None or mode_lo != mode_hi:
+        return None
+    if not (0 <= pmin <= 100 and 0 <= pmax <= 100):
+        raise ValueError("Percentiles must be in the range [0, 100]")
+    x = x.contiguous()
+    mima = _percentiles_device(x, (pmin, pmax), n_seg, mode_lo)
+    if n_seg == 1:
+        mi, ma = mima[0, 0:1], mima[0, 1:2]
+    else:
+        mi, ma = mima[:, 0].contiguous(), mima[:, 1].contiguous()
+    return _rescale_device(x, mi, ma, n_seg, clip, eps), mi, ma
+
+
 def normalize(x, pmin=3, pmax=99.8, axis=None, clip=False, eps=1e-20, dtype=np.float32):
-    """csbdeep.utils.normalize: percentile-based image normalization."""
+    """csbdeep.utils.normalize: percentile-based image normalization.  numpy in -> numpy out.  A tensor on a HIP device in -> a float32
+    tensor on that device out, equal bit for bit to the host result: exact percentiles by radix selection and a fused rescale
+    (csrc/normalize.hip) for uint8 / uint16 / float32 data and axis = None or "every axis but the last", asynchronously (no copy to the
+    host); any other dtype or axis through the host functions."""
+    if _is_device_tensor(x):
+        res = _normalize_device(x, pmin, pmax, axis, clip, eps, dtype)
+        if res is not None:
+            return res[0]
+        return _via_host(normalize, x, pmin, pmax, axis=axis, clip=clip, eps=eps, dtype=dtype)
     mi = np.percentile(x, pmin, axis=axis, keepdims=True)
     ma = np.percentile(x, pmax, axis=axis, keepdims=True)
     return normalize_mi_ma(x, mi, ma, clip=clip, eps=eps, dtype=dtype)
+
+
+# ----------------------------------------------------------------------------- normalisers for predict(..., normalizer=)
+class NoNormalizer(object):
+    """csbdeep.data.NoNormalizer: leaves the image as it is (before), and the prediction too (after)"""
+
+    def __init__(self, do_after=False):
+        self._do_after = do_after
+
+    def before(self, x, axes):
+        return x
+
+    before_device = before
+
+    def after(self, mean, scale, axes):
+        self.do_after or _raise(ValueError())
+        return mean, scale
+
+    @property
+    def do_after(self):
+        return self._do_after
+
+
+class PercentileNormalizer(object):
+    """csbdeep.data.PercentileNormalizer: `before(x, axes)` normalises with the percentiles pmin / pmax taken over every axis whose letter
+    is not 'C' and keeps them as self.mi / self.ma; `after(mean, scale, axes)` maps a prediction back (alpha = ma - mi, beta = mi).
+    **kwargs go to normalize_mi_ma (clip, eps).  `before_device` is `before` for a tensor on a HIP device: percentiles and rescale run
+    there (stardist_amd.utils.normalize), self.mi / self.ma stay device tensors."""
+
+    def __init__(self, pmin=2, pmax=99.8, do_after=True, dtype=np.float32, **kwargs):
+        (np.isscalar(pmin) and np.isscalar(pmax) and 0 <= pmin < pmax <= 100) or _raise(ValueError())
+        self.pmin = pmin
+        self.pmax = pmax
+        self._do_after = do_after
+        self.dtype = dtype
+        self.kwargs = kwargs
+
+    def before(self, x, axes):
+        if _is_device_tensor(x):
+            return self.before_device(x, axes)
+        self.axes_before = axes
+        axis = tuple(d for d, a in enumerate(axes) if a != "C")
+        self.mi = np.percentile(x, self.pmin, axis=axis, keepdims=True).astype(self.dtype, copy=False)
+        self.ma = np.percentile(x, self.pmax, axis=axis, keepdims=True).astype(self.dtype, copy=False)
+        return normalize_mi_ma(x, self.mi, self.ma, dtype=self.dtype, **self.kwargs)
+
+    def before_device(self, x, axes):
+        import torch
+        self.axes_before = axes
+        axis = tuple(d for d, a in enumerate(axes) if a != "C")
+        res = None
+        if set(self.kwargs) <= {"clip", "eps"} and len(axes) == x.dim() and "C" not in axes[:-1]:
+            res = _normalize_device(x, self.pmin, self.pmax, axis if "C" in axes else None, self.kwargs.get("clip", False),
+                                    self.kwargs.get("eps", 1e-20), self.dtype)
+        if res is None:
+            out = torch.as_tensor(np.ascontiguousarray(self.before(x.cpu().numpy(), axes)), device=x.device)
+            return out
+        keep = tuple(x.shape[d] if a == "C" else 1 for d, a in enumerate(axes))
+        self.mi, self.ma = res[1].reshape(keep), res[2].reshape(keep)
+        return res[0]
+
+    def after(self, mean, scale, axes):
+        self.do_after or _raise(ValueError())
+        self.axes_after = axes
+        mi, ma = (v.cpu().numpy() if type(v).__module__.startswith("torch") else v for v in (self.mi, self.ma))
+        alpha = ma - mi
+        beta = mi
+        return (alpha * mean + beta).astype(self.dtype, copy=False), \
+            (alpha * scale if scale is not None else None)
+
+    @property
+    def do_after(self):
+        return self._do_after
+
+
+class MiMaNormalizer(object):
+    """Normaliser with fixed bounds: before(x, axes) = normalize_mi_ma(x, mi, ma, ...).  For the block-wise predictors
+    (predict_instances_big), where percentiles taken per block would differ from block to block: take mi / ma once for the whole image
+    (np.percentile of a sample, or of the image) and pass them here."""
+
+    def __init__(self, mi, ma, do_after=True, dtype=np.float32, **kwargs):
+        self.mi = mi
+        self.ma = ma
+        self._do_after = do_after
+        self.dtype = dtype
+        self.kwargs = kwargs
+
+    def before(self, x, axes):
+        return normalize_mi_ma(x, self.mi, self.ma, dtype=self.dtype, **self.kwargs)
+
+    before_device = before
+
+    def after(self, mean, scale, axes):
+        self.do_after or _raise(ValueError())
+        alpha = np.asarray(self.ma, self.dtype) - np.asarray(self.mi, self.dtype)
+        beta = np.asarray(self.mi, self.dtype)
+        return (alpha * mean + beta).astype(self.dtype, copy=False), (alpha * scale if scale is not None else None)
+
+    @property
+    def do_after(self):
+        return self._do_after
 
 
 def to_host(t):

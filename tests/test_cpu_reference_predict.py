@@ -102,17 +102,13 @@ def mirror_model(nd, kw, graph):
 
 def _select_standin(prob, dist, prob_thresh, bs):
     """the contract of the selection native (sd_select_candidates_device, csrc/select.hip: strict threshold, border of (lo, hi) grid steps per
-    axis, np.where order, max(1e-3, dist)) as numpy -- there is no GPU here and the product has no CPU path; what this test pins is the
-    HOST logic of predict_sparse around it (axes, pad / crop, grid scaling, filter_points, class rows); the native itself is pinned on
-    the GPU (tests/test_gpu_glue.py)"""
+    axis, np.where order, max(1e-3, dist)) as numpy (_exact.select_numpy) -- there is no GPU here and the product has no CPU path; what this
+    test pins is the HOST logic of predict_sparse around it (axes, pad / crop, grid scaling, filter_points, class rows); the native itself
+    is compared with the same numpy statement on the GPU (tests/test_gpu_glue.py::test_select_candidates_matches_numpy)"""
     import torch
-    p = prob.numpy()
-    mask = p > np.float32(prob_thresh)
-    inner = np.zeros_like(mask)
-    inner[tuple(slice(lo if lo > 0 else None, -hi if hi > 0 else None) for lo, hi in bs)] = True
-    mask &= inner
-    pts = np.stack(np.nonzero(mask), 1).astype(np.int64)
-    return torch.from_numpy(p[mask]), torch.from_numpy(np.maximum(np.float32(1e-3), dist.numpy()[mask])), torch.from_numpy(pts)
+    from _exact import select_numpy
+    p, d, pts = select_numpy(prob.numpy(), dist.numpy(), prob_thresh, bs)
+    return torch.from_numpy(p), torch.from_numpy(d), torch.from_numpy(pts)
 
 
 def _gap_threshold(prob, lo=0.35, hi=0.65):

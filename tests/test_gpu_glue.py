@@ -1,6 +1,7 @@
 """GPU: the glue natives and host paths added in round 5, each against the numpy statement of the reference line it replaces:
 sd_sorted_rows_device (score order -> feature rows + pixel coordinates), sd_dist_to_coord_device (geom2d.py:130-146 in numpy's
-arithmetic), predict_instances_iter (uploads overlapped; same results as predict_instances per image), to_host_many."""
+arithmetic), predict_instances_iter (uploads overlapped; same results as predict_instances per image), to_host_many; and
+sd_select_candidates_device (threshold + border + ordered compaction) against its numpy statement (_exact.select_numpy)."""
 import ctypes
 
 import numpy as np
@@ -175,3 +176,61 @@ def test_predict_instances_2d_fused_survivors_equal_generic_path():
     assert np.array_equal(lab1, lab2)
     for k in ("coord", "points", "prob"):
         assert res1[k].dtype == res2[k].dtype and np.array_equal(res1[k], res2[k]), k
+
+
+# shape, borders (lo, hi) per axis
+SELECT = [((5000,), ((0, 0),)), ((1024,), ((3, 0),)), ((1023,), ((0, 5),)), ((37, 91), ((2, 2), (2, 2))), ((64, 50), ((0, 3), (4, 0))),
+          ((33, 1025), ((1, 0), (0, 1))), ((9, 20, 33), ((2, 2), (2, 2), (2, 2))), ((5, 41, 67), ((0, 1), (3, 0), (0, 0))),
+          ((7, 30), ((4, 3), (0, 0))), ((6, 30), ((0, 0), (40, 0))), ((11, 13, 17), ((1, 1), (6, 7), (1, 1)))]      # the last three: nothing is left
+
+
+@pytest.mark.parametrize("shape,bs", SELECT, ids=str)
+@pytest.mark.parametrize("kind", ["mixed", "all", "none"])
+def test_select_candidates_matches_numpy(shape, bs, kind):
+    """sd_select_candidates_device (csrc/select.hip) == the numpy statement of its contract (_exact.select_numpy): strict threshold --
+    probabilities equal to it and NaNs are not selected --, asymmetric borders, np.where order, distances clamped at 1e-3, both write paths
+    (with distance rows of 1 / 32 / 96 / 100 rays; without); the outputs start as NaN / -1, so only what the contract names may be written;
+    with a capacity below the count the count is still the full count and nothing at or beyond the capacity is written"""
+    import torch
+    from _exact import select_numpy
+    from stardist_amd.lib import _native as N
+    dev = torch.device("cuda:0")
+    rng = np.random.RandomState(len(shape) * 100 + shape[0])
+    thr = np.float32(0.4)
+    prob = rng.rand(*shape).astype(np.float32)
+    if kind == "mixed":
+        prob[rng.rand(*shape) < 0.1] = thr                      # ties with the threshold
+        prob[rng.rand(*shape) < 0.05] = np.nan
+    elif kind == "all":
+        prob = thr + np.float32(0.1) + prob
+    else:
+        prob = np.minimum(prob, thr)
+    nd = len(shape)
+    tshape, tb = np.asarray(shape, np.int32), np.asarray([v for pair in bs for v in pair], np.int32)
+    tp = torch.from_numpy(prob).to(dev)
+    for R in (0, 1, 32, 96, 100):
+        dist = None
+        if R:
+            dist = (rng.rand(*shape, R).astype(np.float32) * 10 - 1).astype(np.float32)
+            dist.reshape(-1)[::7] = 1e-3
+            dist.reshape(-1)[3::11] = 5e-4
+        want_p, want_d, want_pts = select_numpy(prob, dist, thr, bs)
+        n = len(want_p)
+        assert (n > 0) == (kind != "none" and all(lo + hi < s for s, (lo, hi) in zip(shape, bs)))
+        td = torch.from_numpy(dist).to(dev) if R else None
+        for cap in sorted({n + 5, n, max(n // 2, 1)}):
+            op = torch.full((cap,), float("nan"), dtype=torch.float32, device=dev)
+            od = torch.full((cap, R), float("nan"), dtype=torch.float32, device=dev) if R else None
+            opts = torch.full((cap, nd), -1, dtype=torch.int32, device=dev)
+            cnt = torch.full((1,), -7, dtype=torch.int32, device=dev)
+            N.dcall(tp, "sd_select_candidates_device", _vp(tp), _vp(td), nd, N.ptr(tshape), N.ptr(tb), R, float(thr), cap, _vp(op), _vp(od),
+                    _vp(opts), _vp(cnt))
+            assert int(cnt.item()) == n, (int(cnt.item()), n, cap)
+            m = min(n, cap)
+            gp, gpts = op.cpu().numpy(), opts.cpu().numpy()
+            assert np.array_equal(gp[:m], want_p[:m]) and np.isnan(gp[m:]).all()
+            assert np.array_equal(gpts[:m], want_pts[:m]) and (gpts[m:] == -1).all()
+            if R:
+                gd = od.cpu().numpy()
+                assert np.array_equal(gd[:m], want_d[:m]) and np.isnan(gd[m:]).all()
+                assert m == 0 or float(gd[:m].min()) >= np.float32(1e-3)

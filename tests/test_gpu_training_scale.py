@@ -18,7 +18,6 @@ on the partition formulas (_train_partition.py), that the case lists below still
   * one train_loss step of the 2D_demo topology at B = 8, 272 x 272 and one of the 3D_demo configuration at its training shape, against
     float64 autograd of StarDistNet (every parameter within 1e-4 norm-wise; the loss within 1e-5, 1e-4 in 3D as in
     test_gpu_training3d.py), with a prob head scaled down (see _randomise)."""
-import contextlib
 import copy
 import json
 import os
@@ -28,6 +27,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _exact import nan_empty as _nan_empty
 from _training_cases import DEV, discs as _discs, randomise
 
 pytestmark = pytest.mark.gpu
@@ -110,22 +110,6 @@ def _p(t):
 def _call(name, anchor, *args):
     from stardist_amd.lib import _native as N
     N.dcall(anchor, name, *args)
-
-
-@contextlib.contextmanager
-def _nan_empty():
-    """torch.empty / empty_like give NaN-filled floating tensors: a buffer an autograd function allocates and a kernel leaves
-    unwritten then shows up in its result"""
-    empty, empty_like = torch.empty, torch.empty_like
-
-    def fill(t):
-        return t.fill_(float("nan")) if t.is_floating_point() else t
-    torch.empty = lambda *a, **k: fill(empty(*a, **k))
-    torch.empty_like = lambda *a, **k: fill(empty_like(*a, **k))
-    try:
-        yield
-    finally:
-        torch.empty, torch.empty_like = empty, empty_like
 
 
 def _up_nd(t, up, axes):

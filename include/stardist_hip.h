@@ -457,6 +457,25 @@ int sd_convg_ndhwc_device(const float* d_src, int c_in, int src_stride, int D, i
 int sd_label_overlap_device(const int32_t* d_true, const int32_t* d_pred, long long n, long long cap, int64_t* d_keys, int64_t* d_counts,
                             long long* h_count, int32_t* h_minmax, void* stream);
 
+/* The same list for every consecutive pair (k, k + 1) of the K >= 2 frames of the int32 stack d_ys (K, n), in one call: the K - 1 lists
+ * sparse_overlap(ys[k], ys[k + 1]) are concatenated in d_keys / d_counts (format and capacity protocol as above, *h_count = entries of
+ * all lists); h_offsets (host, K entries): list k is [h_offsets[k], h_offsets[k + 1]), h_offsets[K - 1] = *h_count (always filled in
+ * full, whatever cap is).  h_minmax (host, 2 K ints): {min, max} of every frame; a negative minimum leaves everything else 0.  Every
+ * frame is read twice (count pass, append pass); the pair index is sorted as the bits above the ids, and where pair index and ids need
+ * more than 64 bits the pairs are worked off in groups inside the call (ids up to 2^31 - 1, any K).  Integer arithmetic only, bit-
+ * identical from call to call.  Synchronises the stream once plus once per group. */
+int sd_label_overlap_stack_device(const int32_t* d_ys, int K, long long n, long long cap, int64_t* d_keys, int64_t* d_counts,
+                                  long long* h_offsets, long long* h_count, int32_t* h_minmax, void* stream);
+
+/* Relabel a stack through one table per frame: d_out[k][i] = new id of d_ys[k][i] (both int32 (K, n)), 0 stays 0.  The table of frame k
+ * is d_ids / d_new [h_offsets[k], h_offsets[k + 1]) (h_offsets: host, K + 1 entries): raw ids ascending, strictly positive, and the id
+ * each becomes; h_max[k] (host) = the largest raw id of frame k.  An id that is not in its frame's table becomes 0.  Frames with
+ * h_max[k] < 2^22 are looked up in a dense table built here (while the tables of a call stay below 2^26 entries), the others by a
+ * binary search in the sorted ids.  One launch for the stack; every element of d_out is written.  Synchronises the stream once (the
+ * upload of the frame descriptors). */
+int sd_relabel_stack_device(const int32_t* d_ys, int K, long long n, const int32_t* d_ids, const int32_t* d_new,
+                            const long long* h_offsets, const int32_t* h_max, int32_t* d_out, void* stream);
+
 /* ---- training (2D): backward pass and losses (csrc/train2d.hip; the two pooling / up-sampling adjoints: csrc/train3d.hip) ------
  * The reference trains its Keras model with StarDist2D.train (stardist/models/model2d.py) on the losses of base.py:34-60, 315-325; these
  * entry points are the pieces of that step the forward kernels above do not cover.  Channels-last float32, batch B (2D: [B][H][W][C]).

@@ -91,6 +91,8 @@ SIGNATURES = {
     "sd_split16_pack_device": (_i, [_vp, ctypes.c_longlong, _i, _vp, _vp, _vp]),
     "sd_split16_unpack_device": (_i, [_vp, ctypes.c_longlong, _i, _vp, _vp]),
     "sd_label_overlap_device": (_i, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp]),
+    "sd_label_overlap_stack_device": (_i, [_vp, _i, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sd_relabel_stack_device": (_i, [_vp, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sd_conv_wgrad_ndhwc_device": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sd_relu_mask_device": (_i, [_vp, _vp, ctypes.c_longlong, _vp, _vp]),
     "sd_maxpool_adjoint_ndhwc_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -270,10 +270,16 @@ def _objects(y):
     return [(i, sl) for i, sl in enumerate(find_objects(y), 1) if sl is not None]
 
 
-def group_matching_labels(ys, thresh=1e-10, criterion="iou"):
-    """Give matching objects of consecutive label images (frames of a time lapse) the same id (matching.py:409-472): frame k + 1 is matched
-    against the already grouped frame k; a matched object takes its partner's id, an unmatched one the next free id.  Returns an int32
-    stack, the inputs stay untouched."""
+def group_matching_labels(ys, thresh=1e-10, criterion="iou", *, device=None):
+    """Give matching objects of consecutive label images (frames of a time lapse, slices of a stack) the same id (matching.py:409-472):
+    frame k + 1 is matched against the already grouped frame k; a matched object takes its partner's id, an unmatched one the next free id.
+    Returns an int32 stack, the inputs stay untouched.
+    Label images that are torch tensors on a HIP device -- or any input when `device` names one -- are grouped on the device
+    (stardist_amd.matching_sparse.group_matching_labels_device: one overlap kernel call for the stack, the id maps from the sparse lists,
+    one relabel kernel call); device tensors come back as a device tensor, numpy inputs as numpy.  numpy inputs without `device` stay here."""
+    if device is not None or _on_device(ys) or (not isinstance(ys, np.ndarray) and any(_on_device(y) for y in ys)):
+        from .matching_sparse import group_matching_labels_device
+        return group_matching_labels_device(ys, thresh=thresh, criterion=criterion, device=device)
     if len(ys) <= 1:
         raise ValueError("'ys' must have 2 or more entries")
     if isinstance(ys, np.ndarray):

@@ -558,6 +558,32 @@ int sd_maxpool3d_adjoint_ndhwc_device(const float* d_in, const float* d_gout, in
 int sd_upcat3d_adjoint_ndhwc_device(const float* d_gcat, int c0, int up0, int c1, int B, int D, int H, int W, float* d_g0, float* d_g1,
                                     void* stream);
 
+/* ---- training a multi-class model (the reference's StarDistData2D / 3D with n_classes and weighted_categorical_crossentropy,
+ * stardist/models/model2d.py:106-119, base.py:108-126; csrc/train_classes.hip) ---------------------------------------------------
+ * sd_class_targets_device: prob_class of a batch, d_out [B][d][h][w][n_channels] (n_channels = n_classes + 1), in one launch from the
+ * batch's label patches d_labels [B][D][H][W] (int32, negative ids clipped to 0; images: D = d = 1).
+ *   d_meta [B][4] per sample: {offset into d_keys / d_codes, entries, form, default code}.  Form 0: a dense table, the label id is the
+ *   index; form 1: `entries` label ids sorted ascending in d_keys (d_keys may be NULL when every sample is dense), searched.  An id the
+ *   table does not hold has the default code.  Codes: 0 ... n_classes = the class id, -1 = ignore the object, -2 = missing.
+ *   d_tz [d], d_ty [h], d_tx [w]: the source index of each output position along the axis (the nearest-neighbour zoom the reference
+ *   applies, tabulated by the caller), -1 = outside the array.  d_neg [B][d][h][w] (bytes, may be NULL): the negative-label mask.
+ *   Per output pixel, with l its source label: every channel 0; class c >= 1 sets channel c to 1; code -1 sets every channel to -1;
+ *   channel 0 = (l == 0); an outside pixel is all 0; a pixel of d_neg is all -1.
+ *   The launch also looks up every label > 0 of d_labels: if one has code -2, *d_missing (device int32, cleared by the caller) is
+ *   raised with an atomic or.  Nothing is synchronised.
+ * sd_class_loss_device: the weighted categorical cross entropy of the class head over n_pix pixels, from its logits [n_pix][n_channels]
+ * and the targets of sd_class_targets_device, e = 1e-7:
+ *     p = softmax(z),  S = sum_c (p_c + e),  q = clip(p / S, e, 1 - e),  L = -sum_c w_c [t_c >= 0] t_c log q_c,  loss = sum L / n_pix
+ * (every pixel counts in the mean, as in Keras).  d_class_weights: n_channels doubles on the device.  d_losses (device, 2 doubles) =
+ * {loss, w_class * loss}.  d_grad_logits [n_pix][n_channels] = d (w_class * loss) / d z of this literal expression (zero through the
+ * clip where p / S leaves [e, 1 - e]; through the division with every p_j free; through the softmax), or NULL: the loss only, the same
+ * bits.  float64 per pixel, partial sums per fixed pixel range added in order: repeatable bit for bit.  Any n_channels >= 2. */
+int sd_class_targets_device(const int32_t* d_labels, int B, int D, int H, int W, const int32_t* d_meta, const int32_t* d_keys,
+                            const int32_t* d_codes, const int32_t* d_tz, const int32_t* d_ty, const int32_t* d_tx, int d, int h, int w,
+                            const unsigned char* d_neg, int n_channels, float* d_out, int32_t* d_missing, void* stream);
+int sd_class_loss_device(const float* d_logits, const float* d_target, const double* d_class_weights, long long n_pix, int n_channels,
+                         double w_class, double* d_losses, float* d_grad_logits, void* stream);
+
 /* ---- image normalisation (csbdeep.utils.normalize / normalize_mi_ma; csrc/normalize.hip) --------------------------------------
  * d_x: a contiguous array of n_seg interleaved segments of n elements each (element i belongs to segment i % n_seg: a channels-last image
  * whose statistics are taken over every axis but the last; n_seg = 1: over the whole array).  dtype: 0 = uint8, 1 = uint16, 2 = float32.

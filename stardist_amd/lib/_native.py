@@ -106,6 +106,8 @@ SIGNATURES = {
     "sd_convg_dgrad_ndhwc_device": (_i, [_vp, _i, _vp, _i] + [_i] * 16 + [_vp, _vp]),
     "sd_maxpool3d_adjoint_ndhwc_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sd_upcat3d_adjoint_ndhwc_device": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sd_class_targets_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "sd_class_loss_device": (_i, [_vp, _vp, _vp, ctypes.c_longlong, _i, ctypes.c_double, _vp, _vp, _vp]),
     "sd_percentiles_device": (_i, [_vp, _i, ctypes.c_longlong, _i, _vp, _i, _i, _vp, _vp]),
     "sd_normalize_mi_ma_device": (_i, [_vp, _i, ctypes.c_longlong, _i, _vp, _vp, _f, _i, _vp, _vp]),
     "_LIB_non_maximum_suppression_2d": (None, [_vp, _vp, _i, _i, _f, _i, _i, _i, _vp]),

@@ -176,6 +176,25 @@ class StarDistBase(object):
     def _is_multiclass(self):
         return self.config.n_classes is not None
 
+    def _parse_classes_arg(self, classes, length):
+        """the classes tuple of `length` images from the `classes` argument of train() (base.py:262-284): 'auto' (None for a single-class
+        model, class 1 for every object when n_classes == 1), or a tuple / list / array with one entry per image"""
+        if isinstance(classes, str):
+            if classes != "auto":
+                raise ValueError("classes = '%s': only 'auto' supported as string argument for classes" % classes)
+            if self.config.n_classes is None:
+                classes = None
+            elif self.config.n_classes == 1:
+                classes = (1,) * length
+            else:
+                raise ValueError("using classes = 'auto' for n_classes > 1 not supported")
+        elif isinstance(classes, (tuple, list, np.ndarray)):
+            if len(classes) != length:
+                raise ValueError("len(classes) should be %d!" % length)
+        else:
+            raise ValueError("classes should either be 'auto' or a list of scalars/label dicts")
+        return classes
+
     @classmethod
     def from_pretrained(cls, name_or_alias=None, **kwargs):
         """csbdeep BaseModel.from_pretrained: `StarDist2D.from_pretrained('2D_versatile_fluo')`; without an argument the

@@ -129,21 +129,28 @@ class StarDist2D(StarDistBase):
         return r[0], r[1], r[2], r[3]
 
     def train(self, X, Y, validation_data, classes="auto", augmenter=None, seed=None, epochs=None, steps_per_epoch=None, workers=1):
-        """model2d.py train on the library's own kernels (stardist_amd/training.py): U-Net backbone, one input channel, single class,
-        'mae' / 'mse' distance loss, no shape completion -- any other configuration raises NotImplementedError naming the setting.
+        """model2d.py train on the library's own kernels (stardist_amd/training.py): U-Net backbone, one input channel, one or several
+        classes, 'mae' / 'mse' distance loss, no shape completion -- any other configuration raises NotImplementedError naming the setting.
         X: input images (2D, no channel axis), Y: label images (negative values switch the losses off there), validation_data: (X_val,
         Y_val).  With a model folder, weights_best.npz / weights_last.npz are written there and the best weights are loaded at the end.
-        classes: single-class models only, so anything but 'auto' / None is ignored with the reference's warning; workers: accepted for the
-        reference's signature, the host part of the data pipeline runs in the calling thread.
+        classes (a model with n_classes): 'auto' (every object is of class 1; n_classes == 1 only) or one entry per image of X: a dict
+        label id -> class id (0 ... n_classes, None = the class loss ignores the object), one integer for every object, or None;
+        validation_data may then be (X_val, Y_val, classes_val), a pair means 'auto'.  With n_classes > 1, 'auto' is out of scope
+        (NotImplementedError; the reference raises ValueError).  A label that its image's dict does not hold raises the reference's
+        ValueError, for the training data at the end of the epoch that met it.  A single-class model ignores anything but 'auto' / None
+        with the reference's warning.  workers: accepted for the reference's signature, the host part of the data pipeline runs in the
+        calling thread.
         Returns a History (training.History: a dict of per-epoch lists, also reachable as .history, with .epoch and .params) with the
         keys of the reference's Keras history: loss, prob_loss, dist_loss, prob_kld, dist_relevant_mae, dist_relevant_mse,
-        dist_dist_iou_metric, the same seven with a val_ prefix, and lr.  prob_kld averages over batches, the dist_ metrics over
-        pixels, as Keras' Mean does."""
+        dist_dist_iou_metric, the same seven with a val_ prefix, and lr; a multi-class model adds prob_class_loss and
+        val_prob_class_loss, and its loss is the sum of the three weighted by train_loss_weights.  prob_kld averages over batches, the
+        dist_ metrics over pixels, as Keras' Mean does."""
         import warnings
         from ..training import train
-        if classes not in ("auto", None):
+        if not self._is_multiclass() and classes not in ("auto", None):
             warnings.warn("Ignoring given classes as n_classes is set to None")
-        return train(self, X, Y, validation_data, augmenter=augmenter, seed=seed, epochs=epochs, steps_per_epoch=steps_per_epoch)
+        return train(self, X, Y, validation_data, classes=classes, augmenter=augmenter, seed=seed, epochs=epochs,
+                     steps_per_epoch=steps_per_epoch)
 
     def _axes_div_by(self, query_axes):
         """model2d.py:566-574"""

@@ -136,22 +136,24 @@ class StarDist3D(StarDistBase):
 
     def train(self, X, Y, validation_data, classes="auto", augmenter=None, seed=None, epochs=None, steps_per_epoch=None, workers=1):
         """model3d.py train on the library's own kernels (stardist_amd/training3d.py on the layers of stardist_amd/training.py): U-Net or ResNet backbone, one input channel,
-        single class, no batch norm / dropout, 3x3x3 kernels, filter counts in multiples of 32 (at most 512 per layer), 'mae' / 'mse'
+        one or several classes, no batch norm / dropout, 3x3x3 kernels, filter counts in multiples of 32 (at most 512 per layer), 'mae' / 'mse'
         distance loss, grid a power of two per axis, unet_pool 1 or 2 per axis, relu / linear activations, at least two convolutions
         per ResNet block -- any other configuration raises NotImplementedError naming the setting.
         X: input volumes (3D, no channel axis), Y: label volumes (negative values switch the losses off there), validation_data:
         (X_val, Y_val).  With a model folder, weights_best.npz / weights_last.npz are written there and the best weights are loaded at
-        the end.  classes: single-class models only, so anything but 'auto' / None is ignored with the reference's warning; workers:
-        accepted for the reference's signature, the host part of the data pipeline runs in the calling thread.
+        the end.  classes and a third entry of validation_data: as in StarDist2D.train (a model with n_classes; a single-class model
+        ignores anything but 'auto' / None with the reference's warning); workers: accepted for the reference's signature, the host
+        part of the data pipeline runs in the calling thread.
         Returns a History (training.History: a dict of per-epoch lists, also reachable as .history, with .epoch and .params) with the
         keys of the reference's Keras history: loss, prob_loss, dist_loss, prob_kld, dist_relevant_mae, dist_relevant_mse,
-        dist_dist_iou_metric, the same seven with a val_ prefix, and lr.  prob_kld averages over batches, the dist_ metrics over
-        pixels, as Keras' Mean does."""
+        dist_dist_iou_metric, the same seven with a val_ prefix, and lr; a multi-class model adds prob_class_loss and
+        val_prob_class_loss.  prob_kld averages over batches, the dist_ metrics over pixels, as Keras' Mean does."""
         import warnings
         from ..training3d import train3d
-        if classes not in ("auto", None):
+        if not self._is_multiclass() and classes not in ("auto", None):
             warnings.warn("Ignoring given classes as n_classes is set to None")
-        return train3d(self, X, Y, validation_data, augmenter=augmenter, seed=seed, epochs=epochs, steps_per_epoch=steps_per_epoch)
+        return train3d(self, X, Y, validation_data, classes=classes, augmenter=augmenter, seed=seed, epochs=epochs,
+                       steps_per_epoch=steps_per_epoch)
 
     def _axes_div_by(self, query_axes):
         """model3d.py:677-690"""

@@ -18,8 +18,15 @@ volumes (B, D, H, W, C): an image is the D = 1, kz = 1 case of the same native c
   loss         sd_stardist_loss2d_device: both losses and their gradients in one call; in train(), sd_stardist_loss2d_metrics_device,
                which adds the reference's Keras metrics (kld, relevant_mae, relevant_mse, dist_iou_metric) in the same passes.
   optimiser    Keras' Adam (epsilon 1e-7) and ReduceLROnPlateau on val_loss, as torch element-wise updates.
-Scope (2D): U-Net backbone, one input channel, no classes, no batch norm / dropout, 'mae' / 'mse' distance loss, no shape completion;
-check_trainable() names the first setting outside it (the settings common to every backbone first, then the U-Net's)."""
+  classes      a model with n_classes (train(..., classes=...), the reference's _parse_classes_arg): ClassTables (per image the table
+               label id -> class code) and sd_class_targets_device give prob_class on the device in one launch per batch, equal to the
+               reference's mask_to_categorical + scipy.ndimage.zoom(..., 1 / grid, order=0) + negative-label mask; the class head
+               (features_class on the common layer, the 1x1 prob_class in ClassHeadLoss) and sd_class_loss_device, the weighted
+               categorical cross entropy and its gradient on the logits.  The total is w0 prob + w1 dist + w2 prob_class; the history
+               gains prob_class_loss / val_prob_class_loss.  A single-class model runs what it ran before.
+Scope (2D): U-Net backbone, one input channel, no batch norm / dropout, 'mae' / 'mse' distance loss, no shape completion, classes given
+for a model of several classes; check_trainable() names the first setting outside it (the settings common to every backbone first, then
+the U-Net's)."""
 import ctypes
 import math
 import random
@@ -92,10 +99,18 @@ class TrainData2D(object):
     _nd = 2
 
     def __init__(self, X, Y, batch_size, n_rays, length, patch_size=(256, 256), grid=(1, 1), augmenter=None, foreground_prob=0,
-                 sample_ind_cache=True, maxfilter_patch_size=None):
+                 sample_ind_cache=True, maxfilter_patch_size=None, n_classes=None, classes=None):
         X = [np.asarray(x).astype(np.float32, copy=False) for x in X]
         if not (len(X) == len(Y) and len(X) > 0):
             raise ValueError("X and Y can't be empty and must have same length")
+        if classes is None:
+            classes = (None,) * len(X)          # every object ignored by the class loss
+        elif n_classes is None:
+            warnings.warn("Ignoring classes since n_classes is None")
+        if len(classes) != len(X):
+            raise ValueError("X and classes must have same length")
+        self.n_classes, self.classes = n_classes, classes
+        self.class_tables = ClassTables(classes, n_classes) if n_classes is not None else None
         self.data_size, self.batch_size = len(X), int(batch_size)
         self.length = 2 ** 63 - 1 if length is None else int(length)
         self.index_map = {}
@@ -171,12 +186,17 @@ class TrainData2D(object):
         X, Y = tuple(zip(*tuple(self.augmenter(_x, _y) for _x, _y in zip(X, Y))))
         return X, Y
 
+    def batch_classes(self, i):
+        """what the targets functions take as `classes` for batch i: (the class tables, the batch's image indices), or None for a
+        single-class model.  Draws no random numbers: the permutation of batch(i) is the one sample(i) made."""
+        return None if self.class_tables is None else (self.class_tables, self.batch(i))
+
     def batch_device(self, i, device):
-        """x (B, H, W, 1), prob_true (B, h, w), dist_true_mask (B, h, w, n_rays + 1): float32 device tensors"""
+        """x (B, H, W, 1), prob_true (B, h, w), dist_true_mask (B, h, w, n_rays + 1): float32 device tensors; with n_classes also
+        prob_class_true (B, h, w, n_classes + 1)"""
         X, Y = self.sample(i)
         x = torch.from_numpy(np.ascontiguousarray(np.stack(X)[..., None], np.float32)).to(device, non_blocking=False)
-        prob, dtm = targets_device(Y, self.n_rays, self.grid, device)
-        return x, prob, dtm
+        return (x,) + targets_device(Y, self.n_rays, self.grid, device, self.batch_classes(i))
 
 
 def _upload_labels(Y, grid, device):
@@ -205,9 +225,10 @@ def _finish_targets(prob, dist, neg):
     return prob, dtm
 
 
-def targets_device(Y, n_rays, grid, device):
-    """the targets of StarDistData2D.__getitem__ (model2d.py:63-104, shape_completion=False) for the label images Y (one shape) from ONE
-    upload: prob_true (B, h, w) (-1 where the label is negative) and dist_true_mask (B, h, w, n_rays + 1) on `device`"""
+def targets_device(Y, n_rays, grid, device, classes=None):
+    """the targets of StarDistData2D.__getitem__ (model2d.py:63-119, shape_completion=False) for the label images Y (one shape) from ONE
+    upload: prob_true (B, h, w) (-1 where the label is negative) and dist_true_mask (B, h, w, n_rays + 1) on `device`; with classes =
+    (ClassTables, the images' indices into them) also prob_class_true (B, h, w, n_classes + 1)"""
     from .utils import edt_prob
     gy, gx = int(grid[0]), int(grid[1])
     lab, neg, d_lab, d_u16 = _upload_labels(Y, grid, device)
@@ -224,7 +245,118 @@ def targets_device(Y, n_rays, grid, device):
         else:
             N.dcall(d_sub, "sd_edt_prob_device", _p(d_sub[b]), 1, h, w, 1.0, 1.0, 1.0, max(hi, 0), _p(prob[b]))
         N.dcall(d_u16, "sd_star_dist2d_device", _p(d_u16[b]), H, W, int(n_rays), gy, gx, _p(dist[b]))
-    return _finish_targets(prob, dist, neg)
+    if classes is None:
+        return _finish_targets(prob, dist, neg)
+    return _finish_targets(prob, dist, neg) + (class_targets_device(d_lab, neg, grid, *classes),)
+
+
+# ---- class targets ---------------------------------------------------------------------------------------------------------------
+CODE_IGNORE, CODE_MISSING = -1, -2            # the codes of sd_class_targets_device beside the class ids 0 ... n_classes
+MISSING_LABEL_MESSAGE = "all gt labels should be present in class dict provided"
+
+
+class ClassTables(object):
+    """The `classes` of a data set (per image a dict label id -> class id, one integer, or None) as the tables sd_class_targets_device
+    reads: per image (offset, entries, form, default code) and the codes (with the sorted label ids for form 1) of all images in one
+    array, uploaded once per device.  A dict is a dense table over 0 ... max id where that is small, sorted ids otherwise (the split
+    targets_device makes for edt_prob); an integer or None is the default code of a table that holds label 0 alone.  A class id outside
+    0 ... n_classes raises here (mask_to_categorical's ValueError); a label that a dict does not hold is found on the device: the kernel
+    raises the flag that check() reads."""
+
+    def __init__(self, classes, n_classes):
+        if not (np.issubdtype(type(n_classes), np.integer) and n_classes >= 1):
+            raise ValueError("n_classes is '%s' but should be a positive integer" % (n_classes,))
+        self.n_classes = int(n_classes)
+        code = self._code
+        meta, keys, codes, off = [], [], [], 0
+        for cls in classes:
+            if cls is None or np.issubdtype(type(cls), np.integer):
+                k, c, form, dflt = np.zeros(1, np.int32), np.zeros(1, np.int32), 0, code(cls)
+            elif isinstance(cls, dict):
+                items = {int(k): code(v) for k, v in cls.items() if 0 <= k < 2 ** 31}
+                items.setdefault(0, 0)            # background pixels are in no class unless the dict says so
+                hi = max(items)
+                if hi > 4 * len(items) + 1024:
+                    k = np.array(sorted(items), np.int32)
+                    c, form = np.array([items[i] for i in k.tolist()], np.int32), 1
+                else:
+                    k, c, form = np.zeros(hi + 1, np.int32), np.full(hi + 1, CODE_MISSING, np.int32), 0
+                    c[list(items)] = list(items.values())
+                dflt = CODE_MISSING
+            else:
+                raise ValueError("classes should be dict, single scalar, or None!")
+            meta.append((off, len(c), form, dflt))
+            keys.append(k)
+            codes.append(c)
+            off += len(c)
+        if off >= 2 ** 31:
+            raise ValueError("class tables too large")
+        self.meta = np.array(meta, np.int32).reshape(-1, 4)
+        self._host = (np.concatenate(keys), np.concatenate(codes))
+        self._dev = {}
+
+    def _code(self, cls):
+        if cls is None:
+            return CODE_IGNORE
+        if np.issubdtype(type(cls), np.integer) and 0 <= cls <= self.n_classes:
+            return int(cls)
+        raise ValueError("Wrong class id '%s' (for n_classes=%s)" % (cls, self.n_classes))
+
+    def device(self, device):
+        """(keys, codes, flag) on `device`: the int32 tables and the int32 flag the kernel raises for a missing label"""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.from_numpy(a).to(device) for a in self._host) + (torch.zeros(1, dtype=torch.int32, device=device),)
+        return self._dev[key]
+
+    def check(self, flag_value=None):
+        """raise the reference's ValueError if a batch since the last check held a label that its image's dict does not; flag_value:
+        the flag as already read by the caller (one device only), None: read here (a host synchronisation)"""
+        raised = bool(flag_value) if flag_value is not None else any(bool(int(d[2].item())) for d in self._dev.values())
+        if raised:
+            for d in self._dev.values():
+                d[2].zero_()
+            raise ValueError(MISSING_LABEL_MESSAGE)
+
+
+_zoom_dev = {}
+
+
+def _zoom_table_device(n, g, device):
+    key = (int(n), int(g), str(device))
+    if key not in _zoom_dev:
+        from .utils import nearest_zoom_table
+        _zoom_dev[key] = torch.from_numpy(np.array(nearest_zoom_table(n, g))).to(device)
+    return _zoom_dev[key]
+
+
+def class_targets_device(d_lab, neg, grid, tables, idx):
+    """prob_class of StarDistData2D / StarDistData3D.__getitem__ (model2d.py:106-119, model3d.py:107-127) in one launch: d_lab the
+    batch's int32 label patches on the device (B, [D,] H, W) and neg the negative-label masks on the grid (or None), both as
+    _upload_labels returns them; tables the ClassTables of the data set, idx the batch's image indices.  mask_to_categorical per pixel,
+    the reference's scipy.ndimage.zoom(..., 1 / grid, order=0) as one gather table per axis (utils.nearest_zoom_table: not [::g], and
+    rows that scipy reads from outside the patch are 0 in every channel), then -1 at negative labels.  Returns float32
+    (B, [d,] h, w, n_classes + 1).  A label missing from its dict raises the tables' flag (ClassTables.check), not an error here."""
+    device = d_lab.device
+    nd = d_lab.ndim - 1
+    B, (D, H, W) = int(d_lab.shape[0]), _dhw(d_lab.shape[1:])
+    tabs = [_zoom_table_device(n, g, device) for n, g in zip(_dhw(d_lab.shape[1:]), _dhw_grid(grid))]
+    d, h, w = (int(t.numel()) for t in tabs)
+    C = tables.n_classes + 1
+    d_neg = None
+    if neg is not None:
+        d_neg = torch.from_numpy(np.ascontiguousarray(np.stack(neg))).to(device)
+        if tuple(d_neg.shape) != (B,) + (d, h, w)[3 - nd:]:
+            raise ValueError("the patch size must be divisible by the grid")
+    meta = np.ascontiguousarray(tables.meta[np.asarray(idx, np.int64)])
+    if len(meta) != B:
+        raise ValueError("one image index per label patch expected")
+    d_keys, d_codes, flag = tables.device(device)
+    d_meta = torch.from_numpy(meta).to(device)
+    out = torch.empty((B,) + (d, h, w)[3 - nd:] + (C,), dtype=torch.float32, device=device)
+    N.dcall(d_lab, "sd_class_targets_device", _p(d_lab), B, D, H, W, _p(d_meta), _p(d_keys), _p(d_codes), *(_p(t) for t in tabs), d, h, w,
+            _p(d_neg), C, _p(out), _p(flag))
+    return out
 
 
 # ---- scope ---------------------------------------------------------------------------------------------------------------------
@@ -239,10 +371,10 @@ def _relu_or_linear(c, key, no):
         no("%s = %r (relu or linear only)" % (key, getattr(c, key)))
 
 
-def check_scope(config, nd, backbones):
+def check_scope(config, nd, backbones, classes="auto"):
     """the checks of check_trainable (nd = 2) and check_trainable3d (nd = 3): raise NotImplementedError naming the first setting outside
-    the scope of the native training -- the settings common to every backbone, then those of the U-Net.  Returns the function that
-    raises, for the checks of another backbone."""
+    the scope of the native training -- the settings common to every backbone, then those of the U-Net.  classes: the argument of
+    train(); a model of several classes needs them given.  Returns the function that raises, for the checks of another backbone."""
     c = config
 
     def no(what):
@@ -251,8 +383,8 @@ def check_scope(config, nd, backbones):
         no("n_dim = %s (%dD only)" % (c.n_dim, nd))
     if c.backbone not in backbones:
         no("backbone = %r (%s only)" % (c.backbone, "U-Net" if backbones == ("unet",) else " or ".join(backbones)))
-    if c.n_classes is not None:
-        no("n_classes = %r (single class only)" % (c.n_classes,))
+    if c.n_classes is not None and c.n_classes > 1 and isinstance(classes, str) and classes == "auto":
+        no("n_classes = %r without classes (using classes = 'auto' for n_classes > 1 not supported)" % (c.n_classes,))
     if c.n_channel_in != 1:
         no("n_channel_in = %d (one input channel only)" % c.n_channel_in)
     if c.train_dist_loss not in ("mae", "mse"):
@@ -281,9 +413,9 @@ def check_scope(config, nd, backbones):
     return no
 
 
-def check_trainable(config):
-    """raise NotImplementedError naming the first setting outside the scope of the native training"""
-    check_scope(config, 2, ("unet",))
+def check_trainable(config, classes="auto"):
+    """raise NotImplementedError naming the first setting outside the scope of the native training; classes: train()'s argument"""
+    check_scope(config, 2, ("unet",), classes)
 
 
 # ---- layers: tensors (B, H, W, C) or (B, D, H, W, C), float32; without a depth axis D = 1 and kz = 1 ----------------------------------
@@ -334,6 +466,11 @@ def _packed(w, kind):
 
 def _p(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _dhw_grid(grid):
+    """the grid of two or three axes as (gz, gy, gx), gz = 1 when there is no depth axis"""
+    return (1,) * (3 - len(grid)) + tuple(int(g) for g in grid)
 
 
 def _dhw(extents):
@@ -476,6 +613,44 @@ class HeadsLoss(torch.autograd.Function):
         return dfeat, dw, db, None, None, None
 
 
+class ClassHeadLoss(torch.autograd.Function):
+    """logits = Conv1x1(feat) of the class head and the weighted categorical cross entropy of softmax(logits) against prob_class_true
+    (sd_class_loss_device: the softmax is never written): returns w_class * loss (float64 scalar) and, not differentiable, (loss,
+    w_class * loss).  class_weights: n_classes + 1 doubles on the device; want_grad False (validation): the loss only."""
+
+    @staticmethod
+    def forward(ctx, feat, weight, bias, target, class_weights, w_class, want_grad):
+        B, H, W, C = (int(v) for v in feat.shape)
+        co = int(weight.shape[0])
+        if tuple(target.shape) != (B, H, W, co) or class_weights.numel() != co or class_weights.dtype != torch.float64:
+            raise ValueError("prob_class_true %s for logits %s and %d float64 class weights expected"
+                             % (tuple(target.shape), (B, H, W, co), co))
+        wp = _packed(weight.detach(), "convg")
+        logits = torch.empty((B, H, W, co), dtype=torch.float32, device=feat.device)
+        N.dcall(feat, "sd_convg_ndhwc_device", _p(feat), C, C, B, H, W, 1, 1, 1, 1, 1, 1, 0, 0, 0, B, H, W, _p(wp), _p(bias.detach()),
+                None, 0, co, 0, _p(logits), co)
+        losses = torch.empty(2, dtype=torch.float64, device=feat.device)
+        gz = torch.empty_like(logits) if want_grad else None
+        N.dcall(feat, "sd_class_loss_device", _p(logits), _p(target), _p(class_weights), B * H * W, co, float(w_class), _p(losses), _p(gz))
+        ctx.save_for_backward(feat, weight, gz)
+        ctx.mark_non_differentiable(losses)
+        return losses[1].clone(), losses
+
+    @staticmethod
+    def backward(ctx, gl, _):
+        feat, weight, gz = ctx.saved_tensors
+        B, H, W, C = (int(v) for v in feat.shape)
+        co = int(weight.shape[0])
+        g = (gz * gl.to(torch.float32)).contiguous()
+        dw = torch.empty(tuple(weight.shape), dtype=torch.float32, device=g.device)
+        db = torch.empty((co,), dtype=torch.float32, device=g.device)
+        N.dcall(g, "sd_conv_wgrad_ndhwc_device", _p(g), co, _p(feat), C, 0, None, 0, 0, B, H, W, 1, _p(dw), _p(db))
+        wt = _packed(weight.detach().transpose(0, 1).contiguous(), "convg")
+        dfeat = torch.empty_like(feat)
+        N.dcall(g, "sd_convg_ndhwc_device", _p(g), co, co, B, H, W, 1, 1, 1, 1, 1, 1, 0, 0, 0, B, H, W, _p(wt), None, None, 0, C, 0, _p(dfeat), C)
+        return dfeat, dw, db, None, None, None, None
+
+
 def _conv_layer(conv, kind, src0, src1=None, up0=0, res=None):
     """one stride-1 3x3 / 3x3x3 convolution of the network with its activation (kind 0 linear, 1 relu)"""
     if kind not in (0, 1):
@@ -519,9 +694,24 @@ def unet_forward(net, x):
     return x
 
 
-def heads_loss(net, config, x, prob_true, dtm, metrics_out):
+_class_weights = {}
+
+
+def class_weights_device(config, device):
+    """train_class_weights as float64 on the device (cached)"""
+    key = (tuple(float(v) for v in config.train_class_weights), str(device))
+    if key not in _class_weights:
+        _class_weights[key] = torch.tensor(key[0], dtype=torch.float64, device=device)
+    return _class_weights[key]
+
+
+def heads_loss(net, config, x, prob_true, dtm, metrics_out, prob_class_true=None):
     """the feature convolution, the two heads as one 1x1 convolution and the losses on the backbone's output x: what train_loss
-    returns.  The heads and the losses are per pixel: every axis before the last two spatial ones folds into one."""
+    returns.  The heads and the losses are per pixel: every axis before the last two spatial ones folds into one.  A multi-class net
+    takes prob_class_true: its class head (features_class, a layer like features on x, and the 1x1 prob_class) and class loss follow,
+    the total gains train_loss_weights[2] times the class loss and the losses become (prob, dist, total, prob_class)."""
+    if (net.n_classes is None) != (prob_class_true is None):
+        raise ValueError("prob_class_true is what a multi-class model takes, and only such a model")
     feat = _convact(net.features, x)
     w = torch.cat([net.prob.weight, net.dist.weight], 0)
     b = torch.cat([net.prob.bias, net.dist.bias], 0)
@@ -529,16 +719,26 @@ def heads_loss(net, config, x, prob_true, dtm, metrics_out):
     c = config
     args = (c.train_dist_loss == "mse", c.train_loss_weights[0], c.train_loss_weights[1], c.train_background_reg, torch.is_grad_enabled(),
             metrics_out)
-    return HeadsLoss.apply(feat.reshape(-1, h, wd, C), w, b, prob_true.reshape(-1, h, wd).contiguous(),
-                           dtm.reshape(-1, h, wd, dtm.shape[-1]).contiguous(), args)
+    total, losses = HeadsLoss.apply(feat.reshape(-1, h, wd, C), w, b, prob_true.reshape(-1, h, wd).contiguous(),
+                                    dtm.reshape(-1, h, wd, dtm.shape[-1]).contiguous(), args)
+    if prob_class_true is None:
+        return total, losses
+    fc = _convact(net.features_class, x)
+    K = int(prob_class_true.shape[-1])
+    cls_total, cls = ClassHeadLoss.apply(fc.reshape(-1, h, wd, int(fc.shape[-1])), net.prob_class.weight, net.prob_class.bias,
+                                         prob_class_true.reshape(-1, h, wd, K).contiguous(), class_weights_device(c, x.device),
+                                         c.train_loss_weights[2], torch.is_grad_enabled())
+    total = total + cls_total
+    return total, torch.cat([losses[:2], total.detach()[None], cls[:1]])
 
 
-def train_loss(net, config, x, prob_true, dtm, metrics_out=None):
+def train_loss(net, config, x, prob_true, dtm, metrics_out=None, prob_class_true=None):
     """total loss (float64 device scalar, differentiable w.r.t. the net's parameters) of one batch and the losses (prob, dist, total) (a
     float64 device vector): the network of StarDistNet evaluated on the library's exact-f32 kernels.  x (B, H, W, 1), prob_true (B, h, w),
     dtm (B, h, w, n_rays + 1) float32 device tensors.  metrics_out (a float64 device tensor of 4, optional) receives the batch's
-    metrics (kld, relevant_mae, relevant_mse, dist_iou_metric)"""
-    return heads_loss(net, config, unet_forward(net, x), prob_true, dtm, metrics_out)
+    metrics (kld, relevant_mae, relevant_mse, dist_iou_metric).  A multi-class model takes prob_class_true (B, h, w, n_classes + 1) as
+    well: the total includes the class loss, which is appended to the losses: (prob, dist, total, prob_class)"""
+    return heads_loss(net, config, unet_forward(net, x), prob_true, dtm, metrics_out, prob_class_true)
 
 
 # ---- optimiser -----------------------------------------------------------------------------------------------------------------
@@ -598,14 +798,17 @@ class ReduceLROnPlateau(object):
 LOSS_NAMES = ("loss", "prob_loss", "dist_loss")
 METRIC_NAMES = ("prob_kld", "dist_relevant_mae", "dist_relevant_mse", "dist_dist_iou_metric")
 HISTORY_KEYS = LOSS_NAMES + METRIC_NAMES + tuple("val_" + k for k in LOSS_NAMES + METRIC_NAMES) + ("lr",)
+# a multi-class model: Keras adds the third output's loss (the reference registers no metric for it)
+_NAMES_MULTICLASS = LOSS_NAMES + ("prob_class_loss",) + METRIC_NAMES
+HISTORY_KEYS_MULTICLASS = _NAMES_MULTICLASS + tuple("val_" + k for k in _NAMES_MULTICLASS) + ("lr",)
 
 
 class History(dict):
     """what Keras' Model.fit returns, as the dict of its per-epoch values: hist["val_loss"] and hist.history["val_loss"] are the same
-    list; .epoch the epoch indices, .params {verbose, epochs, steps}"""
+    list; .epoch the epoch indices, .params {verbose, epochs, steps}; multiclass: with prob_class_loss / val_prob_class_loss"""
 
-    def __init__(self, epochs, steps):
-        super(History, self).__init__((k, []) for k in HISTORY_KEYS)
+    def __init__(self, epochs, steps, multiclass=False):
+        super(History, self).__init__((k, []) for k in (HISTORY_KEYS_MULTICLASS if multiclass else HISTORY_KEYS))
         self.epoch = []
         self.params = {"verbose": 1, "epochs": int(epochs), "steps": int(steps)}
 
@@ -628,40 +831,53 @@ def keras_epoch_metrics(values, n_pix):
     return torch.cat([kld[None], dist])
 
 
-def train(model, X, Y, validation_data, augmenter=None, seed=None, epochs=None, steps_per_epoch=None):
-    """StarDist2D.train (see the module docstring); returns the History (a dict) of HISTORY_KEYS with one entry per epoch"""
+def train(model, X, Y, validation_data, classes="auto", augmenter=None, seed=None, epochs=None, steps_per_epoch=None):
+    """StarDist2D.train (see the module docstring); returns the History (a dict) of HISTORY_KEYS (a multi-class model:
+    HISTORY_KEYS_MULTICLASS) with one entry per epoch"""
     def data(cfg):
-        return TrainData2D, dict(n_rays=cfg.n_rays), lambda Y, dev: targets_device(Y, cfg.n_rays, cfg.grid, dev)
-    return run_training(model, X, Y, validation_data, augmenter, seed, epochs, steps_per_epoch, check_trainable, data, train_loss)
+        return TrainData2D, dict(n_rays=cfg.n_rays), lambda Y, dev, cls=None: targets_device(Y, cfg.n_rays, cfg.grid, dev, cls)
+    return run_training(model, X, Y, validation_data, augmenter, seed, epochs, steps_per_epoch, check_trainable, data, train_loss, classes)
 
 
-def run_training(model, X, Y, validation_data, augmenter, seed, epochs, steps_per_epoch, check, data, loss_fn):
-    """the body of train and train3d: check(config) for the scope, begin_training, the validation patches drawn once and cut into
-    batches with their targets, the training generator, fit.  data(config) gives (the TrainData class, its keyword arguments beyond
-    the patch settings, targets(Y, device) -> (prob_true, dist_true_mask)); loss_fn is train_loss or train_loss3d."""
+def run_training(model, X, Y, validation_data, augmenter, seed, epochs, steps_per_epoch, check, data, loss_fn, classes="auto"):
+    """the body of train and train3d: check(config, classes) for the scope, begin_training, the classes parsed as the reference does, the
+    validation patches drawn once and cut into batches with their targets, the training generator, fit.  data(config) gives (the
+    TrainData class, its keyword arguments beyond the patch settings, targets(Y, device, classes) -> (prob_true, dist_true_mask
+    [, prob_class_true])); loss_fn is train_loss or train_loss3d."""
     cfg = model.config
-    check(cfg)
-    epochs, steps_per_epoch = begin_training(model, validation_data, seed, epochs, steps_per_epoch)
+    check(cfg, classes)
+    epochs, steps_per_epoch, validation_data = begin_training(model, validation_data, seed, epochs, steps_per_epoch)
+    multiclass = cfg.n_classes is not None
+    classes = model._parse_classes_arg(classes, len(X)) if multiclass else None
     Data, data_kwargs, targets = data(cfg)
     data_kwargs = dict(data_kwargs, patch_size=cfg.train_patch_size, grid=cfg.grid, foreground_prob=cfg.train_foreground_only,
                        sample_ind_cache=cfg.train_sample_cache)
+    if multiclass:
+        data_kwargs["n_classes"] = cfg.n_classes
     n_data_val = len(validation_data[0])
+    classes_val = model._parse_classes_arg(validation_data[2], n_data_val) if multiclass else None
     n_take = cfg.train_n_val_patches if cfg.train_n_val_patches is not None else n_data_val
     dev = model.device
-    data_val = Data(validation_data[0], validation_data[1], batch_size=n_take, length=1, **data_kwargs)
+    data_val = Data(validation_data[0], validation_data[1], batch_size=n_take, length=1, classes=classes_val, **data_kwargs)
     Xv, Yv = data_val.sample(0)
+    cls_v = data_val.batch_classes(0)
     bs = int(cfg.train_batch_size)
     val_batches = []
     for i in range(0, len(Xv), bs):
         xv = torch.from_numpy(np.ascontiguousarray(np.stack(Xv[i:i + bs])[..., None], np.float32)).to(dev)
-        val_batches.append((xv,) + targets(Yv[i:i + bs], dev) + (len(Xv[i:i + bs]),))
-    model.data_train = data_train = Data(X, Y, batch_size=bs, augmenter=augmenter, length=epochs * steps_per_epoch, **data_kwargs)
+        tg = targets(Yv[i:i + bs], dev) if cls_v is None else targets(Yv[i:i + bs], dev, (cls_v[0], cls_v[1][i:i + bs]))
+        val_batches.append((xv,) + tg + (len(Xv[i:i + bs]),))
+    if cls_v is not None:
+        cls_v[0].check()                            # a validation label that its dict does not hold: raised once, before training starts
+    model.data_train = data_train = Data(X, Y, batch_size=bs, augmenter=augmenter, length=epochs * steps_per_epoch, classes=classes,
+                                         **data_kwargs)
     return fit(model, data_train, val_batches, loss_fn, epochs, steps_per_epoch)
 
 
 def begin_training(model, validation_data, seed, epochs, steps_per_epoch):
     """the checks and settings both train loops start with: a HIP device, np.random.seed(seed), epochs / steps_per_epoch from the config
-    when not given, validation_data a pair, train_patch_size divisible by what the network needs.  Returns (epochs, steps_per_epoch)."""
+    when not given, validation_data a pair (a multi-class model: a pair, which gets 'auto' as its classes, or a triple),
+    train_patch_size divisible by what the network needs.  Returns (epochs, steps_per_epoch, validation_data)."""
     cfg = model.config
     if model.device.type != "cuda":
         raise RuntimeError("training runs on a HIP device (the model lives on %s)" % model.device)
@@ -672,20 +888,30 @@ def begin_training(model, validation_data, seed, epochs, steps_per_epoch):
         epochs = cfg.train_epochs
     if steps_per_epoch is None:
         steps_per_epoch = cfg.train_steps_per_epoch
-    if not isinstance(validation_data, (list, tuple)) or len(validation_data) != 2:
-        raise ValueError("validation_data must be a tuple (X_val, Y_val)")
+    if cfg.n_classes is None:
+        if not isinstance(validation_data, (list, tuple)) or len(validation_data) != 2:
+            raise ValueError("validation_data must be a tuple (X_val, Y_val)")
+    else:
+        if not isinstance(validation_data, (list, tuple)):
+            raise ValueError("validation_data must be a tuple (X_val, Y_val) or (X_val, Y_val, classes_val)")
+        if len(validation_data) == 2:
+            validation_data = tuple(validation_data) + ("auto",)
+        if len(validation_data) != 3:
+            raise ValueError("len(validation_data) = %d, but should be 3" % len(validation_data))
     div_by = model._axes_div_by(cfg.axes.replace("C", ""))
     for p, d, a in zip(cfg.train_patch_size, div_by, cfg.axes.replace("C", "")):
         if p % d != 0:
             raise ValueError("'train_patch_size' must be divisible by {d} along axis '{a}'".format(a=a, d=d))
-    return epochs, steps_per_epoch
+    return epochs, steps_per_epoch, validation_data
 
 
 def fit(model, data_train, val_batches, loss_fn, epochs, steps_per_epoch):
     """the epoch loop of both train functions: Adam steps on loss_fn(net, config, *data_train.batch_device(step, device), metrics_out=...),
     the validation losses and metrics of val_batches [(x, prob_true, dist_true_mask, n)] after each epoch, ReduceLROnPlateau, the
     checkpoints; returns the History.  The losses are averaged as before (training: over steps; validation: weighted by images), the
-    metrics by Keras' rules (keras_epoch_metrics); one host synchronisation per epoch."""
+    metrics by Keras' rules (keras_epoch_metrics); one host synchronisation per epoch.  A multi-class model: the batches carry
+    prob_class_true after dist_true_mask, the losses are four (the class loss last), and the flag of a label missing from its class
+    dict comes to the host with the epoch's values."""
     import os
     cfg, dev = model.config, model.device
     net = model.net
@@ -695,38 +921,46 @@ def fit(model, data_train, val_batches, loss_fn, epochs, steps_per_epoch):
         p.requires_grad_(True)
     opt = Adam(params, cfg.train_learning_rate)
     rlr = ReduceLROnPlateau(**dict(cfg.train_reduce_lr)) if cfg.train_reduce_lr is not None else None
-    history = History(epochs, steps_per_epoch)
+    tables = getattr(data_train, "class_tables", None)
+    n_loss = 3 if tables is None else 4
+    names = LOSS_NAMES + METRIC_NAMES if tables is None else _NAMES_MULTICLASS
+    history = History(epochs, steps_per_epoch, multiclass=tables is not None)
     ckpt = lambda name: os.path.join(model.logdir, os.path.splitext(name)[0] + ".npz")
     best = np.inf
     net.train()
     try:
         step = 0
         for epoch in range(epochs):
-            acc = torch.zeros(3, dtype=torch.float64, device=dev)
+            acc = torch.zeros(n_loss, dtype=torch.float64, device=dev)
             met, met_pix = torch.empty((steps_per_epoch, 4), dtype=torch.float64, device=dev), []
             for i in range(steps_per_epoch):
-                x, pt, dtm = data_train.batch_device(step, dev)
+                x, pt, dtm, *pc = data_train.batch_device(step, dev)
                 step += 1
                 for p in params:
                     p.grad = None
-                loss, losses = loss_fn(net, cfg, x, pt, dtm, metrics_out=met[i])
+                loss, losses = loss_fn(net, cfg, x, pt, dtm, metrics_out=met[i], **(dict(prob_class_true=pc[0]) if pc else {}))
                 loss.backward()
                 acc += losses
                 met_pix.append(pt.numel())
                 opt.step()
             with torch.no_grad():
-                vacc, nv = torch.zeros(3, dtype=torch.float64, device=dev), 0
+                vacc, nv = torch.zeros(n_loss, dtype=torch.float64, device=dev), 0
                 vmet, vmet_pix = torch.empty((len(val_batches), 4), dtype=torch.float64, device=dev), []
-                for j, (xv, ptv, dtmv, n) in enumerate(val_batches):
-                    vacc += loss_fn(net, cfg, xv, ptv, dtmv, metrics_out=vmet[j])[1] * n
+                for j, (xv, ptv, dtmv, *pcv, n) in enumerate(val_batches):
+                    vacc += loss_fn(net, cfg, xv, ptv, dtmv, metrics_out=vmet[j], **(dict(prob_class_true=pcv[0]) if pcv else {}))[1] * n
                     nv += n
                     vmet_pix.append(ptv.numel())
-                ep = torch.cat([acc / steps_per_epoch, keras_epoch_metrics(met, met_pix), vacc / nv, keras_epoch_metrics(vmet, vmet_pix)]).tolist()
-            tr, va = ep[:7], ep[7:]
+                ep = [acc / steps_per_epoch, keras_epoch_metrics(met, met_pix), vacc / nv, keras_epoch_metrics(vmet, vmet_pix)]
+                if tables is not None:
+                    ep.append(tables.device(dev)[2].to(torch.float64))
+                ep = torch.cat(ep).tolist()
+            if tables is not None:
+                tables.check(ep.pop())
+            tr, va = ep[:n_loss + 4], ep[n_loss + 4:]
             # Keras reports the total loss as the weighted sum of the outputs' losses
-            for k, v in zip(LOSS_NAMES + METRIC_NAMES, [tr[2], tr[0], tr[1]] + tr[3:]):
+            for k, v in zip(names, [tr[2], tr[0], tr[1]] + tr[3:]):
                 history[k].append(v)
-            for k, v in zip(LOSS_NAMES + METRIC_NAMES, [va[2], va[0], va[1]] + va[3:]):
+            for k, v in zip(names, [va[2], va[0], va[1]] + va[3:]):
                 history["val_" + k].append(v)
             history["lr"].append(opt.lr)
             history.epoch.append(epoch)
@@ -775,6 +1009,20 @@ def reference_losses(prob, dist, prob_true, dist_true_mask, dist_loss="mae", los
         per_pixel = per_pixel + background_reg * ((1 - mask) * dist.abs()).mean(-1)
     d_loss = per_pixel.mean()
     return prob_loss, d_loss, loss_weights[0] * prob_loss + loss_weights[1] * d_loss
+
+
+def reference_class_loss(logits, prob_class_true, class_weights, from_logits=True):
+    """the loss of sd_class_loss_device as a differentiable torch expression (any dtype; the tests evaluate it in float64): the
+    reference's weighted_categorical_crossentropy (base.py:108-126) restated literally on the softmax of logits (..., n_classes + 1)
+    (from_logits=False: on the probabilities given), prob_class_true of the same shape (negative: ignored), one weight per channel;
+    Keras' mean over every pixel, the ignored ones included."""
+    eps = 1e-7
+    p = torch.softmax(logits, -1) if from_logits else logits
+    w = torch.as_tensor(class_weights, dtype=p.dtype, device=p.device)
+    t = prob_class_true.to(p.dtype)
+    mask = (t >= 0).to(p.dtype)
+    q = (p / (p + eps).sum(-1, keepdim=True)).clamp(eps, 1 - eps)
+    return (-(w * mask * t * torch.log(q)).sum(-1)).mean()
 
 
 def reference_metrics(prob, dist, prob_true, dist_true_mask):

@@ -1,5 +1,5 @@
 """StarDist3D training on the library's own kernels (the reference's StarDist3D.train, stardist/models/model3d.py:450-560, with the
-losses of stardist/models/base.py:34-60, 315-325 and the data generator StarDistData3D, model3d.py:30-104, without classes): what
+losses of stardist/models/base.py:34-60, 315-325 and the data generator StarDistData3D, model3d.py:30-127): what
 has no 2D counterpart.  The 3x3x3 layer, the max-pool, the U-Net walk, the heads and losses, the loop and the common scope checks are
 those of training.py on five-axis tensors.
 
@@ -22,6 +22,8 @@ those of training.py on five-axis tensors.
   loss         sd_stardist_loss2d_device with n_pix = B * d * h * w (the 3D model uses the same losses and metrics; in train3d()
                sd_stardist_loss2d_metrics_device, the metrics per voxel).
   optimiser    training.Adam / ReduceLROnPlateau, the epoch loop and checkpoints of training.fit (training.run_training).
+  classes      a model with n_classes: training.class_targets_device on the volume patches (d = the zoom along z as well) and the class
+               head / class loss of training.heads_loss, with the batch and z folded; see training.py.
 Scope: check_trainable3d() names the first setting outside it."""
 
 import numpy as np
@@ -29,32 +31,34 @@ import torch
 
 from .lib import _native as N
 from .training import (TrainData2D, _conv_layer, _convact, _finish_targets, _multiple_of_32, _p, _packed, _relu_or_linear,
-                       _upload_labels, check_scope, heads_loss, run_training, unet_forward)
+                       _upload_labels, check_scope, class_targets_device, heads_loss, run_training, unet_forward)
 
 
 # ---- data ----------------------------------------------------------------------------------------------------------------------
 class TrainData3D(TrainData2D):
-    """StarDistData3D (no classes, one channel) on top of csbdeep's RollingSequence: sample(i) is what its __getitem__(i) draws (volume
+    """StarDistData3D (one channel) on top of csbdeep's RollingSequence: sample(i) is what its __getitem__(i) draws (volume
     and label patches after the augmenter), batch_device(i) adds the targets, computed on the device"""
     _nd = 3
 
     def __init__(self, X, Y, batch_size, rays, length, patch_size=(128, 128, 128), grid=(1, 1, 1), anisotropy=None, augmenter=None,
-                 foreground_prob=0, sample_ind_cache=True, maxfilter_patch_size=None):
+                 foreground_prob=0, sample_ind_cache=True, maxfilter_patch_size=None, n_classes=None, classes=None):
         super().__init__(X, Y, batch_size, len(rays), length, patch_size=patch_size, grid=grid, augmenter=augmenter,
-                         foreground_prob=foreground_prob, sample_ind_cache=sample_ind_cache, maxfilter_patch_size=maxfilter_patch_size)
+                         foreground_prob=foreground_prob, sample_ind_cache=sample_ind_cache, maxfilter_patch_size=maxfilter_patch_size,
+                         n_classes=n_classes, classes=classes)
         self.rays, self.anisotropy = rays, anisotropy
 
     def batch_device(self, i, device):
-        """x (B, D, H, W, 1), prob_true (B, d, h, w), dist_true_mask (B, d, h, w, n_rays + 1): float32 device tensors"""
+        """x (B, D, H, W, 1), prob_true (B, d, h, w), dist_true_mask (B, d, h, w, n_rays + 1): float32 device tensors; with n_classes
+        also prob_class_true (B, d, h, w, n_classes + 1)"""
         X, Y = self.sample(i)
         x = torch.from_numpy(np.ascontiguousarray(np.stack(X)[..., None], np.float32)).to(device, non_blocking=False)
-        prob, dtm = targets_device3d(Y, self.rays, self.grid, self.anisotropy, device)
-        return x, prob, dtm
+        return (x,) + targets_device3d(Y, self.rays, self.grid, self.anisotropy, device, self.batch_classes(i))
 
 
-def targets_device3d(Y, rays, grid, anisotropy, device):
-    """the targets of StarDistData3D.__getitem__ (model3d.py:66-104, no classes) for the label volumes Y (one shape) from ONE upload:
-    prob_true (B, d, h, w) (-1 where the sub-sampled label is negative) and dist_true_mask (B, d, h, w, n_rays + 1) on `device`"""
+def targets_device3d(Y, rays, grid, anisotropy, device, classes=None):
+    """the targets of StarDistData3D.__getitem__ (model3d.py:66-127) for the label volumes Y (one shape) from ONE upload: prob_true
+    (B, d, h, w) (-1 where the sub-sampled label is negative) and dist_true_mask (B, d, h, w, n_rays + 1) on `device`; with classes =
+    (training.ClassTables, the volumes' indices into them) also prob_class_true (B, d, h, w, n_classes + 1)"""
     from .utils import edt_prob
     gz, gy, gx = (int(g) for g in grid)
     lab, neg, d_lab, d_u16 = _upload_labels(Y, grid, device)
@@ -75,14 +79,16 @@ def targets_device3d(Y, rays, grid, anisotropy, device):
             pf = full
         prob[b] = pf[::gz, ::gy, ::gx]
         N.dcall(d_u16, "sd_star_dist3d_device", _p(d_u16[b]), Z, H, W, _p(rz), _p(ry), _p(rx), R, gz, gy, gx, _p(dist[b]))
-    return _finish_targets(prob, dist, neg)
+    if classes is None:
+        return _finish_targets(prob, dist, neg)
+    return _finish_targets(prob, dist, neg) + (class_targets_device(d_lab, neg, grid, *classes),)
 
 
 # ---- scope ---------------------------------------------------------------------------------------------------------------------
-def check_trainable3d(config):
-    """raise NotImplementedError naming the first setting outside the scope of the native 3D training"""
+def check_trainable3d(config, classes="auto"):
+    """raise NotImplementedError naming the first setting outside the scope of the native 3D training; classes: train()'s argument"""
     c = config
-    no = check_scope(c, 3, ("unet", "resnet"))
+    no = check_scope(c, 3, ("unet", "resnet"), classes)
     if c.backbone == "resnet":
         if getattr(c, "resnet_batch_norm", False):
             no("resnet_batch_norm = True")
@@ -191,24 +197,27 @@ def _resnet_block(blk, x):
     return y
 
 
-def train_loss3d(net, config, x, prob_true, dtm, metrics_out=None):
+def train_loss3d(net, config, x, prob_true, dtm, metrics_out=None, prob_class_true=None):
     """total loss (float64 device scalar, differentiable w.r.t. the net's parameters) of one batch and the losses (prob, dist, total) (a
     float64 device vector): the U-Net or ResNet of StarDistNet evaluated on the library's exact-f32 kernels.  x (B, D, H, W, 1),
-    prob_true (B, d, h, w), dtm (B, d, h, w, n_rays + 1) float32 device tensors; metrics_out as in training.train_loss"""
+    prob_true (B, d, h, w), dtm (B, d, h, w, n_rays + 1) float32 device tensors; metrics_out and, for a multi-class model,
+    prob_class_true (B, d, h, w, n_classes + 1) as in training.train_loss"""
     if config.backbone == "unet":
         x = unet_forward(net, x)
     else:
         from .models.unet import ResNetBlock
         for m in net.backbone:
             x = _resnet_block(m, x) if isinstance(m, ResNetBlock) else _same_conv(m, x)
-    return heads_loss(net, config, x, prob_true, dtm, metrics_out)
+    return heads_loss(net, config, x, prob_true, dtm, metrics_out, prob_class_true)
 
 
 # ---- the loop ------------------------------------------------------------------------------------------------------------------
-def train3d(model, X, Y, validation_data, augmenter=None, seed=None, epochs=None, steps_per_epoch=None):
-    """StarDist3D.train (see the module docstring); returns the History (a dict) of training.HISTORY_KEYS with one entry per epoch"""
+def train3d(model, X, Y, validation_data, classes="auto", augmenter=None, seed=None, epochs=None, steps_per_epoch=None):
+    """StarDist3D.train (see the module docstring); returns the History (a dict) of training.HISTORY_KEYS (a multi-class model:
+    HISTORY_KEYS_MULTICLASS) with one entry per epoch"""
     def data(cfg):
         from .rays3d import rays_from_json
         rays = rays_from_json(cfg.rays_json)
-        return TrainData3D, dict(rays=rays, anisotropy=cfg.anisotropy), lambda Y, dev: targets_device3d(Y, rays, cfg.grid, cfg.anisotropy, dev)
-    return run_training(model, X, Y, validation_data, augmenter, seed, epochs, steps_per_epoch, check_trainable3d, data, train_loss3d)
+        return TrainData3D, dict(rays=rays, anisotropy=cfg.anisotropy), \
+            lambda Y, dev, cls=None: targets_device3d(Y, rays, cfg.grid, cfg.anisotropy, dev, cls)
+    return run_training(model, X, Y, validation_data, augmenter, seed, epochs, steps_per_epoch, check_trainable3d, data, train_loss3d, classes)

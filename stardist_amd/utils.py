@@ -477,6 +477,56 @@ def calculate_extents(lbl, func=np.median):
     return func(np.array([[s.stop - s.start for s in box] for _, box in boxes]), axis=0)
 
 
+def mask_to_categorical(y, n_classes, classes, return_cls_dict=False):
+    """The multi-channel class map of the integer label array y (stardist/utils.py:318-380): float32 of shape y.shape + (n_classes + 1,),
+    the first channel the background.  classes: a dict label id -> class id (0 = background class, 1 ... n_classes = that object class,
+    None = ignore the object: -1 in every channel but the background's), or one integer / None for every label.  With return_cls_dict
+    also the dict class id -> labels.  Host function: the training step builds the same map on the device (sd_class_targets_device)."""
+    from collections import defaultdict
+    from .matching import _check_label_array
+    _check_label_array(y, "y")
+    if not (np.issubdtype(type(n_classes), np.integer) and n_classes >= 1):
+        raise ValueError("n_classes is '%s' but should be a positive integer" % (n_classes,))
+    y_labels = np.unique(y[y > 0]).tolist()
+    if np.issubdtype(type(classes), np.integer) or classes is None:
+        classes = dict((k, classes) for k in y_labels)
+    elif not isinstance(classes, dict):
+        raise ValueError("classes should be dict, single scalar, or None!")
+    if not set(y_labels).issubset(set(classes.keys())):
+        raise ValueError("all gt labels should be present in class dict provided \ngt_labels found\n%s\nclass dict labels provided\n%s"
+                         % (set(y_labels), set(classes.keys())))
+    cls_dict = defaultdict(list)
+    for k, v in classes.items():
+        cls_dict[v].append(k)
+    y_mask = np.zeros(y.shape + (n_classes + 1,), np.float32)
+    for cls, labels in cls_dict.items():
+        if cls is None:
+            y_mask[np.isin(y, labels), :] = -1
+        elif np.issubdtype(type(cls), np.integer) and 0 <= cls <= n_classes:
+            y_mask[np.isin(y, labels), cls] = 1
+        else:
+            raise ValueError("Wrong class id '%s' (for n_classes=%s)" % (cls, n_classes))
+    y_mask[..., 0] = (y == 0)
+    return (y_mask, cls_dict) if return_cls_dict else y_mask
+
+
+_zoom_tables = {}
+
+
+def nearest_zoom_table(n, g):
+    """The rows scipy.ndimage.zoom(a, 1 / g, order=0) reads along an axis of length n, as an int32 array: entry i is the source row of
+    output row i, or -1 where scipy reads past the array and fills 0.  Taken from the installed scipy itself (the zoom of 1 ... n), so
+    it is what the reference's down-sampling of prob_class gives on this host -- which is not [::g].  Cached per (n, g)."""
+    key = (int(n), int(g))
+    t = _zoom_tables.get(key)
+    if t is None:
+        from scipy.ndimage import zoom
+        t = (np.rint(zoom(np.arange(1, key[0] + 1, dtype=np.float64), 1.0 / key[1], order=0)) - 1).astype(np.int32)
+        t.setflags(write=False)
+        _zoom_tables[key] = t
+    return t
+
+
 def optimize_threshold(Y, Yhat, model, nms_thresh, measure="accuracy", iou_threshs=[0.3, 0.5, 0.7], bracket=None, tol=1e-2, maxiter=20, verbose=1):
     """Tune prob_thresh for a fixed nms_thresh so that `measure` of stardist.matching (averaged over iou_threshs) between the label images Y
     and the instances of the predictions Yhat = [(prob, dist), ...] is largest: golden-section search over [max prob / 2, max prob]

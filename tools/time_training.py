@@ -9,7 +9,12 @@ timed as separate phases.
             resnet  the 3D_demo topology: 4 blocks of 3 convolutions, 32 filters, grid (1, 2, 2), anisotropy (2, 1, 1), 96 rays
             unet    the default Config3D U-Net (depth 2, 32 filters, 96 rays, grid (1, 1, 1))
             both    (default) the two of them
-Usage: python tools/time_training.py --dim {2,3} [--backbone {resnet,unet,both}] [--reps N] [--out FILE]"""
+  --classes K   instead: what the class head of a model with K classes adds to a step.  The same topology (--dim 2: 2D_demo, --dim 3:
+            the 3D_demo ResNet) as a single-class and as a K-class model, on the same seeded patches, one step of each in turn
+            (data, forward, backward, optimiser; wall clock around the synchronised step), medians -> one entry of
+            profiles/training_classes_times.json.  The single-class step launches what it launched before the class head existed
+            (tests/test_cpu_training_calls.py pins its calls), so it is the baseline.
+Usage: python tools/time_training.py --dim {2,3} [--backbone {resnet,unet,both}] [--classes K] [--reps N] [--out FILE]"""
 import argparse
 import copy
 import json
@@ -98,13 +103,94 @@ def time_config(model, data, loss_fn, reps, warm):
     return native, library
 
 
+def time_classes(make_model, make_data, loss_fn, K, reps, warm):
+    """medians (ms) of one whole step of the single-class and of the K-class model, taken in turn"""
+    from stardist_amd.training import Adam
+    sync = torch.cuda.synchronize
+    runs = []
+    for n_classes in (None, K):
+        model = make_model(n_classes)
+        params = list(model.net.parameters())
+        for p in params:
+            p.requires_grad_(True)
+        np.random.seed(0)
+        runs.append((model, params, Adam(params, 3e-4), make_data(n_classes), []))
+    for i in range(reps + warm):
+        for model, params, opt, data, times in runs:
+            sync(); t0 = time.perf_counter()
+            x, pt, dtm, *pc = data.batch_device(i, model.device)
+            for p in params:
+                p.grad = None
+            loss, _ = loss_fn(model.net, model.config, x, pt, dtm, **(dict(prob_class_true=pc[0]) if pc else {}))
+            loss.backward()
+            opt.step()
+            sync()
+            if i >= warm:
+                times.append((time.perf_counter() - t0) * 1e3)
+    for r in runs:
+        if r[3].class_tables is not None:
+            r[3].class_tables.check()
+    single, multi = (float(np.median(r[4])) for r in runs)
+    spread = [float(np.percentile(r[4], 75) - np.percentile(r[4], 25)) for r in runs]
+    return {"single_class_step_ms": single, "multi_class_step_ms": multi, "extra_ms": multi - single, "ratio": multi / single,
+            "interquartile_range_ms": {"single_class": spread[0], "multi_class": spread[1]}, "n_classes": K, "steps": reps, "warm_up": warm}
+
+
+def main_classes(a):
+    dev = torch.device("cuda:0")
+    out = a.out or os.path.join(ROOT, "profiles", "training_classes_times.json")
+    K = a.classes
+    if a.dim == 2:
+        from stardist_amd.models import Config2D, StarDist2D
+        from stardist_amd.training import TrainData2D, train_loss
+        name, B, S = "2D_demo", 4, 256
+        X, Y = zip(*[discs(512, 120, s) for s in range(8)])
+        make_model = lambda n: StarDist2D(Config2D(n_rays=32, grid=(2, 2), n_classes=n, train_patch_size=(S, S), train_batch_size=B),
+                                          basedir=None, device=dev, seed=0)
+        make_data = lambda n: TrainData2D(list(X), list(Y), batch_size=B, n_rays=32, length=10 ** 6, patch_size=(S, S), grid=(2, 2),
+                                          foreground_prob=0.9, n_classes=n,
+                                          classes=None if n is None else [{k: 1 + k % n for k in range(1, 121)} for _ in X])
+        res = time_classes(make_model, make_data, train_loss, K, a.reps or 20, 3)
+        res["what"] = "2D_demo topology (U-Net, grid (2, 2), 32 rays, depth 3, 32 filters), batch %d of %d^2 patches" % (B, S)
+    else:
+        from stardist_amd.models import Config3D, StarDist3D
+        from stardist_amd.rays3d import rays_from_json
+        from stardist_amd.training3d import TrainData3D, train_loss3d
+        name = "3D_demo_resnet"
+        X, Y = zip(*[balls((64, 160, 160), 150, s) for s in range(4)])
+        kw = dict(backbone="resnet", n_rays=96, grid=(1, 2, 2), anisotropy=(2, 1, 1), resnet_n_blocks=4, resnet_n_filter_base=32,
+                  resnet_n_conv_per_block=3, net_conv_after_resnet=128, train_patch_size=(48, 96, 96), train_batch_size=2)
+        make_model = lambda n: StarDist3D(Config3D(n_classes=n, **kw), basedir=None, device=dev, seed=0)
+        rays = rays_from_json(Config3D(**kw).rays_json)
+        make_data = lambda n: TrainData3D(list(X), list(Y), batch_size=2, rays=rays, length=10 ** 6, patch_size=(48, 96, 96), grid=(1, 2, 2),
+                                          anisotropy=(2, 1, 1), foreground_prob=0.9, n_classes=n,
+                                          classes=None if n is None else [{k: 1 + k % n for k in range(1, 151)} for _ in X])
+        res = time_classes(make_model, make_data, train_loss3d, K, a.reps or 10, 2)
+        res["what"] = "3D_demo topology (ResNet, 4 blocks of 3 convolutions, 32 filters, grid (1, 2, 2), 96 rays), batch 2 of 48 x 96 x 96 patches"
+    res["what"] += ("; one whole training step (data, forward, backward, optimiser) of the single-class and of the multi-class model in "
+                    "turn, wall clock around each synchronised step, median ms")
+    res["device"] = torch.cuda.get_device_name(0)
+    allres = {}
+    if os.path.exists(out):
+        with open(out) as fh:
+            allres = json.load(fh)
+    allres[name] = res
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(allres, fh, indent=1)
+    print(json.dumps({name: res}, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dim", type=int, choices=(2, 3), required=True)
     ap.add_argument("--backbone", choices=("resnet", "unet", "both"), default="both", help="--dim 3 only")
     ap.add_argument("--reps", type=int, default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--classes", type=int, default=None, help="time the step of a model with this many classes next to the single-class one")
     a = ap.parse_args()
+    if a.classes is not None:
+        return main_classes(a)
     dev = torch.device("cuda:0")
     what = ("; median of %d steps after %d warm-up steps, wall clock around each synchronised phase, ms.  native forward = network + heads + "
             "fused loss kernel; library forward = the network alone, its loss expression timed as 'loss'; both backward phases include "

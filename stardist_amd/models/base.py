@@ -402,7 +402,7 @@ class StarDistBase(object):
                         raise ValueError("%s%s does not fit its layer" % (base, suffix))
                     attr.copy_(torch.from_numpy(v))
         # captured forward passes hold the packed form of the OLD kernels (the packed tensors are re-made when a parameter changes,
-        # models/unet.py _packed_conv_weights); the layers' range fallbacks were decided on the old weights as well
+        # models/native_layers.py _packed_conv_weights); the layers' range fallbacks were decided on the old weights as well
         self.__dict__.pop("_graphs", None)
         for mod in self.net.modules():
             mod.__dict__.pop("_sd_force_form", None)
@@ -450,9 +450,9 @@ class StarDistBase(object):
         return _permute_axes
 
     def _net_forward(self, x, sparse_head=False):
-        """_net_forward_once under the range guard of the default split-fp16 convolutions (models/unet.py conv_mode): every such layer ORs
+        """_net_forward_once under the range guard of the default split-fp16 convolutions (models/native_layers.py conv_mode): every such layer ORs
         ITS word of this model's flag tensor with 1 when an f32 activation it reads lies outside the fp16 range (|x| > 65504 or infinite),
-        with 2 when a value of the split16 tensor it WRITES does (models/unet.py "split16": the producer makes the reader's fp16 terms).
+        with 2 when a value of the split16 tensor it WRITES does (models/native_layers.py "split16": the producer makes the reader's fp16 terms).
         The words are read back after the pass (one 1-KiB copy); when one is set the outputs are discarded, a warning names the layers
         and the magnitude limit, exactly the layers that read the offending activation are moved to the six-product bf16 form (f32 range)
         for the rest of the model's life (its producer writes f32 again), and the pass is repeated -- the other layers stay on the fp16 form."""
@@ -470,7 +470,7 @@ class StarDistBase(object):
                 ys = self._net_forward_once(x, sparse_head)
             h = flags.cpu().numpy()
             if unet.split16_replan() and not h.any():
-                # a layer met a split16 tensor it cannot read (models/unet.py _unpack_for): its producer writes f32 from now on; the pass is
+                # a layer met a split16 tensor it cannot read (models/native_layers.py _unpack_for): its producer writes f32 from now on; the pass is
                 # repeated so that the result does not depend on which form carried the activation
                 self.__dict__.pop("_graphs", None)
                 continue

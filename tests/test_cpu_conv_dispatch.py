@@ -2,7 +2,6 @@
 takes, and that every call it would make matches the C ABI's signature (argument count and ctypes conversions) with the right channel
 counts, strides, up-sampling masks and kernel depth.  The device call itself is replaced by a recorder."""
 import ctypes
-import inspect
 
 import numpy as np
 import pytest
@@ -12,7 +11,7 @@ import pytest
 def recorder(monkeypatch):
     import torch  # noqa: F401
     from stardist_amd.lib import _native as N
-    from stardist_amd.models import unet as U
+    from stardist_amd.models import native_layers as NL
     calls = []
 
     def fake_dcall(t, name, *args):
@@ -22,20 +21,10 @@ def recorder(monkeypatch):
             at.from_param(a)                      # raises if the Python value does not convert to the declared C type
         calls.append((name, [None if a is None else (a.value if isinstance(a, ctypes.c_void_p) else a) for a in args]))
     monkeypatch.setattr(N, "dcall", fake_dcall)
-    # the wrapper insists on CUDA tensors; run its logic on CPU tensors by dropping exactly that check
-    src = inspect.getsource(U._hand_conv)
-    gsrc = inspect.getsource(U._general_conv)
-    assert "t.is_cuda and " in src and "x.is_cuda and " in gsrc
-    ns = dict(U.__dict__)
-
-    class _Flag(object):
-        def data_ptr(self):
-            return 12345
-    ns["range_flag"] = lambda device: _Flag()
-    ns["_flag_ptr"] = lambda conv, device: 12345          # (the layer's word of the model's range-flag tensor)
-    exec(gsrc.replace("x.is_cuda and ", ""), ns)
-    exec(src.replace("t.is_cuda and ", ""), ns)
-    return ns["_hand_conv"], calls
+    # the wrapper insists on device tensors; run its logic on CPU tensors by answering exactly that question with yes
+    monkeypatch.setattr(NL, "_on_device", lambda t: True)
+    monkeypatch.setattr(NL, "_flag_ptr", lambda conv, device: 12345)          # (the layer's word of the model's range-flag tensor)
+    return NL._hand_conv, calls
 
 
 def _t(shape, cl):

@@ -303,7 +303,11 @@ int sd_add_bias_act_device(float* d_x, const float* d_addend, const float* d_bia
                            int n_channels, long long inner, int act, void* stream);
 
 /* Keras MaxPooling2D / 3D(pool), 'valid', stride = pool, channels-last float32 (csbdeep unet_block between its levels; the grid > 1
- * stages of stardist/models/model2d.py:317-325): d_in [D][H][W][C] -> d_out [D/pz][H/py][W/px][C]; 2D: D = pz = 1.  C % 4 == 0. */
+ * stages of stardist/models/model2d.py:317-325): d_in [D][H][W][C] -> d_out [D/pz][H/py][W/px][C]; 2D: D = pz = 1.  C % 4 == 0.
+ * Special values (one rule for both pooling forms, this one and sd_maxpool_split16_ndhwc_device): a window that holds a NaN, of either
+ * sign, gives NaN -- pooling never hides a numerical failure, and the forward maximum is the element the adjoint
+ * (sd_maxpool3d_adjoint_ndhwc_device) takes as the arg-max; otherwise the maximum in the total order -inf < .. < -0 < +0 < .. < +inf.
+ * (The ReLU of the epilogues -- sd_bias_act_device and the convolutions' -- is max(v, 0) of the hardware: a NaN and -0 give +0.) */
 int sd_maxpool_ndhwc_device(const float* d_in, int n_channels, int D, int H, int W, int pz, int py, int px, float* d_out, void* stream);
 
 /* point-level probe of the reference's inside_polyhedron (stardist/lib/stardist3d_impl.cpp:153-191) for ONE polyhedron
@@ -407,8 +411,13 @@ int sd_dot_combine_device(const float* d_partial, int groups, long long n_pix, c
  *                                     (in_split16: all sources; out_split16: no fused head then).  d_range_flag |= 1: an f32 INPUT was
  *                                     outside the fp16 range; |= 2: a value of the split16 OUTPUT was (the output is not valid).
  *   sd_conv3_c1x32_split16_device     the one-channel first layer (1 -> 32, weights packed by sd_conv3_pack_weights_host) writing split16
- *   sd_maxpool_split16_ndhwc_device   MaxPooling on a split16 tensor: == split16(maxpool(f32 tensor)) bit for bit (x -> (hi, lo') is monotone)
- *   sd_split16_pack_device / _unpack_device   f32 <-> split16 as their own passes (tests; consumers that only take f32 tensors) */
+ *   sd_maxpool_split16_ndhwc_device   MaxPooling on a split16 tensor: == split16(maxpool(f32 tensor)) bit for bit (x -> (hi, lo') is monotone);
+ *                                     the special-value rule of sd_maxpool_ndhwc_device: a pair whose value hi + lo' 2^-11 is NaN wins, so the result is NaN
+ *                                     in both terms wherever the f32 form gives NaN; the pair of +-inf, (+-inf, NaN), is ordered by its hi
+ *   sd_split16_pack_device / _unpack_device   f32 <-> split16 as their own passes (tests; consumers that only take f32 tensors);
+ *                                     d_range_flag (may be NULL) |= 2 when a value is outside the fp16 range, infinities included.  A NaN
+ *                                     is NOT a range error, here and in the flags of the convolutions alike: it is not flagged and stays
+ *                                     a NaN in both terms */
 int sd_conv3_f16x3_fmt_ndhwc_device(const float* d_src0, int c0, int up0, const float* d_src1, int c1, int up1, int D, int H, int W, int kz,
                                     const float* d_wpacked, const float* d_bias, int c_out, int act, float* d_out, int in_split16,
                                     int out_split16, int* d_range_flag, const float* d_dot_w, float* d_dot_partial, void* stream);

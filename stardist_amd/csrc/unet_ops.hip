@@ -137,6 +137,9 @@ __global__ void __launch_bounds__(256) k_head_rows(const float* __restrict__ fea
 // Keras MaxPooling2D / 3D(pool), padding 'valid', stride = pool (csbdeep unet_block between the levels; the grid > 1 stages in front
 // of the U-Net, stardist/models/model2d.py:317-325): out[zo][yo][xo][c] = max over the pz x py x px window.  One thread per (output
 // pixel, channel quad); 64-bit indexing (a 32-channel 416^3 level has more than 2^31 elements).  HBM-bound: 4 B read per input element.
+// Special values (stardist_hip.h): a NaN in the window gives NaN -- v_max_f32 alone would drop it, and an all-NaN window would give -inf;
+// otherwise v_max_f32's total order (-0 < +0).  One unordered compare and one select per element on top of the max.
+__device__ __forceinline__ float sp_max_nan(float m, float v) { return __builtin_isunordered(m, v) ? __builtin_nanf("") : fmaxf(m, v); }
 __global__ void __launch_bounds__(256) k_maxpool_cl4(const float4* __restrict__ in, float4* __restrict__ out, long long n_out4, int C4, int Ho, int Wo,
                                                      int H, int W, int pz, int py, int px) {
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -152,7 +155,7 @@ __global__ void __launch_bounds__(256) k_maxpool_cl4(const float4* __restrict__ 
         const float4* row = in + (((zo * pz + dz) * H + ((long long)yo * py + dy)) * W + (long long)xo * px) * C4 + q;
         for (int dx = 0; dx < px; ++dx) {
           const float4 v = row[(long long)dx * C4];
-          m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+          m.x = sp_max_nan(m.x, v.x); m.y = sp_max_nan(m.y, v.y); m.z = sp_max_nan(m.z, v.z); m.w = sp_max_nan(m.w, v.w);
         }
       }
     out[idx] = m;
@@ -169,6 +172,10 @@ typedef float sp_f8 __attribute__((ext_vector_type(8)));
 // monotone, so this is the pair the consumer would derive from max(x): the pooled split16 tensor equals split(maxpool(f32 tensor))
 // bit for bit.  Two pairs with the same value (hi + half a step, hi' - half a step; or -0 and +0) can only come from x < x': the larger
 // hi wins, in the total order that puts -0 below +0 (what v_max_f32 does with the f32 values).  Thread per (output pixel, chunk, octet).
+// Special values, as in k_maxpool_cl4: a pair whose hi is NaN (the split of a NaN of either sign) beats everything, so a window that holds
+// one gives NaN terms; the pair of +-inf is (+-inf, NaN) -- (inf - inf) 2^11 -- and is ordered by its hi.
+// (The x != x / x == x tests below are the NaN tests: this file must never be built with finite-math flags.  A pair with a finite hi
+// and a NaN lo', which no producer writes, counts as a NaN as well: its value is one.)
 __device__ __forceinline__ unsigned sp_order_key(_Float16 h) {
   const unsigned b = __builtin_bit_cast(unsigned short, h);
   return (b & 0x8000u) ? (~b & 0xFFFFu) : (b | 0x8000u);
@@ -194,10 +201,12 @@ __global__ void __launch_bounds__(256) k_maxpool_split16(const sp_h8* __restrict
           const sp_f8 v = __builtin_convertvector(h, sp_f8) + __builtin_convertvector(l, sp_f8) * 4.8828125e-4f;
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
-            const float vk = v[k];                          // (a scalar copy: __builtin_bit_cast on the vector ELEMENT compiled to element 0's bits for every k)
+            const float hk = (float)h[k];
+            float vk = v[k];                                // (a scalar copy: __builtin_bit_cast on the vector ELEMENT compiled to element 0's bits for every k)
+            vk = (vk != vk && hk == hk) ? hk : vk;          // +-inf
             const unsigned fb = __float_as_uint(vk);
             const unsigned fk = (fb & 0x80000000u) ? ~fb : (fb | 0x80000000u);
-            const unsigned long long key = (((unsigned long long)fk << 16) | (unsigned long long)sp_order_key(h[k])) + 1ull;      // (> 0: beats the empty slot)
+            const unsigned long long key = (vk != vk) ? ~0ull : (((unsigned long long)fk << 16) | (unsigned long long)sp_order_key(h[k])) + 1ull;      // (> 0: beats the empty slot)
             const bool take = key > bk[k];
             bk[k] = take ? key : bk[k];
             bh[k] = take ? h[k] : bh[k];

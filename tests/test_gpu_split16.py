@@ -11,25 +11,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def np_split16(x_cl):
-    """numpy statement of the form for a channels-last array (..., C), C % 32 == 0: float32 array of the same shape holding, per pixel
-    and 32-channel chunk, 32 float16 hi terms then 32 float16 lo' terms (hi = fp16(x), lo' = fp16((x - hi) * 2^11), round to nearest even)"""
-    x = np.ascontiguousarray(x_cl, np.float32)
-    C = x.shape[-1]
-    assert C % 32 == 0
-    v = x.reshape(-1, C // 32, 32)
-    with np.errstate(over="ignore", invalid="ignore"):
-        hi = v.astype(np.float16)
-        lo = ((v - hi.astype(np.float32)) * np.float32(2048.0)).astype(np.float16)
-    both = np.concatenate([hi, lo], axis=-1)                     # (n, chunks, 64) float16
-    return np.ascontiguousarray(both).view(np.float32).reshape(x.shape)
-
-
-def np_unsplit16(s_cl):
-    s = np.ascontiguousarray(s_cl, np.float32)
-    C = s.shape[-1]
-    h = s.reshape(-1, C // 32, 32).view(np.float16).reshape(-1, C // 32, 64)
-    return (h[..., :32].astype(np.float32) + h[..., 32:].astype(np.float32) * np.float32(2.0 ** -11)).reshape(s.shape)
+from _unet_ops_cases import np_split16, np_unsplit16  # noqa: E402,F401  (the statement of the form; shared with the exact tests)
 
 
 def _cl(t):

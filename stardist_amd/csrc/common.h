@@ -45,6 +45,10 @@ class Arena {
 };
 Arena& arena();
 
+// One non-blocking helper stream per device (the current one), created on first use: for work that is independent of the caller's
+// stream for a while (fork / join by events).  nullptr + error set when there is no current device or the stream cannot be created.
+hipStream_t side_stream();
+
 static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // Result-preserving switches between equivalent formulations (set through sd_set_option of the C ABI, documented there): the parity

@@ -3,6 +3,7 @@
 #include "../../include/stardist_hip.h"
 #include <stdarg.h>
 #include <stdlib.h>
+#include <mutex>
 
 namespace sd {
 
@@ -31,6 +32,16 @@ Arena& arena() {
   int d = 0;
   if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) d = 0;
   return g_arena[d];
+}
+
+hipStream_t side_stream() {
+  static std::mutex mu;
+  static hipStream_t st[kMaxDevices] = {};
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) { set_error("side_stream: no current device"); return nullptr; }
+  std::lock_guard<std::mutex> lock(mu);
+  if (!st[d] && hipStreamCreateWithFlags(&st[d], hipStreamNonBlocking) != hipSuccess) { st[d] = nullptr; set_error("side_stream: cannot create a stream"); }
+  return st[d];
 }
 
 size_t Arena::capacity() const { size_t t = 0; for (int i = 0; i < n_; ++i) t += cap_[i]; return t; }

@@ -28,6 +28,7 @@
 #include "clip_beam.h"
 #include "area_bounds.h"
 #include "poly_pass.h"
+#include "nms_rounds.h"
 #include "../../include/stardist_hip.h"
 #include <hipcub/hipcub.hpp>
 #include <math.h>
@@ -37,8 +38,6 @@
 namespace {
 
 using sdclip::i64;
-
-enum { ST_UNDECIDED = 0, ST_KEPT = 1, ST_SUPPRESSED = 2 };
 
 __device__ __forceinline__ float wave_min(float v) { for (int o = 32; o; o >>= 1) v = fminf(v, __shfl_xor(v, o)); return v; }
 __device__ __forceinline__ float wave_max(float v) { for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o)); return v; }
@@ -231,10 +230,8 @@ __device__ __forceinline__ bool bbox_intersect(const int4 a, const int4 b) {   /
   return (b.x <= a.y && a.x <= b.y && b.z <= a.w && a.z <= b.w);
 }
 
-struct Flags { int use_kdtree, use_bbox, thr_nonneg; float thr; float max_dist; };
-
 // symmetric "may interact" predicate used for the dependency lists
-__device__ __forceinline__ bool may_interact(const Flags f, const int4 bi, const int4 bj, float pyi, float pxi, float pyj, float pxj,
+__device__ __forceinline__ bool may_interact(const NmsFlags f, const int4 bi, const int4 bj, float pyi, float pxi, float pyj, float pxj,
                                              float ai, float aj) {
   if (f.thr_nonneg) {
     // disjoint integer bboxes => area 0 => overlap 0 <= thr; more generally area_inter <= area(bbox_i ∩ bbox_j), so a pair
@@ -259,10 +256,8 @@ __device__ __forceinline__ bool may_interact(const Flags f, const int4 bi, const
 // MODE 2: ONE pass into per-candidate slots whose capacity is the population of the cells scanned (k_cell_fill slotCap; nbrStart = slot
 // starts): the better-scored neighbours are written from the slot's front, the others from its back, nbrLow / nbrCount (= the number of
 // the others) tell the consumers where each half ends -- the candidate tests of the counting pass are not repeated
-#define WAIT_NONE (-2)
-#define WAIT_SCAN (-1)
 template <int MODE>
-__global__ void __launch_bounds__(256) k_neighbours(int N, GridP g, Flags f, const CellRec* __restrict__ rec, const int* __restrict__ cellStart,
+__global__ void __launch_bounds__(256) k_neighbours(int N, GridP g, NmsFlags f, const CellRec* __restrict__ rec, const int* __restrict__ cellStart,
                                                     int* __restrict__ nbrCount, int* __restrict__ nbrLow, const i64* __restrict__ nbrStart,
                                                     int* __restrict__ nbr, int* __restrict__ waitOn, int by_bbox, float reach, unsigned long long* __restrict__ total) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -329,121 +324,10 @@ __global__ void __launch_bounds__(256) k_neighbours(int N, GridP g, Flags f, con
   }
 }
 
-// exact number of list entries of the single-pass form: sum of both halves' sizes, one atomic per workgroup
-__global__ void __launch_bounds__(256) k_sum_halves(const int* __restrict__ nLow, const int* __restrict__ nHigh, int N, unsigned long long* total) {
-  __shared__ unsigned long long ws[4];
-  unsigned long long v = 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) v += (unsigned long long)(nLow[i] + nHigh[i]);
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(total, ws[0] + ws[1] + ws[2] + ws[3]);
-}
-
-// Round kernel A1: thread per undecided candidate, O(1): waitOn[i] is the higher-scored neighbour i was last seen waiting
-// for (k_neighbours seeds it with the best-scored one; WAIT_NONE = there is none, WAIT_SCAN = unknown).  Most waits persist
-// from round to round, so only the candidates whose wait target has just been decided go to the list scan (A2).
-__global__ void __launch_bounds__(1024) k_round_triage(const int* __restrict__ U, int nU, const unsigned char* __restrict__ state,
-                                                       const int* __restrict__ waitOn, int* __restrict__ Unext, int* __restrict__ K,
-                                                       int* __restrict__ S, int* counters /*0:nUnext 1:nK 2:nS*/,
-                                                       const unsigned char* __restrict__ pend) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  int kind = 0, i = -1;                       // 0 drop, 1 still waiting, 2 becomes a survivor, 3 needs the list scan
-  if (t < nU) {
-    i = U[t];
-    if (state[i] != ST_SUPPRESSED) {
-      const int wo = waitOn[i];
-      if (pend[i]) kind = 1;                  // a survivor's pair with i is deferred to the general path: i cannot be promoted yet
-      else if (wo == WAIT_NONE) kind = 2;
-      else if (wo >= 0 && state[wo] == ST_UNDECIDED) kind = 1;
-      else kind = 3;
-    }
-  }
-  // ONE atomic per list and workgroup of 1024 candidates: an atomic per wave (6 500 waves x 3 lists at 2048^2) serialises at the L2 --
-  // measured 138 us for this kernel in round 1, most of it waiting for the three counters
-  __shared__ int wcnt[3][16];
-  __shared__ int bbase[3];
-#pragma unroll
-  for (int q = 1; q <= 3; ++q) {
-    const unsigned long long m = __ballot(kind == q);
-    if (lane == 0) wcnt[q - 1][wave] = __popcll(m);
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    int sum = 0;
-    for (int w = 0; w < nw; ++w) { const int c = wcnt[threadIdx.x][w]; wcnt[threadIdx.x][w] = sum; sum += c; }
-    bbase[threadIdx.x] = sum ? atomicAdd(&counters[threadIdx.x], sum) : 0;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 1; q <= 3; ++q) {
-    const unsigned long long m = __ballot(kind == q);
-    if (kind == q) (q == 1 ? Unext : (q == 2 ? K : S))[bbase[q - 1] + wcnt[q - 1][wave] + __popcll(m & ((1ull << lane) - 1))] = i;
-  }
-}
-
-// Round kernel A2: wave per candidate of the scan list (persistent grid; the list length is read on the device).
-__global__ void __launch_bounds__(256) k_round_scan(const int* __restrict__ S, const unsigned char* __restrict__ state,
-                                                    const i64* __restrict__ nbrStart, const int* __restrict__ nbrLow, const int* __restrict__ nbr,
-                                                    int* __restrict__ waitOn, int* __restrict__ Unext, int* __restrict__ K,
-                                                    int* counters /*0:nUnext 1:nK 2:nS*/, const unsigned char* __restrict__ pend) {
-  const int lane = threadIdx.x & 63;
-  const int nS = counters[2];
-  const int nWaves = gridDim.x * (blockDim.x >> 6);
-  // a wave visits its candidates one after the other; the outcomes are collected (lane k keeps the k-th) and appended to the two
-  // lists with ONE atomic per list and 64 candidates -- an atomicAdd per candidate on a single counter serialises at the L2
-  // (10^5 candidates in the second round = 1 ms)
-  int myI = -1, myKind = 0, nbuf = 0;
-  auto flush = [&]() {
-#pragma unroll
-    for (int q = 1; q <= 2; ++q) {
-      const unsigned long long m = __ballot(lane < nbuf && myKind == q);
-      if (!m) continue;
-      int base = 0;
-      if (lane == 0) base = atomicAdd(&counters[q - 1], __popcll(m));
-      base = __shfl(base, 0);
-      if (lane < nbuf && myKind == q) (q == 1 ? Unext : K)[base + __popcll(m & ((1ull << lane) - 1))] = myI;
-    }
-    nbuf = 0;
-  };
-  // FOUR candidates per wave at a time, 16 lanes each (a list of better-scored neighbours holds ~40 entries): the kernel is a chain of
-  // dependent gathers (list bounds -> neighbour -> its state), so candidates in flight are what counts
-  const int sub = lane >> 4, sl = lane & 15;
-  for (int w0 = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 4; w0 < nS; w0 += nWaves * 4) {
-    const int w = w0 + sub;
-    const bool valid = w < nS;
-    const int i = valid ? S[w] : -1;
-    i64 t = 0, end = 0;
-    if (valid) { t = nbrStart[i]; end = t + nbrLow[i]; }        // the better-scored neighbours
-    int found = -1;
-    while (__any(found < 0 && t < end)) {
-      const i64 idx = t + sl;
-      int j = -1;
-      if (found < 0 && idx < end) { j = nbr[idx]; if (!(j < i && state[j] == ST_UNDECIDED)) j = -1; }
-      const unsigned long long m = __ballot(j >= 0);
-      const unsigned int m16 = (unsigned int)(m >> (sub << 4)) & 0xffffu;
-      const int src = (sub << 4) + (m16 ? __ffs((int)m16) - 1 : 0);
-      const int jf = __shfl(j, src);
-      if (found < 0 && m16) found = jf;
-      t += 16;
-    }
-    if (valid && sl == 0) waitOn[i] = found >= 0 ? found : WAIT_NONE;
-    const int kind = (found >= 0 || (valid && pend[i])) ? 1 : 2;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int vi = __shfl(i, q << 4), vk = __shfl(kind, q << 4);
-      if (vi >= 0) { if (lane == nbuf) { myI = vi; myKind = vk; } ++nbuf; }      // (vi is wave-uniform)
-    }
-    if (nbuf > 60) flush();
-  }
-  flush();
-}
-
 // Round kernel B: wave per new survivor: mark it, emit the pairs the reference would evaluate.
 constexpr int EMIT_STAGE = 512;
 __global__ void __launch_bounds__(256) k_round_emit(const int* __restrict__ K, const int* __restrict__ nKPtr, unsigned char* __restrict__ state,
-                                                    const i64* __restrict__ nbrStart, const int* __restrict__ nbrHigh, const int* __restrict__ nbr, Flags f,
+                                                    const i64* __restrict__ nbrStart, const int* __restrict__ nbrHigh, const int* __restrict__ nbr, NmsFlags f,
                                                     const float* __restrict__ pts, const int4* __restrict__ bbox,
                                                     const float* __restrict__ radius, const float* __restrict__ area,
                                                     int2* __restrict__ pairs, unsigned long long* pairCount,
@@ -617,7 +501,7 @@ __global__ void __launch_bounds__(256) k_pairs_decide(const int2* __restrict__ p
 // are computed speculatively (supp[edge]), and one workgroup then replays the remaining greedy rounds on the device:
 // j is suppressed iff some KEPT i < j has supp(i, j); it is kept once every such i is decided and none suppresses it.
 __global__ void __launch_bounds__(256) k_tail_emit(const int* __restrict__ U, int nU, const unsigned char* __restrict__ state,
-                                                   const i64* __restrict__ nbrStart, const int* __restrict__ nbrLow, const int* __restrict__ nbr, Flags f,
+                                                   const i64* __restrict__ nbrStart, const int* __restrict__ nbrLow, const int* __restrict__ nbr, NmsFlags f,
                                                    const float* __restrict__ pts, const int4* __restrict__ bbox,
                                                    const float* __restrict__ radius, const float* __restrict__ area,
                                                    int2* __restrict__ pairs, unsigned long long* pairCount, unsigned long long pairCap,
@@ -867,11 +751,6 @@ __global__ void __launch_bounds__(256) k_pair_bucket_scatter(const int2* __restr
 }
 
 __global__ void k_count_after(unsigned int* out, const unsigned int* total, const unsigned int* first) { *out = *total > *first ? *total - *first : 0u; }
-__global__ void k_iota(int* a, int n) { int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) a[i] = i; }
-__global__ void k_keep(const unsigned char* __restrict__ state, unsigned char* __restrict__ keep, int n) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) keep[i] = (state[i] != ST_SUPPRESSED);
-}
 
 }  // namespace
 
@@ -935,15 +814,6 @@ struct BeamPath {
   }
 };
 }  // namespace
-
-// one non-blocking helper stream per device for work that is independent of the caller's stream for a while (fork / join by events)
-static hipStream_t side_stream() {
-  static hipStream_t st[64] = {};
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) { sd::set_error("sd_nms2d: no current device"); return nullptr; }
-  if (!st[d] && hipStreamCreateWithFlags(&st[d], hipStreamNonBlocking) != hipSuccess) { sd::set_error("sd_nms2d: cannot create a stream"); return nullptr; }
-  return st[d];
-}
 
 extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n_polys, int n_rays, int use_kdtree,
                                int use_bbox, int verbose, float threshold, uint8_t* d_keep, int64_t* stats,
@@ -1009,7 +879,7 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
   else if (R <= 128) prepStride = sizeof(sdclip::PolyPrep<128>); else prepStride = sizeof(sdclip::PolyPrep<256>);
   void* prep = A.take((size_t)N * prepStride);
   if (!prep) return -1;
-  hipStream_t side = side_stream();
+  hipStream_t side = sd::side_stream();
   if (!side) return -1;
   hipEvent_t evFork = nullptr, evJoin = nullptr;
   SD_CHECK(hipEventCreateWithFlags(&evFork, hipEventDisableTiming));
@@ -1089,7 +959,7 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
   // Neighbour lists in ONE pass (option "nms2d_neighbours_single_pass", default 1): every candidate gets a slot as large as the population
   // of the cells its list is built from (known from the cell table: no candidate test needed), the lists are written into the slots --
   // better-scored neighbours from the front, the others from the back -- and the exact total is counted on the way.  The two-pass form
-  // (count, scan, fill: every candidate test done twice, 1.2 + 0.8 ms at 2048^2) remains for inputs whose slots would exceed 32-bit indices.
+  // (count, scan, fill: every candidate test done twice, 1.2 + 0.8 ms at 2048^2) remains for inputs whose slots would exceed 32-bit indices or the workspace.
   const bool singlePass = sd::option(sd::OPT_NMS2D_NBR_SINGLE) != 0;
   SD_CHECK(hipMemsetAsync(nbrCount, 0, (N + 1) * sizeof(int), s));
   hipLaunchKernelGGL(k_cell_fill, dim3(sd::div_up(N, 256)), dim3(256), 0, s, N, candCell, cellStart, cellFill, d_points, bbox, area, cellRec, g, by_bbox, reach,
@@ -1107,63 +977,36 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
   SD_CHECK(hipMemsetAsync(head0, 0xFF, (size_t)N * sizeof(int), s));
   SD_CHECK(hipMemsetAsync(dcount0, 0, sizeof(unsigned int), s));
 
-  Flags f;
+  NmsFlags f;
   f.use_kdtree = use_kdtree; f.use_bbox = use_bbox; f.thr_nonneg = (threshold >= 0.f); f.thr = threshold; f.max_dist = max_dist;
 
-  // ---- neighbour CSR
+  // ---- neighbour CSR (build_neighbour_lists, nms_rounds.h)
   const int nbBlocks = (sd::div_up(N, 4) + 7) & ~7;
-  i64 totalNbr = 0, slotTotal = 0;
-  bool slots = false;
-  unsigned long long* d_total = A.take_n<unsigned long long>(1);
-  if (!d_total) return -1;
-  if (singlePass) {
-    SD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp, tmpBytes, nbrCount, nbrStart, N + 1, s));
-    SD_CHECK(hipMemcpyAsync(&slotTotal, nbrStart + N, sizeof(i64), hipMemcpyDeviceToHost, s));
-    SD_CHECK(hipStreamSynchronize(s));
-    slots = slotTotal >= 0 && slotTotal < (i64)0x7fffffff;
-  }
-  // the slots can be several times the exact list size (every candidate of the window counts): when they do not fit the workspace the
-  // call falls back to the exact-size two-pass form instead of failing
-  int* nbr = nullptr;
-  if (slots) {
-    nbr = A.take_n<int>((size_t)slotTotal);
-    if (!nbr) slots = false;
-  }
-  if (slots && launch_side()) return -1;
-  if (!slots) {
-    SD_CHECK(hipMemsetAsync(nbrCount, 0, (N + 1) * sizeof(int), s));
-    hipLaunchKernelGGL((k_neighbours<0>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nullptr, (int*)nullptr,
-                       (int*)nullptr, by_bbox, reach, (unsigned long long*)nullptr);
-    SD_LAUNCH_CHECK();
-    SD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp, tmpBytes, nbrCount, nbrStart, N + 1, s));
-    SD_CHECK(hipMemcpyAsync(&totalNbr, nbrStart + N, sizeof(i64), hipMemcpyDeviceToHost, s));
-    SD_CHECK(hipStreamSynchronize(s));
-    if (launch_side()) return -1;
-  }
+  NbrLists L{};
+  L.count = nbrCount; L.low = nbrLow; L.start = nbrStart;
+  auto launch_neighbours = [&](int mode, const NbrLists& l) {
+    if (mode == 0)
+      hipLaunchKernelGGL((k_neighbours<0>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nullptr, (int*)nullptr,
+                         (int*)nullptr, by_bbox, reach, (unsigned long long*)nullptr);
+    else if (mode == 1)
+      hipLaunchKernelGGL((k_neighbours<1>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nbrStart, l.nbr, l.waitOn, by_bbox, reach,
+                         (unsigned long long*)nullptr);
+    else
+      hipLaunchKernelGGL((k_neighbours<2>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nbrStart, l.nbr, l.waitOn, by_bbox, reach,
+                         (unsigned long long*)nullptr);
+  };
+  const int rcLists = build_neighbour_lists(A, s, N, singlePass, scanTmp, tmpBytes, launch_neighbours, launch_side, L);
   // capacity of one call: neighbour lists and pair queues are indexed with 32 bits.  Beyond it (about 13 M candidates at the density
   // of the 2048^2 bench set) the input has to be sharded -- predict_instances_sharded / predict_instances_big do exactly that.
-  if (totalNbr < 0 || totalNbr >= (i64)0x7fffffff) {
+  if (rcLists > 0) {
     sd::set_error("sd_nms2d: %lld neighbour entries for %d candidates exceed the capacity of one call (2^31 - 1): shard the input "
-                  "(predict_instances_sharded / predict_instances_big)", (long long)totalNbr, N);
+                  "(predict_instances_sharded / predict_instances_big)", (long long)L.total, N);
     return -1;
   }
-  if (!slots) nbr = A.take_n<int>((size_t)totalNbr);
-  int* waitOn = A.take_n<int>(N);
-  if (!nbr || !waitOn) return -1;
-  if (slots) {
-    SD_CHECK(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL((k_neighbours<2>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nbrStart, nbr, waitOn, by_bbox, reach, d_total);
-    hipLaunchKernelGGL(k_sum_halves, dim3(sd::div_up(N, 256) < 1024 ? sd::div_up(N, 256) : 1024), dim3(256), 0, s, nbrLow, nbrCount, N, d_total);
-    SD_LAUNCH_CHECK();
-    unsigned long long tot = 0;
-    SD_CHECK(hipMemcpyAsync(&tot, d_total, sizeof(tot), hipMemcpyDeviceToHost, s));
-    SD_CHECK(hipStreamSynchronize(s));
-    totalNbr = (i64)tot;
-  } else {
-    hipLaunchKernelGGL((k_neighbours<1>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nbrStart, nbr, waitOn, by_bbox, reach,
-                       (unsigned long long*)nullptr);
-    SD_LAUNCH_CHECK();
-  }
+  if (rcLists) return -1;
+  const int* nbr = L.nbr;
+  int* waitOn = L.waitOn;
+  const i64 totalNbr = L.total;
 
   // (the prepared polygons are being written on the side stream meanwhile; the sweep kernels are their first readers and wait for
   // evPrep in run_pairs -- with the shortcut on, the decision kernel of round 1 runs before that and only needs the properties)

@@ -10,6 +10,7 @@
 #include "clip_sweep_full.h"
 #include "clip_beam.h"
 #include "poly_pass.h"
+#include "nms_rounds.h"
 #include <stdlib.h>
 #include "../../include/stardist_hip.h"
 
@@ -18,7 +19,6 @@ using sdclip::i64;
 
 // One thread per pair; persistent grid, the pair count is read on the device.  The result is applied directly
 // (stardist2d.cpp:579-585): no intermediate area array, no host round trip.
-enum { ST_SUPPRESSED_ = 2 };
 template <int MAXV, int MAXIL, int MAXREC, int MAXPT, int MAXJ>
 __global__ void __launch_bounds__(64) k_full_pairs(const int2* __restrict__ pairs, const unsigned int* __restrict__ idx, const unsigned int* __restrict__ nPtr, unsigned int cap, int R,
                                                    const int* __restrict__ vx, const int* __restrict__ vy,
@@ -41,7 +41,7 @@ __global__ void __launch_bounds__(64) k_full_pairs(const int2* __restrict__ pair
     if (sw.status & ~sdclip::ST_FAIL) atomicAdd(errCount, 1u);
     const float area_inter = 0.5f * (float)twice;
     const float overlap = (float)((double)area_inter / fmin((double)area[ij.x] + 1.e-10, (double)area[ij.y] + 1.e-10));
-    if (overlap > thr) { if (supp) supp[p] = 1; else state[ij.y] = ST_SUPPRESSED_; }
+    if (overlap > thr) { if (supp) supp[p] = 1; else state[ij.y] = ST_SUPPRESSED; }
   }
 }
 
@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(LDSF_T) k_full_pairs_lds(const int2* __restric
     if (sw.status & ~sdclip::ST_FAIL) atomicAdd(errCount, 1u);
     const float area_inter = 0.5f * (float)twice;
     const float overlap = (float)((double)area_inter / fmin((double)area[ij.x] + 1.e-10, (double)area[ij.y] + 1.e-10));
-    if (overlap > thr) { if (supp) supp[p] = 1; else state[ij.y] = ST_SUPPRESSED_; }
+    if (overlap > thr) { if (supp) supp[p] = 1; else state[ij.y] = ST_SUPPRESSED; }
   }
 }
 template <int MAXV, int MAXIL, int MAXREC, int MAXPT, int MAXJ>

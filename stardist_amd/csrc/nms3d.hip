@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "geom3d.h"
+#include "nms_rounds.h"
 #include "../../include/stardist_hip.h"
 #include <hipcub/hipcub.hpp>
 #include <math.h>
@@ -36,7 +37,6 @@
 namespace {
 
 typedef long long i64;
-enum { ST_UNDECIDED = 0, ST_KEPT = 1, ST_SUPPRESSED = 2 };
 
 // ------------------------------------------------------------------ P1 / P2
 // The per-candidate kernels walk a candidate's R distances in face order (gathers).  A workgroup's rows are contiguous in memory: they are
@@ -175,15 +175,12 @@ __global__ void k_cell_fill3(int N, const int* __restrict__ candCell, const int*
   cellRec[cellStart[c] + atomicAdd(&cellFill[c], 1)] = r;
 }
 
-struct Flags3 { int use_kdtree, use_bbox, thr_nonneg; float thr, max_dist; };
-#define WAIT3_NONE (-2)
-
 __device__ __forceinline__ bool bbox_pos_overlap(const int* a, const int* b) {
   return (min(a[1], b[1]) - max(a[0], b[0]) > 0) && (min(a[3], b[3]) - max(a[2], b[2]) > 0) && (min(a[5], b[5]) - max(a[4], b[4]) > 0);
 }
 
 // symmetric superset of the pairs that can interact
-__device__ __forceinline__ bool may_interact3(const Flags3 f, const float* pi, const float* pj, const int* bi, const int* bj) {
+__device__ __forceinline__ bool may_interact3(const NmsFlags f, const float* pi, const float* pj, const int* bi, const int* bj) {
   const float dz = pi[0] - pj[0], dy = pi[1] - pj[1], dx = pi[2] - pj[2];
   const float rr = 2.f * f.max_dist + 1.f;
   if (f.use_kdtree && !(dz * dz + dy * dy + dx * dx < rr * rr)) return false;
@@ -195,7 +192,7 @@ __device__ __forceinline__ bool may_interact3(const Flags3 f, const float* pi, c
 // one wave per candidate, taken in cell order; consecutive workgroups go round-robin over the 8 XCDs, so block b is given the
 // (b % 8)-th eighth of the cell-ordered list: the candidates of one region of space stay on one XCD's L2
 template <int MODE>
-__global__ void __launch_bounds__(256) k_neighbours3(int N, Grid3 g, Flags3 f, const CellRec3* __restrict__ cellRec,
+__global__ void __launch_bounds__(256) k_neighbours3(int N, Grid3 g, NmsFlags f, const CellRec3* __restrict__ cellRec,
                                                      const int* __restrict__ candCell, const int* __restrict__ cellStart,
                                                      int* __restrict__ nbrCount, int* __restrict__ nbrLow,
                                                      const i64* __restrict__ nbrStart, int* __restrict__ nbr, int* __restrict__ waitOn, int W) {
@@ -246,104 +243,8 @@ __global__ void __launch_bounds__(256) k_neighbours3(int N, Grid3 g, Flags3 f, c
   if (MODE && lane == 0) nbrCount[i] = nHi;            // from here on nbrCount holds the size of the higher-index half (k_round_emit3)
   if (MODE) {
     for (int o = 32; o; o >>= 1) minj = min(minj, __shfl_xor(minj, o));
-    if (lane == 0) waitOn[i] = (minj < i) ? minj : WAIT3_NONE;
+    if (lane == 0) waitOn[i] = (minj < i) ? minj : WAIT_NONE;
   }
-}
-// exact number of list entries of the single-pass form: one atomic per workgroup
-__global__ void __launch_bounds__(256) k_sum_halves3(const int* __restrict__ nLow, const int* __restrict__ nHigh, int N, unsigned long long* total) {
-  __shared__ unsigned long long ws[4];
-  unsigned long long v = 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) v += (unsigned long long)(nLow[i] + nHigh[i]);
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(total, ws[0] + ws[1] + ws[2] + ws[3]);
-}
-
-// Greedy round, step 1: one THREAD per undecided candidate, O(1).  waitOn[i] is the better-scored neighbour i was last seen waiting
-// for (seeded by k_neighbours3 with the best-scored one; WAIT3_NONE: it has none).  While that neighbour is undecided, i keeps
-// waiting; only the candidates whose wait target has just been decided go to the list scan (k_round_decide3 over the list S).
-__global__ void __launch_bounds__(256) k_round_triage3(const int* __restrict__ U, int nU, const unsigned char* __restrict__ state,
-                                                       const int* __restrict__ waitOn, int* __restrict__ Unext, int* __restrict__ K,
-                                                       int* __restrict__ S, int* counters /* 0: nUnext, 1: nK, 6: nS */,
-                                                       const unsigned char* __restrict__ pend) {
-  // pend[i] != 0: a pair (kept, i) of an earlier round is still to be evaluated (its exact volume was carried into the tail batch,
-  // k_defer3): i stays undecided -- and everything that waits for it -- until the tail batch
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  int kind = 0, i = -1;                       // 0 drop, 1 still waiting, 2 becomes a survivor, 3 needs the list scan
-  if (t < nU) {
-    i = U[t];
-    if (state[i] != ST_SUPPRESSED) {
-      const int wo = waitOn[i];
-      if (pend && pend[i]) kind = 1;
-      else if (wo == WAIT3_NONE) kind = 2;
-      else if (wo >= 0 && state[wo] == ST_UNDECIDED) kind = 1;
-      else kind = 3;
-    }
-  }
-#pragma unroll
-  for (int q = 1; q <= 3; ++q) {
-    const unsigned long long m = __ballot(kind == q);
-    if (!m) continue;
-    int base = 0;
-    if (lane == 0) base = atomicAdd(&counters[q == 3 ? 6 : q - 1], __popcll(m));
-    base = __shfl(base, 0);
-    if (kind == q) (q == 1 ? Unext : (q == 2 ? K : S))[base + __popcll(m & ((1ull << lane) - 1))] = i;
-  }
-}
-
-// step 2: one WAVE per candidate of the scan list S (its length is read on the device): is any better-scored neighbour still undecided?
-__global__ void __launch_bounds__(256) k_round_decide3(const int* __restrict__ U, const int* __restrict__ nUPtr, const unsigned char* __restrict__ state,
-                                                       const i64* __restrict__ nbrStart, const int* __restrict__ nbrLow, const int* __restrict__ nbr,
-                                                       int* __restrict__ waitOn, int* __restrict__ Unext, int* __restrict__ K, int* counters) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int nU = *nUPtr;
-  // outcomes are collected per wave (lane k keeps the k-th) and appended with one atomic per list and 64 candidates
-  int myI = -1, myKind = 0, nbuf = 0;
-  auto flush = [&]() {
-#pragma unroll
-    for (int q = 1; q <= 2; ++q) {
-      const unsigned long long m = __ballot(lane < nbuf && myKind == q);
-      if (!m) continue;
-      int base = 0;
-      if (lane == 0) base = atomicAdd(&counters[q - 1], __popcll(m));
-      base = __shfl(base, 0);
-      if (lane < nbuf && myKind == q) (q == 1 ? Unext : K)[base + __popcll(m & ((1ull << lane) - 1))] = myI;
-    }
-    nbuf = 0;
-  };
-  // FOUR candidates per wave at a time, 16 lanes each: the kernel is a chain of dependent gathers (list bounds -> neighbour -> its
-  // state), so candidates in flight are what counts (same form as k_round_scan of the 2D NMS)
-  const int sub = lane >> 4, sl = lane & 15;
-  const int nWaves = gridDim.x * (blockDim.x >> 6);
-  for (int w0 = (blockIdx.x * (blockDim.x >> 6) + wave) * 4; w0 < nU; w0 += nWaves * 4) {
-    const int w = w0 + sub;
-    const bool valid = w < nU;
-    const int i = valid ? U[w] : -1;
-    i64 t = 0, end = 0;
-    if (valid) { t = nbrStart[i]; end = t + nbrLow[i]; }          // the lower-index neighbours
-    int found = -1;
-    while (__any(found < 0 && t < end)) {
-      const i64 idx = t + sl;
-      int j = -1;
-      if (found < 0 && idx < end) { j = nbr[idx]; if (!(j < i && state[j] == ST_UNDECIDED)) j = -1; }
-      const unsigned long long m = __ballot(j >= 0);
-      const unsigned int m16 = (unsigned int)(m >> (sub << 4)) & 0xffffu;
-      const int jf = __shfl(j, (sub << 4) + (m16 ? __ffs((int)m16) - 1 : 0));
-      if (found < 0 && m16) found = jf;
-      t += 16;
-    }
-    if (valid && sl == 0) waitOn[i] = found >= 0 ? found : WAIT3_NONE;
-    const int kind = found >= 0 ? 1 : 2;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int vi = __shfl(i, q << 4), vk = __shfl(kind, q << 4);
-      if (vi >= 0) { if (lane == nbuf) { myI = vi; myKind = vk; } ++nbuf; }      // (vi is wave-uniform)
-    }
-    if (nbuf > 60) flush();
-  }
-  flush();
 }
 
 struct Stats { unsigned long long upper, lower, kernel, render, kept_pre, sup_pre, sup_kernel, sup_render, convex, kept_convex, overflow, hiv_faces, hiv_fallback, hiv_list, hiv_clips, hiv_rest, lb_decided, ub_decided, near_thr;
@@ -366,7 +267,7 @@ struct SuppSink {
 
 // Exact volumes carried into the tail batch ("nms3d_defer_exact"): a late round's launch of the exact-volume kernel costs the latency
 // of one exact volume (~0.5 ms) for a few dozen pairs.  From round r on, the pairs (i kept, j) the bounds of stage 3 / stage 4 leave
-// undecided are queued instead; j is marked pending (k_round_triage3 keeps it undecided) and the tail batch evaluates the queue in
+// undecided are queued instead; j is marked pending (k_round_triage keeps it undecided) and the tail batch evaluates the queue in
 // its one pass, in front of its own pairs (k_seed3).  The queue re-enters the cascade at stage 3 (a pair queued by stage 4 passes
 // stage 3's bounds again, with the same outcome).  Same fixed point: the tail replay suppresses j iff a KEPT i has a suppressing edge.
 __global__ void k_defer3(const int2* __restrict__ pairsX, const unsigned int* __restrict__ nX, int2* __restrict__ dfr, unsigned int* dfrCount,
@@ -408,7 +309,7 @@ __global__ void k_tail3_promote(const int* __restrict__ U, int nU, unsigned char
 // emit: exact neighbour predicate + cascade stages 1 and 2 (:1199-1248).  tail != 0: K is the list of the still undecided candidates,
 // none of which is marked kept; every pair of undecided candidates the sequential loop could still evaluate is emitted.
 __global__ void __launch_bounds__(256) k_round_emit3(const int* __restrict__ K, int nK, const int* __restrict__ nKPtr, SuppSink sink, int tail,
-                                                     const i64* __restrict__ nbrStart, const int* __restrict__ nbrHigh, const int* __restrict__ nbr, Flags3 f, Aniso an,
+                                                     const i64* __restrict__ nbrStart, const int* __restrict__ nbrHigh, const int* __restrict__ nbr, NmsFlags f, Aniso an,
                                                      const float* __restrict__ pts, const int* __restrict__ bbox,
                                                      const float* __restrict__ volume, const float* __restrict__ r_outer,
                                                      const float* __restrict__ r_outer_iso, const float* __restrict__ r_inner_iso,
@@ -2145,11 +2046,6 @@ __global__ void k_cone_map(const float* __restrict__ verts, const int* __restric
   const int cell = blockIdx.x * blockDim.x + threadIdx.x;
   if (cell < SD_CM_CELLS) sd3::cone_map_build_cell(cell, verts, faces, F, list, count);
 }
-__global__ void k_iota3(int* a, int n) { int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) a[i] = i; }
-__global__ void k_keep3(const unsigned char* __restrict__ state, unsigned char* __restrict__ keep, int n) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) keep[i] = (state[i] != ST_SUPPRESSED);
-}
 
 }  // namespace
 
@@ -2177,7 +2073,7 @@ int hull_planes(const float* d_dist, const float* d_points, const float* d_verts
   int* cnt = A.take_n<int>(n);
   int* list = A.take_n<int>(n);
   if (!pl || !adj || !cnt || !list) return -1;
-  hipLaunchKernelGGL(k_iota3, dim3(sd::div_up(n, 256)), dim3(256), 0, s, list, n);
+  hipLaunchKernelGGL(k_iota, dim3(sd::div_up(n, 256)), dim3(256), 0, s, list, n);
   const unsigned int bh = n < 32768 ? (unsigned int)n : 32768u;
   hipLaunchKernelGGL(k_hull, dim3(bh), dim3(64), ldsH, s, list, (unsigned int)n, d_dist, d_points, d_verts, R, cap, pl, adj, cnt);
   SD_LAUNCH_CHECK();
@@ -2311,15 +2207,6 @@ extern "C" int sd_inside_polyhedron_device(const float* d_dist, const float* d_c
   return 0;
 }
 
-// helper stream of the 3D NMS (one per device, created on first use; nullptr: everything stays on the caller's stream)
-static hipStream_t side_stream3() {
-  static hipStream_t st[64] = {};
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return nullptr;
-  if (!st[d] && hipStreamCreateWithFlags(&st[d], hipStreamNonBlocking) != hipSuccess) { st[d] = nullptr; return nullptr; }
-  return st[d];
-}
-
 extern "C" int sd_nms3d_device(const float* d_scores, const float* d_dist, const float* d_points, int n_polys, int n_rays, int n_faces,
                                const float* d_verts, const int* d_faces, float threshold, int use_bbox, int use_kdtree, int verbose,
                                uint8_t* d_keep, int64_t* stats, void* stream_) {
@@ -2414,7 +2301,7 @@ extern "C" int sd_nms3d_device(const float* d_scores, const float* d_dist, const
     unsigned short* cmList = A.take_n<unsigned short>((size_t)SD_CM_CELLS * SD_CM_CAP);
     signed char* cmCount = A.take_n<signed char>(SD_CM_CELLS);
     if (!cmList || !cmCount) return -1;
-    hipStream_t side = side_stream3();
+    hipStream_t side = sd::side_stream();          // (nullptr: everything stays on the caller's stream)
     if (side) {
       SD_CHECK(hipEventCreateWithFlags(&coneJoin.fork, hipEventDisableTiming));
       SD_CHECK(hipEventCreateWithFlags(&coneJoin.done, hipEventDisableTiming));
@@ -2488,31 +2375,15 @@ extern "C" int sd_nms3d_device(const float* d_scores, const float* d_dist, const
   SD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp, tb1, cellCount, cellStart, nCells + 1, s));
   // neighbour lists in ONE pass (option "nms3d_neighbours_single_pass", default 1; nms2d.hip has the 2D twin): slots sized from the cell
   // table, better-scored neighbours from the slot's front, the others from its back, the exact total summed afterwards; the two-pass form
-  // (count, scan, fill: every candidate test done twice) remains for inputs whose slots would exceed 32-bit indices
+  // (count, scan, fill: every candidate test done twice) remains for inputs whose slots would exceed 32-bit indices or the workspace
   const bool singlePass = sd::option(sd::OPT_NMS3D_NBR_SINGLE) != 0;
   SD_CHECK(hipMemsetAsync(nbrCount, 0, (N + 1) * sizeof(int), s));
   hipLaunchKernelGGL(k_cell_fill3, dim3(sd::div_up(N, 256)), dim3(256), 0, s, N, candCell, cellStart, cellFill, d_points, bbox, cellRec, gr, W,
                      singlePass ? nbrCount : (int*)nullptr);
   SD_LAUNCH_CHECK();
   const int nbBlocks = (sd::div_up(N, 4) + 7) & ~7;
-  Flags3 f;
+  NmsFlags f;
   f.use_kdtree = use_kdtree; f.use_bbox = use_bbox; f.thr_nonneg = (threshold >= 0.f); f.thr = threshold; f.max_dist = max_dist;
-  Flags3 fs = f;
-  i64 totalNbr = 0, slotTotal = 0;
-  if (singlePass) {
-    SD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp, tb1, nbrCount, nbrStart, N + 1, s));
-    SD_CHECK(hipMemcpyAsync(&slotTotal, nbrStart + N, sizeof(i64), hipMemcpyDeviceToHost, s));
-    SD_CHECK(hipStreamSynchronize(s));
-  }
-  const bool slots = singlePass && slotTotal >= 0 && slotTotal < (i64)0x7fffffff;
-  if (!slots) {
-    SD_CHECK(hipMemsetAsync(nbrCount, 0, (N + 1) * sizeof(int), s));
-    hipLaunchKernelGGL((k_neighbours3<0>), dim3(nbBlocks), dim3(256), 0, s, N, gr, fs, cellRec, candCell, cellStart,
-                       nbrCount, nbrLow, (const i64*)nullptr, (int*)nullptr, (int*)nullptr, W);
-    SD_LAUNCH_CHECK();
-    SD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp, tb1, nbrCount, nbrStart, N + 1, s));
-    SD_CHECK(hipMemcpyAsync(&totalNbr, nbrStart + N, sizeof(i64), hipMemcpyDeviceToHost, s));
-  }
   // ray mesh: edge adjacency (seeds of the exact volume routine) and validity (precondition of the volume bounds)
   int* faceAdj = A.take_n<int>((size_t)3 * F);
   int* d_mesh = A.take_n<int>(4);
@@ -2570,33 +2441,32 @@ extern "C" int sd_nms3d_device(const float* d_scores, const float* d_dist, const
       b3verts = v3; b3faces = f3; b3R = R3; b3F = F3;
     }
   }
+  // neighbour lists (build_neighbour_lists, nms_rounds.h)
+  NbrLists L{};
+  L.count = nbrCount; L.low = nbrLow; L.start = nbrStart;
+  auto launch_neighbours = [&](int mode, const NbrLists& l) {
+    if (mode == 0)
+      hipLaunchKernelGGL((k_neighbours3<0>), dim3(nbBlocks), dim3(256), 0, s, N, gr, f, cellRec, candCell, cellStart,
+                         nbrCount, nbrLow, (const i64*)nullptr, (int*)nullptr, (int*)nullptr, W);
+    else if (mode == 1)
+      hipLaunchKernelGGL((k_neighbours3<1>), dim3(nbBlocks), dim3(256), 0, s, N, gr, f, cellRec, candCell, cellStart,
+                         nbrCount, nbrLow, (const i64*)nbrStart, l.nbr, l.waitOn, W);
+    else
+      hipLaunchKernelGGL((k_neighbours3<2>), dim3(nbBlocks), dim3(256), 0, s, N, gr, f, cellRec, candCell, cellStart,
+                         nbrCount, nbrLow, (const i64*)nbrStart, l.nbr, l.waitOn, W);
+  };
+  const int rcLists = build_neighbour_lists(A, s, N, singlePass, scanTmp, tb1, launch_neighbours, []() { return 0; }, L);
   // capacity of one call (32-bit indices into the neighbour lists and pair queues, N * n_rays * 4 bytes of distances): beyond it the
   // input has to be sharded -- predict_instances_sharded / predict_instances_big do exactly that
-  if (totalNbr < 0 || totalNbr >= (i64)0x7fffffff || (i64)N * R >= (i64)0x3fffffff) {
+  if (rcLists > 0 || (rcLists == 0 && (i64)N * R >= (i64)0x3fffffff)) {
     sd::set_error("sd_nms3d: %d candidates (%lld neighbour entries) exceed the capacity of one call (2^30 distance values, 2^31 - 1 "
-                  "neighbour entries): shard the input (predict_instances_sharded / predict_instances_big)", N, (long long)totalNbr);
+                  "neighbour entries): shard the input (predict_instances_sharded / predict_instances_big)", N, (long long)L.total);
     return -1;
   }
-  int* nbr = A.take_n<int>((size_t)(slots ? slotTotal : totalNbr));
-  int* waitOn = A.take_n<int>(N);
-  if (!nbr || !waitOn) return -1;
-  if (slots) {
-    unsigned long long* d_total = A.take_n<unsigned long long>(1);
-    if (!d_total) return -1;
-    SD_CHECK(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL((k_neighbours3<2>), dim3(nbBlocks), dim3(256), 0, s, N, gr, fs, cellRec, candCell, cellStart,
-                       nbrCount, nbrLow, (const i64*)nbrStart, nbr, waitOn, W);
-    hipLaunchKernelGGL(k_sum_halves3, dim3(sd::div_up(N, 256) < 1024 ? sd::div_up(N, 256) : 1024), dim3(256), 0, s, nbrLow, nbrCount, N, d_total);
-    SD_LAUNCH_CHECK();
-    unsigned long long tot = 0;
-    SD_CHECK(hipMemcpyAsync(&tot, d_total, sizeof(tot), hipMemcpyDeviceToHost, s));
-    SD_CHECK(hipStreamSynchronize(s));
-    totalNbr = (i64)tot;
-  } else {
-    hipLaunchKernelGGL((k_neighbours3<1>), dim3(nbBlocks), dim3(256), 0, s, N, gr, fs, cellRec, candCell, cellStart,
-                       nbrCount, nbrLow, (const i64*)nbrStart, nbr, waitOn, W);
-    SD_LAUNCH_CHECK();
-  }
+  if (rcLists) return -1;
+  const int* nbr = L.nbr;
+  int* waitOn = L.waitOn;
+  const i64 totalNbr = L.total;
   if (stats) SD_CHECK(hipEventRecord(evb1, s));
 
   // (the cone map of stage 5 was started on the helper stream in front of the anisotropy sum; from here on the caller's stream waits for it)
@@ -2610,7 +2480,7 @@ extern "C" int sd_nms3d_device(const float* d_scores, const float* d_dist, const
   int2* pairs4 = A.take_n<int2>(pairCap);
   int2* pairs5 = A.take_n<int2>(pairCap);
   int2* pairsX = (split3 || split4) ? A.take_n<int2>(pairCap) : nullptr;          // pairs whose exact volume is needed
-  struct Counters { int nU, nK; unsigned int nP3, nP4, nP5, nHull; int nS; unsigned int nX3, nX4; };
+  struct Counters { int nU, nK, nS; unsigned int nP3, nP4, nP5, nHull, nX3, nX4; };     // (the first three: k_round_triage / k_round_scan)
   Counters* d_cnt = (Counters*)A.take(sizeof(Counters));
   Stats* d_st = (Stats*)A.take(sizeof(Stats));
   if (!U0 || !U1 || !Kl || !Sl || !pairs3 || !pairs4 || !pairs5 || !d_cnt || !d_st || ((split3 || split4) && !pairsX)) return -1;
@@ -2624,7 +2494,7 @@ extern "C" int sd_nms3d_device(const float* d_scores, const float* d_dist, const
   if (!hullState || !hullCount || !hullList) return -1;
   SD_CHECK(hipMemsetAsync(hullState, 0, (size_t)N * sizeof(int), s));
   SD_CHECK(hipMemsetAsync(d_st, 0, sizeof(Stats), s));
-  hipLaunchKernelGGL(k_iota3, dim3(sd::div_up(N, 256)), dim3(256), 0, s, U0, N);
+  hipLaunchKernelGGL(k_iota, dim3(sd::div_up(N, 256)), dim3(256), 0, s, U0, N);
   int nU = N, rounds = 0;
   int* Ucur = U0; int* Unext = U1;
   Counters h;
@@ -2668,9 +2538,9 @@ extern "C" int sd_nms3d_device(const float* d_scores, const float* d_dist, const
       if (hDef) hipLaunchKernelGGL(k_seed3, dim3(sd::div_up(hDef, 256)), dim3(256), 0, s, dfr, dfrCount, dfrCap, pairs3, &d_cnt->nP3);
       h.nK = nU; h.nU = 0;
     } else {
-      hipLaunchKernelGGL(k_round_triage3, dim3(sd::div_up(nU, 256)), dim3(256), 0, s, Ucur, nU, state, waitOn, Unext, Kl, Sl, (int*)d_cnt, (const unsigned char*)pend);
+      hipLaunchKernelGGL(k_round_triage, dim3(sd::div_up(nU, 256)), dim3(256), 0, s, Ucur, nU, state, waitOn, Unext, Kl, Sl, (int*)d_cnt, (const unsigned char*)pend);
       const int wgrid = sd::div_up(nU, 4) < 2048 ? sd::div_up(nU, 4) : 2048;
-      hipLaunchKernelGGL(k_round_decide3, dim3(wgrid), dim3(256), 0, s, Sl, &d_cnt->nS, state, nbrStart, nbrLow, nbr, waitOn, Unext, Kl, (int*)d_cnt);
+      hipLaunchKernelGGL(k_round_scan, dim3(wgrid), dim3(256), 0, s, Sl, state, nbrStart, nbrLow, nbr, waitOn, Unext, Kl, (int*)d_cnt, (const unsigned char*)pend);
       SD_LAUNCH_CHECK();
     }
     const SuppSink sink = tail ? SuppSink{state, supEdges, supCount, pairCap} : SuppSink{state, nullptr, nullptr, 0u};
@@ -2797,7 +2667,7 @@ extern "C" int sd_nms3d_device(const float* d_scores, const float* d_dist, const
     nU = nUndecided;
     int* t = Ucur; Ucur = Unext; Unext = t;
   }
-  hipLaunchKernelGGL(k_keep3, dim3(sd::div_up(N, 256)), dim3(256), 0, s, state, d_keep, N);
+  hipLaunchKernelGGL(k_keep, dim3(sd::div_up(N, 256)), dim3(256), 0, s, state, d_keep, N);
   SD_LAUNCH_CHECK();
   Stats hs_;
   SD_CHECK(hipMemcpyAsync(&hs_, d_st, sizeof(Stats), hipMemcpyDeviceToHost, s));

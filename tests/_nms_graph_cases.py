@@ -231,8 +231,10 @@ def _register(dim, f, *a, **kw):
     return key
 
 
-CHAIN_N_2D = (1, 2, 5, 6, 7, 12, 13, 64, 600, 3000)
-CHAIN_N_3D = (3, 40, 400, 520, 3200)
+# (1023..1025 in 2D, 255..257 in 3D: the round triage closes its lists per workgroup -- of 1024 resp. 256 candidates: a partial last wave,
+# a full last wave, a second workgroup of one candidate)
+CHAIN_N_2D = (1, 2, 5, 6, 7, 12, 13, 64, 600, 1023, 1024, 1025, 3000)
+CHAIN_N_3D = (3, 40, 255, 256, 257, 400, 520, 3200)
 
 CHAINS_2D = [_register(2, chain, n) for n in CHAIN_N_2D] + \
             [_register(2, chain, n, layout="serpentine") for n in (64, 600)] + \

@@ -83,6 +83,7 @@ def test_generator_invariants(key):
 def test_round_count_of_a_monotone_chain():
     """the regime bounds the GPU test places on stats[2], from the host loop of sd_nms2d"""
     assert [C.rounds_2d_monotone(n) for n in (1, 2, 5, 6, 7, 12, 13, 64, 600, 3000)] == [1, 2, 3, 4, 4, 7, 7, 29, 252, 1252]
+    assert [C.rounds_2d_monotone(n) for n in (1023, 1024, 1025)] == [428, 429, 429]
     for n in list(C.CHAIN_N_2D) + list(range(1, 200)):
         t = min(n // 6, 65536)
         assert C.rounds_2d_monotone(n) >= (n - t) // 2

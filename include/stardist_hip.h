@@ -80,9 +80,10 @@ int sd_get_option(const char* name);
  * descending.  use_kdtree / use_bbox / verbose / threshold as in the reference ("O!O!iiif").
  * keep   (n_polys,) bytes: 1 = survivor, 0 = suppressed (the reference returns NPY_BOOL).
  * stats  optional int64[16] (may be NULL): {0 pairs evaluated, 1 pairs re-run on the exact-join path,
- *        2 greedy rounds, 3 neighbour entries, 4 pair-kernel time ns (HIP events on `stream`),
+ *        2 greedy rounds, 3 ordered neighbour relations (2 x the entries the lists store), 4 pair-kernel time ns (HIP events on `stream`),
  *        5 pair-kernel launches, 6 exact-join kernel ns, 7 build+bin+neighbour kernels ns, 8 capacity spills,
- *        9 pairs decided by the area enclosure (counted in 0 as well), 10 undecided pairs deferred to the tail batch, 11.. 0}.
+ *        9 pairs decided by the area enclosure (counted in 0 as well), 10 undecided pairs deferred to the tail batch,
+ *        11 undecided pairs not swept because another pair had suppressed their j meanwhile (counted in 0 as well), 12.. 0}.
  */
 int sd_nms2d_host(const float* dist, const float* points, int n_polys, int n_rays,
                   int use_kdtree, int use_bbox, int verbose, float threshold,
@@ -90,6 +91,12 @@ int sd_nms2d_host(const float* dist, const float* points, int n_polys, int n_ray
 int sd_nms2d_device(const float* d_dist, const float* d_points, int n_polys, int n_rays,
                     int use_kdtree, int use_bbox, int verbose, float threshold,
                     uint8_t* d_keep, int64_t* stats, void* stream);
+
+/* Test probe of the 2D NMS's build step, exactly as sd_nms2d_device runs it (same kernel, same table of ray directions): integer
+ * vertices d_vx / d_vy (n_polys, n_rays), d_bbox (n_polys, 4) [xmin, xmax, ymin, ymax], d_radius, d_area (n_polys) and d_gstats (5):
+ * bits of the largest distance, min / max of floor(y) and of floor(x) over the centres. */
+int sd_nms2d_build_device(const float* d_dist, const float* d_points, int n_polys, int n_rays, int32_t* d_vx, int32_t* d_vy,
+                          int32_t* d_bbox, float* d_radius, float* d_area, int32_t* d_gstats, void* stream);
 
 /* replaces stardist.lib.stardist2d.c_non_max_suppression_inds_old
  *   (stardist/lib/stardist2d.cpp:173-386, "O!O!fiiii"; caller stardist/nms.py:20-74 _non_maximum_suppression_old; the reference keeps

@@ -4,17 +4,18 @@
 // (stardist/lib/stardist2d.cpp:390-615).  Same inputs (candidates sorted by score
 // descending), same survivor set, different schedule:
 //
-//   K1 build      one wave per candidate: integer vertices (float math + truncation exactly as
+//   K1 build      one thread per candidate (more than 32 rays: one wave): integer vertices (float math + truncation exactly as
 //                 stardist2d.cpp:447-471, sin/cos table computed by the HOST libm so the device
 //                 never evaluates sinf/cosf), int bbox, outer radius, float area (:128-138).
 //   K2 bin        counting sort of candidates into a uniform grid (replaces the nanoflann
 //                 kd-tree, stardist2d.cpp:486-513; result-neutral).
-//   K3 neighbours CSR lists of candidates whose bounding boxes can touch (symmetric superset
-//                 of every pair the reference would test).
+//   K3 neighbours CSR lists of the BETTER-scored candidates whose bounding boxes can touch a candidate's (the predicate is a
+//                 symmetric superset of every pair the reference would test; the worse-scored ones are found again by
+//                 the few candidates that become survivors, from the cell grid).
 //   greedy rounds A: a candidate becomes a survivor once every higher-scored neighbour is
 //                    decided and none suppressed it;   (wave ballot over the neighbour list)
-//                 B: each new survivor emits the (i, j) pairs the reference would evaluate
-//                    for it (stardist2d.cpp:566-577 predicate, exact) via ballot/prefix-sum
+//                 B: each new survivor walks its cell window and emits the (i, j) pairs the reference
+//                    would evaluate for it (stardist2d.cpp:566-577 predicate, exact) via ballot/prefix-sum
 //                    compaction into a pair queue;
 //                 C: one thread per pair runs the integer scan-beam intersection
 //                    (clip_sweep.h) and applies  overlap > threshold  (:579-585).
@@ -105,68 +106,99 @@ __global__ void __launch_bounds__(256) k_build(const float* __restrict__ dist, c
   }
 }
 
-// k_build for n_rays <= 32: HALF a wave per candidate (a 32-ray polygon leaves half of a wave idle in k_build: 0.47 -> 0.25 ms for the
-// 418 577 candidates of the 2048^2 bench set, on the critical path of the grid set-up).  Same arithmetic, same order of the float area sum.
-__global__ void __launch_bounds__(256) k_build32(const float* __restrict__ dist, const float* __restrict__ pts,
-                                                 const float2* __restrict__ sincos, int N, int R,
-                                                 int* __restrict__ vx, int* __restrict__ vy, int4* __restrict__ bbox,
-                                                 float* __restrict__ radius, float* __restrict__ area, int* gstats) {
-  __shared__ int sxy[8][2][32];
-  const int l = threadIdx.x & 31, hw = threadIdx.x >> 5;
-  const int i = blockIdx.x * 8 + hw;
-  const bool cv = i < N, lv = cv && l < R;
-  int* sx = sxy[hw][0];
-  int* sy = sxy[hw][1];
-  float py = 0.f, px = 0.f;
-  if (cv) { py = pts[2 * i]; px = pts[2 * i + 1]; }
-  float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY, rmax = 0.f;
-  if (lv) {
-    const float d = dist[(size_t)i * R + l];
-    const float2 sc = sincos[l];
-    const float y = py + d * sc.x;   // stardist2d.cpp:454 (compiled with -ffp-contract=off)
-    const float x = px + d * sc.y;   // stardist2d.cpp:455
-    xmin = xmax = x; ymin = ymax = y;
-    const int X = (int)(long long)x, Y = (int)(long long)y;   // IntPoint(cInt(x), cInt(y)) :471
-    sx[l] = X; sy[l] = Y;
-    vx[(size_t)i * R + l] = X; vy[(size_t)i * R + l] = Y;
-    rmax = fmaxf(0.f, d);
+// k_build for n_rays <= 32: ONE THREAD per candidate, one wave (= one workgroup) per 64 candidates.  Before: half a wave per candidate,
+// seven 5-step shuffle reductions (two of them 64-bit) and five guarded atomics per candidate, 0.28 ms for the 418 577 candidates of the
+// 2048^2 bench set against 50 us of memory traffic.  Here a thread keeps its candidate's running extremes and the integer cross-product
+// sums in registers, the wave reduces the five gstats words once and issues one guarded atomic per word.  The wave's 64 rows of dist, vx
+// and vy are contiguous in memory: they are moved with lane-consecutive (16-byte where aligned) accesses and staged in LDS, where a thread
+// walks its own row -- starting at ray (its index mod R), so that the lanes of a step hit different banks (R = 32: rows are 32 words apart).
+// Same arithmetic: every vertex is the same float expression, min / max and the int64 sums do not depend on the order, and the float area
+// of a polygon with sum |term| >= 2^24 is replayed in path order.
+// LDS (dynamic): 64 * R words of distances, overwritten in place by x; 64 * R words of y.
+__global__ void __launch_bounds__(64) k_build32(const float* __restrict__ dist, const float* __restrict__ pts,
+                                                const float2* __restrict__ sincos, int N, int R, int vec4,
+                                                int* __restrict__ vx, int* __restrict__ vy, int4* __restrict__ bbox,
+                                                float* __restrict__ radius, float* __restrict__ area, int* gstats) {
+  extern __shared__ __attribute__((aligned(16))) int rows[];
+  __shared__ float2 ssc[32];
+  const int c = threadIdx.x;
+  const int base = blockIdx.x * 64;
+  const int cnt = min(64, N - base);                  // (>= 1: the grid is div_up(N, 64))
+  const int nel = cnt * R;                            // elements of this wave's rows, <= 64 * R
+  int* sx = rows;
+  int* sy = rows + 64 * R;
+  if (c < R) ssc[c] = sincos[c];
+  {
+    const int* g = (const int*)dist + (size_t)base * R;   // (moved as bits: the LDS rows are ints throughout)
+    const int nv = vec4 ? nel >> 2 : 0;               // (base * R * 4 bytes is a multiple of 256: the rows are aligned if the array is)
+    for (int e = c; e < nv; e += 64) ((int4*)rows)[e] = ((const int4*)g)[e];
+    for (int e = 4 * nv + c; e < nel; e += 64) rows[e] = g[e];
   }
-  for (int o = 16; o; o >>= 1) {
-    xmin = fminf(xmin, __shfl_xor(xmin, o)); xmax = fmaxf(xmax, __shfl_xor(xmax, o));
-    ymin = fminf(ymin, __shfl_xor(ymin, o)); ymax = fmaxf(ymax, __shfl_xor(ymax, o));
-    rmax = fmaxf(rmax, __shfl_xor(rmax, o));
-  }
-  __builtin_amdgcn_wave_barrier();           // (a wave's LDS accesses are processed in order)
-  i64 s = 0, sa = 0;
-  if (lv) {
-    const int kn = (l + 1 == R) ? 0 : l + 1;
-    const i64 c = (i64)sx[l] * sy[kn] - (i64)sy[l] * sx[kn];
-    s = c; sa = (c < 0 ? -c : c);
-  }
-  for (int o = 16; o; o >>= 1) { s += __shfl_xor(s, o); sa += __shfl_xor(sa, o); }
-  if (cv && l == 0) {
+  __syncthreads();
+  const bool cv = c < cnt;
+  float rmax = 0.f;
+  int iy = INT32_MAX, ix = INT32_MAX, iyh = INT32_MIN, ixh = INT32_MIN;
+  if (cv) {
+    const int i = base + c;
+    const float py = pts[2 * i], px = pts[2 * i + 1];
+    float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
+    i64 s = 0, sa = 0;
+    int X0 = 0, Y0 = 0, Xp = 0, Yp = 0;
+    int k = c % R;
+    for (int t = 0; t < R; ++t) {
+      const float d = __int_as_float(rows[c * R + k]);
+      const float2 sc = ssc[k];
+      const float y = py + d * sc.x;   // stardist2d.cpp:454 (compiled with -ffp-contract=off)
+      const float x = px + d * sc.y;   // stardist2d.cpp:455
+      xmin = fminf(xmin, x); xmax = fmaxf(xmax, x);
+      ymin = fminf(ymin, y); ymax = fmaxf(ymax, y);
+      rmax = fmaxf(rmax, d);
+      const int X = (int)(long long)x, Y = (int)(long long)y;   // IntPoint(cInt(x), cInt(y)) :471
+      sx[c * R + k] = X; sy[c * R + k] = Y;
+      if (t) { const i64 cr = (i64)Xp * Y - (i64)Yp * X; s += cr; sa += (cr < 0 ? -cr : cr); }
+      else { X0 = X; Y0 = Y; }
+      Xp = X; Yp = Y;
+      k = (k + 1 == R) ? 0 : k + 1;
+    }
+    { const i64 cr = (i64)Xp * Y0 - (i64)Yp * X0; s += cr; sa += (cr < 0 ? -cr : cr); }      // closes the cycle of R edges
     // area_from_path :128-138: float accumulation of int64 cross products in path order; equals the exact integer sum whenever
-    // sum|term| < 2^24, else the serial order is replayed
+    // sum|term| < 2^24, else the serial order is replayed (from the thread's own row)
     float a;
     if (sa < (1ll << 24)) a = (float)s;
     else {
       a = 0.f;
-      for (int k = 0; k < R; ++k) {
-        const int kn = (k + 1 == R) ? 0 : k + 1;
-        a += (float)((i64)sx[k] * sy[kn] - (i64)sy[k] * sx[kn]);
+      for (int q = 0; q < R; ++q) {
+        const int qn = (q + 1 == R) ? 0 : q + 1;
+        a += (float)((i64)sx[c * R + q] * sy[c * R + qn] - (i64)sy[c * R + q] * sx[c * R + qn]);
       }
     }
     area[i] = (float)(0.5 * (double)fabsf(a));
     radius[i] = rmax;
     bbox[i] = make_int4((int)xmin, (int)xmax, (int)ymin, (int)ymax);   // bbox_intersect takes ints :142-148
+    iy = iyh = (int)floorf(py); ix = ixh = (int)floorf(px);
+  }
+  for (int o = 32; o; o >>= 1) {
+    rmax = fmaxf(rmax, __shfl_xor(rmax, o));
+    iy = min(iy, __shfl_xor(iy, o)); iyh = max(iyh, __shfl_xor(iyh, o));
+    ix = min(ix, __shfl_xor(ix, o)); ixh = max(ixh, __shfl_xor(ixh, o));
+  }
+  if (c == 0) {
+    // contended global atomics only when the running extremum actually improves
     const int rb = __float_as_int(rmax);
-    const int iy = (int)floorf(py), ix = (int)floorf(px);
     volatile int* gs = gstats;
     if (rb > gs[0]) atomicMax(&gstats[0], rb);
     if (iy < gs[1]) atomicMin(&gstats[1], iy);
-    if (iy > gs[2]) atomicMax(&gstats[2], iy);
+    if (iyh > gs[2]) atomicMax(&gstats[2], iyh);
     if (ix < gs[3]) atomicMin(&gstats[3], ix);
-    if (ix > gs[4]) atomicMax(&gstats[4], ix);
+    if (ixh > gs[4]) atomicMax(&gstats[4], ixh);
+  }
+  __syncthreads();
+  {
+    int* gx = vx + (size_t)base * R;
+    int* gy = vy + (size_t)base * R;
+    const int nv = vec4 ? nel >> 2 : 0;
+    for (int e = c; e < nv; e += 64) { ((int4*)gx)[e] = ((const int4*)sx)[e]; ((int4*)gy)[e] = ((const int4*)sy)[e]; }
+    for (int e = 4 * nv + c; e < nel; e += 64) { gx[e] = sx[e]; gy[e] = sy[e]; }
   }
 }
 
@@ -223,6 +255,7 @@ __global__ void k_cell_fill(int N, const int* __restrict__ candCell, const int* 
     int u = -1;
     for (int yy = w.ylo; yy <= w.yhi; ++yy) u += cellStart[yy * g.nx + w.xhi + 1] - cellStart[yy * g.nx + w.xlo];
     slotCap[i] = u;
+    if (i == 0) slotCap[N] = 0;               // (closes the array for the exclusive scan)
   }
 }
 
@@ -252,90 +285,103 @@ __device__ __forceinline__ bool may_interact(const NmsFlags f, const int4 bi, co
   return ok;
 }
 
-// MODE 0: count neighbours, MODE 1: fill CSR (two passes: exact-size lists);
+// The rows of a window are contiguous runs of the cell-ordered records; the runs are walked as ONE list, 64 records per step whatever the
+// row lengths -- a row of ~35 records does not cost a step of its own.  Lane r holds row r's start and the exclusive prefix of the row
+// lengths; nrows and total are wave-uniform (the whole wave walks ONE candidate's window).
+struct WindowRuns { int rbeg, excl, nrows, total; };
+__device__ __forceinline__ WindowRuns window_runs(const GridP g, const Window win, const int* __restrict__ cellStart, int lane) {
+  WindowRuns w;
+  w.nrows = __builtin_amdgcn_readfirstlane(win.yhi - win.ylo + 1);
+  int rbeg = 0, rlen = 0;
+  if (lane < w.nrows) { rbeg = cellStart[(win.ylo + lane) * g.nx + win.xlo]; rlen = cellStart[(win.ylo + lane) * g.nx + win.xhi + 1] - rbeg; }
+  int incl = rlen;
+  for (int o = 1; o < MAX_WIN_ROWS; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+  w.total = __builtin_amdgcn_readlane(incl, w.nrows - 1);
+  w.rbeg = rbeg; w.excl = incl - rlen;
+  return w;
+}
+// body(index into the cell-ordered records, or -1 past the end) is called by the whole wave, once per step.  The row of virtual index v is
+// the last row whose exclusive prefix is <= v (rows may be empty).  A step's 64 indices span few rows: the wave keeps the row of the
+// step's first index and advances it, and only the rows that begin inside the step are compared per lane -- scalar reads of the two lane
+// arrays (before: every row of the window, two cross-lane reads each, in every step).
+template <class Body>
+__device__ __forceinline__ void walk_window(const WindowRuns& w, int lane, Body&& body) {
+  int r0 = 0;
+  for (int t = 0; t < w.total; t += 64) {
+    while (r0 + 1 < w.nrows && __builtin_amdgcn_readlane(w.excl, r0 + 1) <= t) ++r0;
+    int rb = __builtin_amdgcn_readlane(w.rbeg, r0), re = __builtin_amdgcn_readlane(w.excl, r0);
+    const int v = t + lane;
+    for (int r = r0 + 1; r < w.nrows; ++r) {
+      const int e_r = __builtin_amdgcn_readlane(w.excl, r);
+      if (e_r > t + 63) break;
+      const int b_r = __builtin_amdgcn_readlane(w.rbeg, r);
+      if (e_r <= v) { rb = b_r; re = e_r; }
+    }
+    body(v < w.total ? rb + (v - re) : -1);
+  }
+}
+
+// The lists hold a candidate's BETTER-scored (lower-index) neighbours only -- what the greedy scan and the tail batch look at.  The
+// worse-scored ones are not listed: a new survivor finds them by walking its own window (k_round_emit), and only 3 % of the candidates
+// ever become one.  The predicate is symmetric, so the number of ordered neighbour relations is twice the number of entries.
+// MODE 0: count (nbrCount = nbrLow = the list's size), MODE 1: fill CSR (two passes: exact-size lists);
 // MODE 2: ONE pass into per-candidate slots whose capacity is the population of the cells scanned (k_cell_fill slotCap; nbrStart = slot
-// starts): the better-scored neighbours are written from the slot's front, the others from its back, nbrLow / nbrCount (= the number of
-// the others) tell the consumers where each half ends -- the candidate tests of the counting pass are not repeated
+// starts), written from the slot's front; nbrLow tells the consumers where the list ends -- the candidate tests of the counting pass
+// are not repeated
 template <int MODE>
 __global__ void __launch_bounds__(256) k_neighbours(int N, GridP g, NmsFlags f, const CellRec* __restrict__ rec, const int* __restrict__ cellStart,
                                                     int* __restrict__ nbrCount, int* __restrict__ nbrLow, const i64* __restrict__ nbrStart,
-                                                    int* __restrict__ nbr, int* __restrict__ waitOn, int by_bbox, float reach, unsigned long long* __restrict__ total) {
+                                                    int* __restrict__ nbr, int* __restrict__ waitOn, int by_bbox, float reach) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // wave w handles the w-th candidate IN CELL ORDER, and consecutive workgroups of one XCD (blockIdx % 8) get consecutive
-  // cells: the 5x5 cell neighbourhoods of successive waves overlap almost completely and stay in that XCD's L2
+  // cells: the windows of successive waves overlap almost completely and stay in that XCD's L2
   const int per = gridDim.x >> 3;                                   // grid is a multiple of 8
   const int blk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
   const int w = blk * (blockDim.x >> 6) + wave;
   if (w >= N) return;
   const CellRec me = rec[w];
   const int i = me.j;
-  int cy, cx;
-  cell_of(g, me.py, me.px, cy, cx);
   const int4 bi = me.bb;
   const float pyi = me.py, pxi = me.px, ai = me.area;
-  // a candidate's list holds its better-scored (lower-index) neighbours first -- what the greedy scan and the tail batch look at --
-  // then the others -- what a new survivor is paired with: each consumer reads its half only
-  int nLo = 0, nHi = 0;
-  int minj = INT32_MAX;                      // MODE 1: best-scored neighbour above i (first wait target of the greedy scan)
-  const i64 baseLo = MODE ? nbrStart[i] : 0;
-  const i64 baseHi = MODE == 1 ? baseLo + nbrLow[i] : (MODE == 2 ? nbrStart[i + 1] - 1 : 0);      // MODE 2: the slot's last entry, filled downwards
-  // The window's rows are contiguous runs of the cell-ordered records; the runs are walked as ONE list (lane r holds row r's start and its
-  // exclusive prefix), 64 records per step whatever the row lengths -- a row of ~35 records no longer costs a step of its own.
-  const Window win = cell_window(g, by_bbox != 0, reach, bi, pyi, pxi);
-  const int nrows = win.yhi - win.ylo + 1;
-  int rbeg = 0, rlen = 0;
-  if (lane < nrows) { rbeg = cellStart[(win.ylo + lane) * g.nx + win.xlo]; rlen = cellStart[(win.ylo + lane) * g.nx + win.xhi + 1] - rbeg; }
-  int incl = rlen;
-  for (int o = 1; o < MAX_WIN_ROWS; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-  const int total_recs = __shfl(incl, nrows - 1);
-  const int excl = incl - rlen;
-  for (int t = 0; t < total_recs; t += 64) {
-    const int v = t + lane;
+  int nLo = 0;
+  int minj = INT32_MAX;                      // best-scored neighbour above i (first wait target of the greedy scan)
+  const i64 base = MODE ? nbrStart[i] : 0;
+  const WindowRuns runs = window_runs(g, cell_window(g, by_bbox != 0, reach, bi, pyi, pxi), cellStart, lane);
+  walk_window(runs, lane, [&](int ri) {
     bool hit = false;
     int j = -1;
-    {
-      // the row of virtual index v: the last row whose exclusive prefix is <= v (rows may be empty)
-      int rb = 0, re = 0;
-      for (int r = 0; r < nrows; ++r) {
-        const int e_r = __shfl(excl, r), b_r = __shfl(rbeg, r);
-        if (e_r <= v) { rb = b_r; re = e_r; }
-      }
-      if (v < total_recs) {
-        const CellRec r = rec[rb + (v - re)];
-        j = r.j;
-        if (j != i) hit = may_interact(f, bi, r.bb, pyi, pxi, r.py, r.px, ai, r.area);
-      }
+    if (ri >= 0) {
+      const CellRec r = rec[ri];
+      j = r.j;
+      if (j < i) hit = may_interact(f, bi, r.bb, pyi, pxi, r.py, r.px, ai, r.area);
     }
-    const unsigned long long mLo = __ballot(hit && j < i), mHi = __ballot(hit && j > i);
-    if (MODE && hit) {
-      const unsigned long long below = (1ull << lane) - 1;
-      if (j < i) { nbr[baseLo + nLo + __popcll(mLo & below)] = j; if (j < minj) minj = j; }
-      else if (MODE == 1) nbr[baseHi + nHi + __popcll(mHi & below)] = j;
-      else nbr[baseHi - (nHi + __popcll(mHi & below))] = j;
-    }
-    nLo += __popcll(mLo); nHi += __popcll(mHi);
-  }
-  if (!MODE && lane == 0) { nbrCount[i] = nLo + nHi; nbrLow[i] = nLo; }
-  if (MODE == 2 && lane == 0) nbrLow[i] = nLo;          // (the total is summed by k_sum_halves: one atomic per candidate on one word serialises at the L2)
-  if (MODE && lane == 0) nbrCount[i] = nHi;            // from here on nbrCount holds the size of the worse-scored half (k_round_emit)
+    const unsigned long long m = __ballot(hit);
+    if (MODE && hit) { nbr[base + nLo + __popcll(m & ((1ull << lane) - 1))] = j; if (j < minj) minj = j; }
+    nLo += __popcll(m);
+  });
+  if (!MODE && lane == 0) nbrCount[i] = nLo;
+  if (MODE != 1 && lane == 0) nbrLow[i] = nLo;
   if (MODE) {
     for (int o = 32; o; o >>= 1) minj = min(minj, __shfl_xor(minj, o));
     if (lane == 0) waitOn[i] = (minj < i) ? minj : WAIT_NONE;
   }
 }
 
-// Round kernel B: wave per new survivor: mark it, emit the pairs the reference would evaluate.
+// Round kernel B: wave per new survivor: mark it, emit the pairs the reference would evaluate.  The survivor walks its own cell window
+// over the cell-ordered records (the walk of k_neighbours): the window covers every j the filters below accept -- with the bbox test
+// in force j's bounding box meets i's, without it j's centre lies within max_dist + radius[i] < 2 reach of i's -- and the record holds
+// everything the filters read of j.
 constexpr int EMIT_STAGE = 512;
 __global__ void __launch_bounds__(256) k_round_emit(const int* __restrict__ K, const int* __restrict__ nKPtr, unsigned char* __restrict__ state,
-                                                    const i64* __restrict__ nbrStart, const int* __restrict__ nbrHigh, const int* __restrict__ nbr, NmsFlags f,
-                                                    const float* __restrict__ pts, const int4* __restrict__ bbox,
+                                                    GridP g, const CellRec* __restrict__ rec, const int* __restrict__ cellStart, int by_bbox, float reach,
+                                                    NmsFlags f, const float* __restrict__ pts, const int4* __restrict__ bbox,
                                                     const float* __restrict__ radius, const float* __restrict__ area,
                                                     int2* __restrict__ pairs, unsigned long long* pairCount,
                                                     unsigned long long pairCap) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int nK = *nKPtr;                               // persistent grid: the survivor count of this round is read on the device
-  // pairs are staged per wave in LDS and appended with ONE atomic per EMIT_STAGE pairs: an atomic per 64-entry chunk of a neighbour list
-  // (1.5 x 10^5 of them on one counter in round 1 at 2048^2) serialises at the L2
+  // pairs are staged per wave in LDS and appended with ONE atomic per EMIT_STAGE pairs: an atomic per 64-record step of a window
+  // serialises at the L2
   __shared__ int2 stage[4][EMIT_STAGE];
   int nst = 0;                                         // (wave-uniform)
   auto flush = [&]() {
@@ -349,49 +395,48 @@ __global__ void __launch_bounds__(256) k_round_emit(const int* __restrict__ K, c
     nst = 0;
   };
   for (int w = blockIdx.x * (blockDim.x >> 6) + wave; w < nK; w += gridDim.x * (blockDim.x >> 6)) {
-  const int i = K[w];
-  if (lane == 0) state[i] = ST_KEPT;
-  const i64 end = nbrStart[i + 1], beg = end - nbrHigh[i];             // the neighbours scored below i (the back of i's slot)
-  const int4 bi = bbox[i];
-  const float pyi = pts[2 * i], pxi = pts[2 * i + 1];
-  const float rad = f.max_dist + radius[i];
-  const float rad2 = rad * rad;                       // stardist2d.cpp:549
-  for (i64 t = beg; t < end; t += 64) {
-    const i64 idx = t + lane;
-    bool emit = false;
-    int j = -1;
-    if (idx < end) {
-      j = nbr[idx];
-      if (j > i && state[j] == ST_UNDECIDED) {        // :572
-        bool ok = true;
-        if (f.use_kdtree) {                           // nanoflann L2_Simple, strict '<' (nanoflann.hpp:249-253)
-          const float d0 = pyi - pts[2 * j], d1 = pxi - pts[2 * j + 1];
+    const int i = K[w];
+    if (lane == 0) state[i] = ST_KEPT;
+    const int4 bi = bbox[i];
+    const float pyi = pts[2 * i], pxi = pts[2 * i + 1];
+    const double ai = (double)area[i] + 1.e-10;
+    const float rad = f.max_dist + radius[i];
+    const float rad2 = rad * rad;                       // stardist2d.cpp:549
+    const WindowRuns runs = window_runs(g, cell_window(g, by_bbox != 0, reach, bi, pyi, pxi), cellStart, lane);
+    walk_window(runs, lane, [&](int ri) {
+      bool emit = false;
+      int j = -1;
+      if (ri >= 0) {
+        const CellRec r = rec[ri];
+        j = r.j;
+        bool ok = j > i;
+        if (ok && f.use_kdtree) {                       // nanoflann L2_Simple, strict '<' (nanoflann.hpp:249-253)
+          const float d0 = pyi - r.py, d1 = pxi - r.px;
           float d2 = d0 * d0; d2 += d1 * d1;
           ok = d2 < rad2;
         }
         if (ok && (f.use_bbox || f.thr_nonneg)) {
-          const int4 bj = bbox[j];
+          const int4 bj = r.bb;
           ok = bbox_intersect(bi, bj);                                               // :576
           if (ok && f.thr_nonneg) {
             // rigorous upper bound: Clipper's output (input vertices + lattice-rounded crossings) stays inside the
             // intersection of the two integer bounding boxes, so area_inter <= w*h; if even that cannot exceed
             // the threshold the reference's  overlap > thr  (:580-581) is false without running the sweep.
             const double w = (double)(min(bi.y, bj.y) - max(bi.x, bj.x)), hgt = (double)(min(bi.w, bj.w) - max(bi.z, bj.z));
-            const float ub = (float)((w * hgt) / fmin((double)area[i] + 1.e-10, (double)area[j] + 1.e-10));   // monotone in the area
+            const float ub = (float)((w * hgt) / fmin(ai, (double)r.area + 1.e-10));   // monotone in the area
             if (!(ub > f.thr)) ok = false;
           }
         }
-        emit = ok;
+        emit = ok && state[j] == ST_UNDECIDED;          // :572 (read last: the only gather of the walk)
       }
-    }
-    const unsigned long long m = __ballot(emit);
-    if (m) {
-      const int c = __popcll(m);
-      if (nst + c > EMIT_STAGE) flush();
-      if (emit) stage[wave][nst + __popcll(m & ((1ull << lane) - 1))] = make_int2(i, j);
-      nst += c;
-    }
-  }
+      const unsigned long long m = __ballot(emit);
+      if (m) {
+        const int c = __popcll(m);
+        if (nst + c > EMIT_STAGE) flush();
+        if (emit) stage[wave][nst + __popcll(m & ((1ull << lane) - 1))] = make_int2(i, j);
+        nst += c;
+      }
+    });
   }
   flush();
 }
@@ -610,14 +655,28 @@ __global__ void k_defer_undecided(const int2* __restrict__ pairs, const unsigned
 // tail batch with both kinds of deferred pairs: all become entries 0 .. nDef-1 of the pair list; kind 0 -> general-path queue and
 // decided[t] = 3 (the sweeps skip them), kind 1 -> decided[t] = 0 (bucketed and swept with the tail's own undecided pairs).
 // *nExact must be zero on entry; *nJoin receives the number of kind-0 pairs (the queue's prefix).
+// A kind-1 pair whose j another survivor's pair has suppressed since it was deferred is not swept (decided[t] = 4, counted in *nSkipped):
+// its supp[] stays 0, j's state is final.
 __global__ void k_tail_init2(Deferred d, const unsigned char* __restrict__ kind, int2* __restrict__ pairs, unsigned int* __restrict__ exact,
-                             unsigned long long* nPairs, unsigned int* nExact, unsigned int* firstNew, unsigned char* __restrict__ decided) {
+                             unsigned long long* nPairs, unsigned int* nExact, unsigned int* firstNew, unsigned char* __restrict__ decided,
+                             const unsigned char* __restrict__ state, unsigned int* __restrict__ nSkipped) {
   unsigned int n = *d.count; if (n > d.cap) n = d.cap;
   for (unsigned int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
-    pairs[t] = d.pairs[t];
-    if (kind[t] == 0) { exact[atomicAdd(nExact, 1u)] = t; decided[t] = 3; } else decided[t] = 0;
+    const int2 ij = d.pairs[t];
+    pairs[t] = ij;
+    if (kind[t] == 0) { exact[atomicAdd(nExact, 1u)] = t; decided[t] = 3; }
+    else if (state[ij.y] == ST_SUPPRESSED) { decided[t] = 4; atomicAdd(nSkipped, 1u); }
+    else decided[t] = 0;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) { *nPairs = n; *firstNew = n; }
+}
+// the per-candidate arrays of the greedy rounds in their initial state, in one launch (before: an iota kernel and four fill commands)
+__global__ void k_round_lists_init(int N, int* __restrict__ U, unsigned char* __restrict__ state, unsigned char* __restrict__ pend,
+                                   int* __restrict__ head, unsigned int* __restrict__ dcount) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) *dcount = 0;
+  if (i >= N) return;
+  U[i] = i; state[i] = ST_UNDECIDED; pend[i] = 0; head[i] = -1;
 }
 __global__ void k_copy_u32(unsigned int* dst, const unsigned int* src) { *dst = *src; }
 // a sweep launch over fewer pairs than this is pure latency (98 304 pairs are in flight at once): option "nms2d_defer_max", default 16 384
@@ -691,6 +750,11 @@ __global__ void __launch_bounds__(1024) k_tail_resolve(const int* __restrict__ U
 // list [first, n) is therefore bucketed by the quantised centre offset (dy major, dx minor) before tier 1: histogram, scan,
 // scatter of PAIR INDICES -- the kernels behind it already work on index lists.  Decisions are per pair, so the order (and the
 // arbitrary order inside a bucket) cannot change any result.
+// state != nullptr (normal rounds: decisions are applied to state[j]): a pair whose j the decision kernel of this round has already
+// suppressed through another pair is left out of the work list, as the reference does (`if suppressed[j] continue`) -- a sweep launch lasts
+// as long as its busiest wave's lanes take one after the other.  Both kernels apply the same predicate and state does not change between
+// them; the count kernel counts the pairs left out (*nSkipped).
+__device__ __forceinline__ bool pair_j_suppressed(const unsigned char* __restrict__ state, int2 ij) { return state && state[ij.y] == ST_SUPPRESSED; }
 constexpr int PAIR_BUCKETS = 4096;
 // key = (local-minima class of the two polygons [nl], dy bin [ny], dx bin [nx]); nl * ny * nx <= PAIR_BUCKETS
 struct PairKey { const char* prep; size_t prepStride; float inv; int nl, ny, nx; };
@@ -708,15 +772,23 @@ __device__ __forceinline__ int pair_bucket(const float* __restrict__ pts, int2 i
 }
 __global__ void __launch_bounds__(256) k_pair_bucket_count(const int2* __restrict__ pairs, const unsigned long long* __restrict__ nPtr,
                                                            const unsigned int* __restrict__ firstPtr, const float* __restrict__ pts, PairKey key,
-                                                           unsigned int* __restrict__ hist, const unsigned char* __restrict__ decided) {
+                                                           unsigned int* __restrict__ hist, const unsigned char* __restrict__ decided,
+                                                           const unsigned char* __restrict__ state, unsigned int* __restrict__ nSkipped) {
   __shared__ unsigned int h[PAIR_BUCKETS];
+  __shared__ unsigned int skipped;
   for (int b = threadIdx.x; b < PAIR_BUCKETS; b += 256) h[b] = 0;
+  if (threadIdx.x == 0) skipped = 0;
   __syncthreads();
   const unsigned long long n = *nPtr, first = firstPtr ? *firstPtr : 0u;
-  for (unsigned long long t = first + (unsigned long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (unsigned long long)gridDim.x * 256)
-    if (!decided || !decided[t]) atomicAdd(&h[pair_bucket(pts, pairs[t], key)], 1u);
+  for (unsigned long long t = first + (unsigned long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (unsigned long long)gridDim.x * 256) {
+    if (decided && decided[t]) continue;
+    const int2 ij = pairs[t];
+    if (pair_j_suppressed(state, ij)) { atomicAdd(&skipped, 1u); continue; }
+    atomicAdd(&h[pair_bucket(pts, ij, key)], 1u);
+  }
   __syncthreads();
   for (int b = threadIdx.x; b < PAIR_BUCKETS; b += 256) if (h[b]) atomicAdd(&hist[b], h[b]);
+  if (threadIdx.x == 0 && skipped) atomicAdd(nSkipped, skipped);
 }
 __global__ void __launch_bounds__(1024) k_pair_bucket_scan(const unsigned int* __restrict__ hist, unsigned int* __restrict__ cursor,
                                                            unsigned long long* __restrict__ nOrdered) {
@@ -741,11 +813,13 @@ __global__ void __launch_bounds__(1024) k_pair_bucket_scan(const unsigned int* _
 __global__ void __launch_bounds__(256) k_pair_bucket_scatter(const int2* __restrict__ pairs, const unsigned long long* __restrict__ nPtr,
                                                              const unsigned int* __restrict__ firstPtr, const float* __restrict__ pts, PairKey key,
                                                              unsigned int* __restrict__ cursor, unsigned int* __restrict__ order, unsigned int cap,
-                                                             const unsigned char* __restrict__ decided) {
+                                                             const unsigned char* __restrict__ decided, const unsigned char* __restrict__ state) {
   const unsigned long long n = *nPtr, first = firstPtr ? *firstPtr : 0u;
   for (unsigned long long t = first + (unsigned long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (unsigned long long)gridDim.x * 256) {
     if (decided && decided[t]) continue;
-    const unsigned int k = atomicAdd(&cursor[pair_bucket(pts, pairs[t], key)], 1u);
+    const int2 ij = pairs[t];
+    if (pair_j_suppressed(state, ij)) continue;
+    const unsigned int k = atomicAdd(&cursor[pair_bucket(pts, ij, key)], 1u);
     if (k < cap) order[k] = (unsigned int)t;
   }
 }
@@ -762,7 +836,7 @@ int clip_full_pairs(const int2* d_pairs, const unsigned int* d_idx, const unsign
 }
 
 namespace {
-struct Counters { int nU, nK, nS, left; unsigned long long nPairs; unsigned int nSpill, nExact, nErr, nDecided; };
+struct Counters { int nU, nK, nS, left; unsigned long long nPairs; unsigned int nSpill, nExact, nErr, nDecided, nSkipped; };
 
 // prepared polygons + the two tiers of the bound-slot pair kernel for one vertex capacity
 template <int MAXV, int SPREP>
@@ -815,6 +889,49 @@ struct BeamPath {
 };
 }  // namespace
 
+namespace {
+// The build step of sd_nms2d_device and of its probe sd_nms2d_build_device: the table of ray directions (host libm: the device never
+// evaluates sinf / cosf; stardist2d.cpp:419,454-455) and the initial gstats in ONE block and one copy -- every copy or fill command in front
+// of the neighbour lists costs 3-6 us and a gap on the critical path -- then k_build32 (n_rays <= 32) or k_build.  *gstatsOut: 8 ints.
+int launch_build(sd::Arena& A, hipStream_t s, const float* d_dist, const float* d_points, int N, int R, int* vx, int* vy, int4* bbox,
+                 float* radius, float* area, int** gstatsOut, hipEvent_t evStart) {
+  const int gs_init[8] = {0, INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN, 0, 0, 0};
+  std::vector<float> hdr(8 + 2 * (size_t)R);
+  memcpy(hdr.data(), gs_init, sizeof(gs_init));
+  const float ANGLE_PI = 2 * M_PI / R;
+  for (int k = 0; k < R; ++k) { hdr[8 + 2 * k] = sinf(ANGLE_PI * k); hdr[8 + 2 * k + 1] = cosf(ANGLE_PI * k); }
+  int* gstats = A.take_n<int>(8 + 2 * (size_t)R);
+  if (!gstats) return -1;
+  const float2* d_sc = (const float2*)(gstats + 8);
+  SD_CHECK(hipMemcpyAsync(gstats, hdr.data(), hdr.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  if (evStart) SD_CHECK(hipEventRecord(evStart, s));
+  if (R <= 32) {
+    const int vec4 = ((((uintptr_t)d_dist | (uintptr_t)vx | (uintptr_t)vy) & 15) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(k_build32, dim3(sd::div_up(N, 64)), dim3(64), 2 * 64 * (size_t)R * sizeof(int), s, d_dist, d_points, d_sc, N, R, vec4,
+                       vx, vy, bbox, radius, area, gstats);
+  } else
+    hipLaunchKernelGGL(k_build, dim3(sd::div_up(N, 4)), dim3(256), 4 * 2 * R * sizeof(int), s, d_dist, d_points, d_sc, N, R,
+                       vx, vy, bbox, radius, area, gstats);
+  SD_LAUNCH_CHECK();
+  *gstatsOut = gstats;
+  return 0;
+}
+}  // namespace
+
+extern "C" int sd_nms2d_build_device(const float* d_dist, const float* d_points, int n_polys, int n_rays, int32_t* d_vx, int32_t* d_vy,
+                                     int32_t* d_bbox, float* d_radius, float* d_area, int32_t* d_gstats, void* stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  if (n_polys <= 0) return 0;
+  if (n_rays < 1 || n_rays > 256) { sd::set_error("sd_nms2d_build: n_rays=%d unsupported (1..256)", n_rays); return -1; }
+  sd::Arena& A = sd::arena();
+  if (A.begin(s)) return -1;
+  int* gstats = nullptr;
+  if (launch_build(A, s, d_dist, d_points, n_polys, n_rays, d_vx, d_vy, (int4*)d_bbox, d_radius, d_area, &gstats, nullptr)) return -1;
+  SD_CHECK(hipMemcpyAsync(d_gstats, gstats, 5 * sizeof(int), hipMemcpyDeviceToDevice, s));
+  SD_CHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
 extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n_polys, int n_rays, int use_kdtree,
                                int use_bbox, int verbose, float threshold, uint8_t* d_keep, int64_t* stats,
                                void* stream_) {
@@ -847,31 +964,16 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
     return 0;
   }
 
-  // host-side sin/cos table with the host libm (stardist2d.cpp:419,454-455)
-  std::vector<float2> sc(R);
-  const float ANGLE_PI = 2 * M_PI / R;
-  for (int k = 0; k < R; ++k) { sc[k].x = sinf(ANGLE_PI * k); sc[k].y = cosf(ANGLE_PI * k); }
-  float2* d_sc = A.take_n<float2>(R);
   int* vx = A.take_n<int>((size_t)N * R);
   int* vy = A.take_n<int>((size_t)N * R);
   int4* bbox = A.take_n<int4>(N);
   float* radius = A.take_n<float>(N);
   float* area = A.take_n<float>(N);
-  int* gstats = A.take_n<int>(8);
   unsigned char* state = A.take_n<unsigned char>(N);
   int* candCell = A.take_n<int>(N);
-  if (!d_sc || !vx || !vy || !bbox || !radius || !area || !gstats || !state || !candCell) return -1;
-  SD_CHECK(hipMemcpyAsync(d_sc, sc.data(), R * sizeof(float2), hipMemcpyHostToDevice, s));
-  const int gs_init[8] = {0, INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN, 0, 0, 0};
-  SD_CHECK(hipMemcpyAsync(gstats, gs_init, sizeof(gs_init), hipMemcpyHostToDevice, s));
-  SD_CHECK(hipMemsetAsync(state, 0, N, s));
-  if (stats) SD_CHECK(hipEventRecord(ev0, s));
-  if (R <= 32)
-    hipLaunchKernelGGL(k_build32, dim3(sd::div_up(N, 8)), dim3(256), 0, s, d_dist, d_points, d_sc, N, R, vx, vy, bbox, radius, area, gstats);
-  else
-    hipLaunchKernelGGL(k_build, dim3(sd::div_up(N, 4)), dim3(256), 4 * 2 * R * sizeof(int), s, d_dist, d_points, d_sc, N, R,
-                       vx, vy, bbox, radius, area, gstats);
-  SD_LAUNCH_CHECK();
+  int* gstats = nullptr;
+  if (!vx || !vy || !bbox || !radius || !area || !state || !candCell) return -1;
+  if (launch_build(A, s, d_dist, d_points, N, R, vx, vy, bbox, radius, area, &gstats, stats ? ev0 : nullptr)) return -1;
   // ---- prepared polygons (Clipper::AddPath once per candidate), on a second stream: they depend on the integer vertices only, the
   // grid and the neighbour lists that follow on the caller's stream do not need them (0.84 ms of independent work at 2048^2)
   size_t prepStride;
@@ -937,16 +1039,15 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
   }
   g.y0 = (float)gs[1]; g.x0 = (float)gs[3]; g.inv_cs = 1.f / cs;
   const int nCells = g.ny * g.nx;
-  int* cellCount = A.take_n<int>(nCells + 1);
+  int* cellCount = A.take_n<int>(2 * ((size_t)nCells + 1));          // the two arrays that start at zero in one block: one fill
+  int* cellFill = cellCount ? cellCount + nCells + 1 : nullptr;
   int* cellStart = A.take_n<int>(nCells + 1);
-  int* cellFill = A.take_n<int>(nCells + 1);
   CellRec* cellRec = (CellRec*)A.take((size_t)N * sizeof(CellRec));
   int* nbrCount = A.take_n<int>(N + 1);
   i64* nbrStart = A.take_n<i64>(N + 1);
   int* nbrLow = A.take_n<int>(N + 1);
   if (!cellCount || !cellStart || !cellFill || !cellRec || !nbrCount || !nbrStart || !nbrLow) return -1;
-  SD_CHECK(hipMemsetAsync(cellCount, 0, (nCells + 1) * sizeof(int), s));
-  SD_CHECK(hipMemsetAsync(cellFill, 0, (nCells + 1) * sizeof(int), s));
+  SD_CHECK(hipMemsetAsync(cellCount, 0, 2 * ((size_t)nCells + 1) * sizeof(int), s));
   hipLaunchKernelGGL(k_cell_count, dim3(sd::div_up(N, 256)), dim3(256), 0, s, d_points, N, g, cellCount, candCell);
   SD_LAUNCH_CHECK();
   size_t tmpBytes = 0, tmpBytes2 = 0;
@@ -957,11 +1058,11 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
   if (!scanTmp) return -1;
   SD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp, tmpBytes, cellCount, cellStart, nCells + 1, s));
   // Neighbour lists in ONE pass (option "nms2d_neighbours_single_pass", default 1): every candidate gets a slot as large as the population
-  // of the cells its list is built from (known from the cell table: no candidate test needed), the lists are written into the slots --
-  // better-scored neighbours from the front, the others from the back -- and the exact total is counted on the way.  The two-pass form
+  // of the cells its list is built from (known from the cell table: no candidate test needed), the lists -- the better-scored neighbours
+  // only -- are written into the slots from their front and the exact total is counted on the way.  The two-pass form
   // (count, scan, fill: every candidate test done twice, 1.2 + 0.8 ms at 2048^2) remains for inputs whose slots would exceed 32-bit indices or the workspace.
   const bool singlePass = sd::option(sd::OPT_NMS2D_NBR_SINGLE) != 0;
-  SD_CHECK(hipMemsetAsync(nbrCount, 0, (N + 1) * sizeof(int), s));
+  // (k_cell_fill writes every slot capacity and the closing zero; the two-pass form clears nbrCount itself)
   hipLaunchKernelGGL(k_cell_fill, dim3(sd::div_up(N, 256)), dim3(256), 0, s, N, candCell, cellStart, cellFill, d_points, bbox, area, cellRec, g, by_bbox, reach,
                      singlePass ? nbrCount : (int*)nullptr);
   SD_LAUNCH_CHECK();
@@ -972,10 +1073,7 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
   int* head0 = A.take_n<int>(N);
   unsigned int* dcount0 = A.take_n<unsigned int>(1);
   if (!U0 || !pend0 || !head0 || !dcount0) return -1;
-  hipLaunchKernelGGL(k_iota, dim3(sd::div_up(N, 256)), dim3(256), 0, s, U0, N);
-  SD_CHECK(hipMemsetAsync(pend0, 0, N, s));
-  SD_CHECK(hipMemsetAsync(head0, 0xFF, (size_t)N * sizeof(int), s));
-  SD_CHECK(hipMemsetAsync(dcount0, 0, sizeof(unsigned int), s));
+  hipLaunchKernelGGL(k_round_lists_init, dim3(sd::div_up(N, 256)), dim3(256), 0, s, N, U0, state, pend0, head0, dcount0);
 
   NmsFlags f;
   f.use_kdtree = use_kdtree; f.use_bbox = use_bbox; f.thr_nonneg = (threshold >= 0.f); f.thr = threshold; f.max_dist = max_dist;
@@ -983,17 +1081,15 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
   // ---- neighbour CSR (build_neighbour_lists, nms_rounds.h)
   const int nbBlocks = (sd::div_up(N, 4) + 7) & ~7;
   NbrLists L{};
-  L.count = nbrCount; L.low = nbrLow; L.start = nbrStart;
+  L.count = nbrCount; L.low = nbrLow; L.start = nbrStart; L.lowOnly = true;
   auto launch_neighbours = [&](int mode, const NbrLists& l) {
     if (mode == 0)
       hipLaunchKernelGGL((k_neighbours<0>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nullptr, (int*)nullptr,
-                         (int*)nullptr, by_bbox, reach, (unsigned long long*)nullptr);
+                         (int*)nullptr, by_bbox, reach);
     else if (mode == 1)
-      hipLaunchKernelGGL((k_neighbours<1>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nbrStart, l.nbr, l.waitOn, by_bbox, reach,
-                         (unsigned long long*)nullptr);
+      hipLaunchKernelGGL((k_neighbours<1>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nbrStart, l.nbr, l.waitOn, by_bbox, reach);
     else
-      hipLaunchKernelGGL((k_neighbours<2>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nbrStart, l.nbr, l.waitOn, by_bbox, reach,
-                         (unsigned long long*)nullptr);
+      hipLaunchKernelGGL((k_neighbours<2>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nbrStart, l.nbr, l.waitOn, by_bbox, reach);
   };
   const int rcLists = build_neighbour_lists(A, s, N, singlePass, scanTmp, tmpBytes, launch_neighbours, launch_side, L);
   // capacity of one call: neighbour lists and pair queues are indexed with 32 bits.  Beyond it (about 13 M candidates at the density
@@ -1006,7 +1102,7 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
   if (rcLists) return -1;
   const int* nbr = L.nbr;
   int* waitOn = L.waitOn;
-  const i64 totalNbr = L.total;
+  const i64 totalNbr = 2 * L.total;            // ordered neighbour relations: the lists hold each unordered pair once (at its worse-scored end)
 
   // (the prepared polygons are being written on the side stream meanwhile; the sweep kernels are their first readers and wait for
   // evPrep in run_pairs -- with the shortcut on, the decision kernel of round 1 runs before that and only needs the properties)
@@ -1032,7 +1128,7 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
   if (!U0 || !U1 || !K || !pairs || !spillPairs || !exactPairs || !Sl || !d_cnt || !bucketHist || !nOrdered || (pairSort && R <= 32 && !pairOrder)) return -1;
   unsigned char* decided = (areaBounds && pairOrder) ? A.take_n<unsigned char>(pairCap) : nullptr;       // (the shortcut filters through the ordered index list)
   if (areaBounds && pairOrder && !decided) return -1;
-  i64 totalDecided = 0;
+  i64 totalDecided = 0, totalSkipped = 0;      // pairs decided by the area enclosure; pairs not swept because j was suppressed meanwhile
   int nU = N, rounds = 0;
   i64 totalPairs = 0, totalExact = 0, totalSpill = 0;
   int* Ucur = U0; int* Unext = U1;
@@ -1098,10 +1194,12 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
         // tail batch with deferred undecided pairs: they sit in the list's prefix with decided[] = 0 and are bucketed with the rest
         const unsigned int* bfirst = (suppOut && deferFrom > 0) ? nullptr : first;
         SD_CHECK(hipStreamWaitEvent(s, evPrep, 0));          // the prepared polygons (side stream; complete long before, except in round 1)
-        hipLaunchKernelGGL(k_pair_bucket_count, dim3(512), dim3(256), 0, s, pairs, &d_cnt->nPairs, bfirst, d_points, key, bucketHist, decided);
+        const unsigned char* liveState = suppOut ? nullptr : state;      // normal round: pairs whose j is suppressed by now are not swept
+        hipLaunchKernelGGL(k_pair_bucket_count, dim3(512), dim3(256), 0, s, pairs, &d_cnt->nPairs, bfirst, d_points, key, bucketHist, decided, liveState,
+                           &d_cnt->nSkipped);
         hipLaunchKernelGGL(k_pair_bucket_scan, dim3(1), dim3(1024), 0, s, bucketHist, bucketHist + PAIR_BUCKETS, nOrdered);
         hipLaunchKernelGGL(k_pair_bucket_scatter, dim3(512), dim3(256), 0, s, pairs, &d_cnt->nPairs, bfirst, d_points, key, bucketHist + PAIR_BUCKETS,
-                           pairOrder, qCap, decided);
+                           pairOrder, qCap, decided, liveState);
         SD_LAUNCH_CHECK();
         rc = BeamPath<32, 64>::tier1(pairs, pairOrder, nOrdered, (const unsigned int*)nullptr, prep, area, threshold, state, suppOut, q1, s);
       } else {
@@ -1136,13 +1234,13 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
   auto account = [&](const char* what) -> int {
     if (h.nPairs > pairCap || h.nSpill > qCap || h.nExact > qCap) { sd::set_error("sd_nms2d: pair queue overflow (internal error)"); return -1; }
     if (h.nErr) { sd::set_error("sd_nms2d: %u pairs exceeded the general path's fixed capacities or the deferred-pair list (with more than 64 rays: at least that many; the launch stops at the first)", h.nErr); return -1; }
-    totalPairs += (i64)h.nPairs; totalExact += h.nExact; totalSpill += h.nSpill; totalDecided += h.nDecided;
+    totalPairs += (i64)h.nPairs; totalExact += h.nExact; totalSpill += h.nSpill; totalDecided += h.nDecided; totalSkipped += h.nSkipped;
     if (stats) {
       float ms = 0, ms2 = 0;
       SD_CHECK(hipEventElapsedTime(&ms, ev0, ev1)); SD_CHECK(hipEventElapsedTime(&ms2, ev2, ev3));
       if (h.nPairs) { ns_pairs += ms * 1e6; ++n_pair_launches; }
       ns_full += ms2 * 1e6;
-      if (sd::option(sd::OPT_TRACE)) printf("%s %d: nU=%d nK=%d pairs=%llu decided by the area enclosure=%u spill=%u exact=%u pair_kernel=%.3f ms general_path=%.3f ms\n", what, rounds, h.nU, h.nK, h.nPairs, h.nDecided, h.nSpill, h.nExact, ms, ms2);
+      if (sd::option(sd::OPT_TRACE)) printf("%s %d: nU=%d nK=%d pairs=%llu decided by the area enclosure=%u j already suppressed=%u spill=%u exact=%u pair_kernel=%.3f ms general_path=%.3f ms\n", what, rounds, h.nU, h.nK, h.nPairs, h.nDecided, h.nSkipped, h.nSpill, h.nExact, ms, ms2);
     }
     return 0;
   };
@@ -1157,7 +1255,8 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
       SD_CHECK(hipMemsetAsync(supp, 0, pairCap, s));
       const int wg = sd::div_up(nU, 4) < 2048 ? sd::div_up(nU, 4) : 2048;
       if (deferFrom > 0) {
-        hipLaunchKernelGGL(k_tail_init2, dim3(64), dim3(256), 0, s, dfr, defKind, pairs, exactPairs, &d_cnt->nPairs, &d_cnt->nExact, firstNew, decided);
+        hipLaunchKernelGGL(k_tail_init2, dim3(64), dim3(256), 0, s, dfr, defKind, pairs, exactPairs, &d_cnt->nPairs, &d_cnt->nExact, firstNew, decided, state,
+                           &d_cnt->nSkipped);
         hipLaunchKernelGGL(k_copy_u32, dim3(1), dim3(1), 0, s, nJoinDef, &d_cnt->nExact);
       } else
         hipLaunchKernelGGL(k_tail_init, dim3(64), dim3(256), 0, s, dfr, pairs, exactPairs, &d_cnt->nPairs, &d_cnt->nExact, firstNew);
@@ -1202,7 +1301,7 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
     hipLaunchKernelGGL(k_round_triage, dim3(sd::div_up(nU, 1024)), dim3(1024), 0, s, Ucur, nU, state, waitOn, Unext, K, Sl, (int*)d_cnt, dfr.pend);
     const int wgrid = sd::div_up(nU, 4) < 2048 ? sd::div_up(nU, 4) : 2048;
     hipLaunchKernelGGL(k_round_scan, dim3(wgrid), dim3(256), 0, s, Sl, state, nbrStart, nbrLow, nbr, waitOn, Unext, K, (int*)d_cnt, dfr.pend);
-    hipLaunchKernelGGL(k_round_emit, dim3(wgrid), dim3(256), 0, s, K, &d_cnt->nK, state, nbrStart, nbrCount, nbr, f, d_points, bbox,
+    hipLaunchKernelGGL(k_round_emit, dim3(wgrid), dim3(256), 0, s, K, &d_cnt->nK, state, g, cellRec, cellStart, by_bbox, reach, f, d_points, bbox,
                        radius, area, pairs, &d_cnt->nPairs, pairCap);
     SD_LAUNCH_CHECK();
     if (run_pairs(nullptr)) return -1;
@@ -1223,7 +1322,7 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
   SD_CHECK(hipStreamSynchronize(s));
   if (stats) { stats[0] = totalPairs; stats[1] = totalExact; stats[2] = rounds; stats[3] = totalNbr;
                stats[4] = (int64_t)ns_pairs; stats[5] = n_pair_launches; stats[6] = (int64_t)ns_full; stats[7] = (int64_t)ns_pre;
-               stats[8] = totalSpill; stats[9] = totalDecided; stats[10] = totalUndecDeferred; }
+               stats[8] = totalSpill; stats[9] = totalDecided; stats[10] = totalUndecDeferred; stats[11] = totalSkipped; }
   if (verbose) {
     printf("NMS: %lld pair intersections (%lld on the exact-join path), %d greedy rounds, %lld neighbour entries\n",
            (long long)totalPairs, (long long)totalExact, rounds, (long long)totalNbr);

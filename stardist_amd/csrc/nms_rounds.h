@@ -22,12 +22,12 @@ __global__ void k_keep(const unsigned char* __restrict__ state, unsigned char* _
   if (i < n) keep[i] = (state[i] != ST_SUPPRESSED);
 }
 
-// exact number of list entries of the single-pass form: sum of both halves' sizes, one atomic per workgroup
-// (one atomic per candidate on one word serialises at the L2)
+// exact number of list entries of the single-pass form: sum of both halves' sizes (nHigh == nullptr: the lists have no second half),
+// one atomic per workgroup (one atomic per candidate on one word serialises at the L2)
 __global__ void __launch_bounds__(256) k_sum_halves(const int* __restrict__ nLow, const int* __restrict__ nHigh, int N, unsigned long long* total) {
   __shared__ unsigned long long ws[4];
   unsigned long long v = 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) v += (unsigned long long)(nLow[i] + nHigh[i]);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) v += (unsigned long long)(nLow[i] + (nHigh ? nHigh[i] : 0));
   for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -140,17 +140,20 @@ __global__ void __launch_bounds__(256) k_round_scan(const int* __restrict__ S, c
 
 // The neighbour lists of all candidates in one array: candidate i's entries start at start[i], its low[i] better-scored neighbours
 // first -- what the list scan and the tail batches look at -- then its count[i] others -- what a new survivor is paired with.
+// lowOnly (2D): the caller's kernel lists the better-scored neighbours only; count[] then holds the slot capacities resp. the counting
+// pass's sizes and nothing afterwards, and total counts the entries stored (half of the ordered neighbour relations).
 struct NbrLists {
   int* count; int* low; long long* start;      // N + 1 entries each, allocated by the caller
   int* nbr; int* waitOn;                       // allocated here
   long long total, slotTotal;                  // list entries; entries of the slots (single-pass form)
   bool slots;                                  // the single-pass form was used: the lists lie in their slots, with gaps
+  bool lowOnly;                                // set by the caller
 };
 
 // Builds the lists behind the caller's cell grid.  On entry count[] holds every candidate's slot capacity, the population of the cells
 // its list is built from (single-pass form; unused otherwise).
-//   single pass: scan the slots, write the lists into them (launch(2): better-scored neighbours from the slot's front, the others from
-//                its back), sum the exact total on the way;
+//   single pass: scan the slots, write the lists into them (launch(2): better-scored neighbours from the slot's front, the others --
+//                unless lowOnly -- from its back), sum the exact total on the way;
 //   two passes:  count (launch(0)), scan, fill (launch(1)): every candidate test is done twice -- the form for inputs whose slots would
 //                exceed 32-bit indices or do not fit the workspace (the slots can be several times the exact list size).
 // launch(mode, lists) enqueues the caller's neighbour kernel; beforeLists() runs once, behind the last read-back in front of the
@@ -190,7 +193,7 @@ int build_neighbour_lists(sd::Arena& A, hipStream_t s, int N, bool singlePass, v
     if (!d_total) return -1;
     SD_CHECK(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), s));
     launch(2, L);
-    hipLaunchKernelGGL(k_sum_halves, dim3(sd::div_up(N, 256) < 1024 ? sd::div_up(N, 256) : 1024), dim3(256), 0, s, L.low, L.count, N, d_total);
+    hipLaunchKernelGGL(k_sum_halves, dim3(sd::div_up(N, 256) < 1024 ? sd::div_up(N, 256) : 1024), dim3(256), 0, s, L.low, L.lowOnly ? (const int*)nullptr : L.count, N, d_total);
     SD_LAUNCH_CHECK();
     unsigned long long tot = 0;
     SD_CHECK(hipMemcpyAsync(&tot, d_total, sizeof(tot), hipMemcpyDeviceToHost, s));

@@ -34,6 +34,7 @@ SIGNATURES = {
     "sd_get_option": (_i, [ctypes.c_char_p]),
     "sd_nms2d_host": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "sd_nms2d_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "sd_nms2d_build_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sd_nms2d_old_host": (_i, [_vp, _i, _i, _vp, _i, _i, _f, _i, _i, _i, _i, _vp]),
     "sd_nms2d_old_device": (_i, [_vp, _i, _i, _vp, _i, _i, _f, _i, _i, _i, _i, _vp, _vp]),
     "sd_clip_pairs_device": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

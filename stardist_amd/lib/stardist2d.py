@@ -172,6 +172,22 @@ def clip_pairs(xa, ya, xb, yb):
     return out.cpu().numpy(), fl.cpu().numpy()
 
 
+def nms2d_build(dist, points):
+    """Probe (tests) of the 2D NMS's build step: dist (n, R) f32, points (n, 2) f32 numpy -> (vx, vy (n, R) int32, bbox (n, 4) int32
+    [xmin, xmax, ymin, ymax], radius, area (n,) f32, gstats (5,) int32) as sd_nms2d_device computes them."""
+    import torch
+    N.require_device()
+    dev = torch.device("cuda")
+    d = torch.from_numpy(np.ascontiguousarray(dist, np.float32)).to(dev); p = torch.from_numpy(np.ascontiguousarray(points, np.float32)).to(dev)
+    n, R = d.shape
+    vx = torch.zeros((n, R), dtype=torch.int32, device=dev); vy = torch.zeros((n, R), dtype=torch.int32, device=dev)
+    bbox = torch.zeros((n, 4), dtype=torch.int32, device=dev); gstats = torch.zeros(5, dtype=torch.int32, device=dev)
+    radius = torch.zeros(n, dtype=torch.float32, device=dev); area = torch.zeros(n, dtype=torch.float32, device=dev)
+    N.dcall(d, "sd_nms2d_build_device", N.tptr(d), N.tptr(p), n, R, N.tptr(vx), N.tptr(vy), N.tptr(bbox), N.tptr(radius), N.tptr(area), N.tptr(gstats))
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in (vx, vy, bbox, radius, area, gstats))
+
+
 def area_bounds_pairs(xa, ya, xb, yb):
     """Pair-level probe (tests) of the 2D NMS's decision shortcut (csrc/area_bounds.h): (exact intersection area float32, half-width of the
     band enclosing Clipper's area, usable bool, number of boundary crossings, number of near edge pairs) per pair.  xa..yb int32 (n_pairs, n_verts <= 32)."""

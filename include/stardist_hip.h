@@ -619,6 +619,20 @@ int sd_percentiles_device(const void* d_x, int dtype, long long n, int n_seg, co
 int sd_normalize_mi_ma_device(const void* d_x, int dtype, long long n, int n_seg, const float* d_mi, const float* d_ma, float eps, int clip,
                               float* d_out, void* stream);
 
+/* ---- linear resampling of an image (scipy.ndimage.zoom(x, zoom, order=1); csrc/zoom.hip, csrc/zoom_linear.h) ------------------
+ * d_src: a contiguous array of shape h_in_shape[0 .. rank - 1], d_dst: one of shape h_out_shape (both shapes on the host, every extent
+ * >= 1, 1 <= rank <= 4), of the same element type.  dtype: 0 = uint8, 1 = uint16, 2 = float32.  d_i0 / d_w0 / d_w1: the per-axis tables
+ * on the device, axis after axis, h_out_shape[d] entries each: for output index k of the axis, i0 = the first source index (floor of the
+ * source coordinate k * (n - 1) / (m - 1); -1 = the coordinate lies past the array, the output is 0) and the float64 weights of the
+ * samples i0 and i0 + 1 (where i0 + 1 is the extent, the mirrored index is read instead, as scipy does; its weight is 0).  An i0 beyond
+ * the source extent is clamped, so no table can make the kernel read outside d_src.  Float64 sum over the 2^rank samples in scipy's
+ * order, each product and sum rounded on its own; float32 is rounded once at the end, integers are rounded half up and saturated.  With
+ * the tables of stardist_amd.utils.zoom_linear the result equals scipy's bit for bit, non-finite pixels included (a NaN is a NaN: its
+ * sign and payload are not defined).  One thread per output element, 64-bit offsets; nothing is copied to the host and the stream is
+ * not synchronised.  d_dst must not be d_src. */
+int sd_zoom_linear_device(const void* d_src, void* d_dst, int dtype, int rank, const int* h_in_shape, const int* h_out_shape,
+                          const int32_t* d_i0, const double* d_w0, const double* d_w1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,7 @@ SIGNATURES = {
     "sd_class_loss_device": (_i, [_vp, _vp, _vp, ctypes.c_longlong, _i, ctypes.c_double, _vp, _vp, _vp]),
     "sd_percentiles_device": (_i, [_vp, _i, ctypes.c_longlong, _i, _vp, _i, _i, _vp, _vp]),
     "sd_normalize_mi_ma_device": (_i, [_vp, _i, ctypes.c_longlong, _i, _vp, _vp, _f, _i, _vp, _vp]),
+    "sd_zoom_linear_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "_LIB_non_maximum_suppression_2d": (None, [_vp, _vp, _i, _i, _f, _i, _i, _i, _vp]),
     "_LIB_polygon_to_label": (None, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "_LIB_star_dist": (None, [_vp, _i, _i, _i, _i, _i, _vp]),

@@ -21,7 +21,7 @@ import numpy as np
 
 from ..lib import _native as N
 from ..nms import _ind_prob_thresh
-from ..utils import to_device
+from ..utils import to_device, zoom_linear
 
 
 def axes_check_and_normalize(axes, length=None):
@@ -912,8 +912,12 @@ class StarDistBase(object):
             for s, a in zip(scale, _axes):
                 if not s > 0: raise ValueError("scale values must be greater than 0")
             scale = tuple(s if a in "XYZ" else 1 for s, a in zip(scale, _axes))
-            from scipy import ndimage as ndi
-            img = ndi.zoom(np.asarray(img.cpu() if N.is_torch(img) else img), scale, order=1)     # base.py:725-735
+            if self.device.type == "cuda" and self._zoom_on_device(img):
+                # the raw image goes up (or stays up) and is resampled there: scipy's values bit for bit (csrc/zoom.hip), no host pass
+                img = zoom_linear((img if N.is_torch(img) else to_device(img, self.device)).to(self.device), scale)
+            else:
+                from scipy import ndimage as ndi
+                img = ndi.zoom(np.asarray(img.cpu() if N.is_torch(img) else img), scale, order=1)     # base.py:725-735
         yield "predict"
         res = None
         if sparse:
@@ -949,6 +953,13 @@ class StarDistBase(object):
         else:
             yield res_instances
 
+    @staticmethod
+    def _zoom_on_device(img):
+        """whether stardist_amd.utils.zoom_linear has a kernel for this image: a uint8 / uint16 / float32 array or tensor of rank <= 4"""
+        if N.is_torch(img):
+            return str(img.dtype) in ("torch.uint8", "torch.uint16", "torch.float32") and 1 <= img.dim() <= 4
+        return isinstance(img, np.ndarray) and img.dtype in (np.uint8, np.uint16, np.float32) and 1 <= img.ndim <= 4
+
     def predict_instances_big(self, img, axes, block_size, min_overlap, context=None, labels_out=None, labels_out_dtype=np.int32,
                               show_progress=True, **kwargs):
         """Predict instances of very large inputs block by block (base.py:838-983).  When torch.distributed is
@@ -968,15 +979,15 @@ class StarDistBase(object):
         overlapped with the step on image k (the reference reads block k + 1 while it works on block k only in its big-image loop,
         stardist/big.py:312-326; a plain loop over predict_instances pays the host -> device copy of every input in front of its step).
         A helper thread copies the next array into page-locked memory (numpy copy: releases the GIL) and enqueues the device copy on
-        its own stream; the step waits for that copy's event only.  Images that need host-side preparation (`scale`, a `normalizer`
-        without `before_device`) and device tensors are passed through unchanged; a normaliser of stardist_amd.utils works on the
-        uploaded raw image.  Results are those of predict_instances(img, **kwargs), image by image."""
+        its own stream; the step waits for that copy's event only.  Images that need host-side preparation (a `normalizer` without
+        `before_device`) and device tensors are passed through unchanged; a normaliser of stardist_amd.utils works on the uploaded raw
+        image, and so does `scale` (the image is resampled on the device).  Results are those of predict_instances(img, **kwargs),
+        image by image."""
         import queue
         import threading
         import torch
         nrm = kwargs.get("normalizer")
-        if self.device.type != "cuda" or (nrm is not None and not callable(getattr(nrm, "before_device", None))) \
-                or kwargs.get("scale") is not None:
+        if self.device.type != "cuda" or (nrm is not None and not callable(getattr(nrm, "before_device", None))):
             for img in imgs:
                 yield self.predict_instances(img, **kwargs)
             return
@@ -1000,7 +1011,8 @@ class StarDistBase(object):
                 for img in imgs:
                     if stop.is_set():
                         return
-                    if N.is_torch(img) or not isinstance(img, np.ndarray) or img.dtype == object:
+                    if N.is_torch(img) or not isinstance(img, np.ndarray) or img.dtype == object \
+                            or (kwargs.get("scale") is not None and not self._zoom_on_device(img)):   # scipy resamples it: stays a host array
                         if not put((img, None)):
                             return
                         continue

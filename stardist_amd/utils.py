@@ -34,7 +34,7 @@ def _is_device_tensor(x):
     return type(x).__module__.startswith("torch") and hasattr(x, "is_cuda") and x.is_cuda
 
 
-# element type codes of sd_percentiles_device / sd_normalize_mi_ma_device
+# element type codes of sd_percentiles_device / sd_normalize_mi_ma_device / sd_zoom_linear_device
 _DEVICE_DTYPE_CODE = {"torch.uint8": 0, "torch.uint16": 1, "torch.float32": 2}
 _NUMPY_2 = int(np.__version__.split(".")[0]) >= 2
 
@@ -178,6 +178,94 @@ def normalize(x, pmin=3, pmax=99.8, axis=None, clip=False, eps=1e-20, dtype=np.f
     mi = np.percentile(x, pmin, axis=axis, keepdims=True)
     ma = np.percentile(x, pmax, axis=axis, keepdims=True)
     return normalize_mi_ma(x, mi, ma, clip=clip, eps=eps, dtype=dtype)
+
+
+# ----------------------------------------------------------------------------- linear resampling (predict_instances(scale=))
+_ZOOM_MAX_RANK = 4
+_zoom_device_tables = {}
+
+
+def _zoom_axis_table(n, m):
+    """(i0 int32, w0 float64, w1 float64), one entry per output index, of scipy.ndimage.zoom(order=1) along an axis that goes from n to
+    m samples (csrc/zoom_linear.h reads them): the source coordinate cc = float64(k) * ((n - 1) / (m - 1)) (ratio 1 for m = 1), i0 =
+    floor(cc), w0 = 1 - (cc - i0), w1 = 1 - w0.  Where the product rounds past n - 1 (it can, for the last k) scipy takes the
+    coordinate for outside the array and writes 0: i0 = -1 says so."""
+    ratio = np.float64(n - 1) / np.float64(m - 1) if m > 1 else np.float64(1.0)
+    cc = np.arange(m, dtype=np.float64) * ratio
+    lo = np.floor(cc)
+    w0 = 1.0 - (cc - lo)
+    w1 = 1.0 - w0
+    i0 = lo.astype(np.int32)
+    i0[cc > n - 1] = -1
+    return i0, w0, w1
+
+
+def _zoom_out_shape(shape, zoom):
+    """the output shape scipy.ndimage.zoom gives an array of this shape, or None where the device kernel does not apply (a zoom that is no
+    plain number per axis, an empty output, a rank beyond 4): scipy then decides, and raises its own errors"""
+    plain = (int, float, np.float64, np.integer)
+    if isinstance(zoom, plain) and not isinstance(zoom, (bool, np.bool_)):
+        zoom = (zoom,) * len(shape)
+    try:
+        zoom = tuple(zoom)
+    except TypeError:
+        return None
+    if not 1 <= len(shape) <= _ZOOM_MAX_RANK or len(zoom) != len(shape):
+        return None
+    if not all(isinstance(z, plain) and not isinstance(z, (bool, np.bool_)) for z in zoom):
+        return None
+    try:
+        out = tuple(int(round(n * z)) for n, z in zip(shape, zoom))         # scipy's expression; Python's round: halves go to even
+    except (ValueError, OverflowError):
+        return None
+    if min(shape) < 1 or min(out) < 1 or max(out) >= 2 ** 31:
+        return None
+    return out
+
+
+def _zoom_tables_on(device, in_shape, out_shape):
+    """the tables of every axis, concatenated, as three device tensors; built and uploaded once per (shapes, device)"""
+    import torch
+    key = (tuple(in_shape), tuple(out_shape), str(device))
+    t = _zoom_device_tables.get(key)
+    if t is None:
+        per_axis = [_zoom_axis_table(n, m) for n, m in zip(in_shape, out_shape)]
+        t = tuple(torch.as_tensor(np.concatenate([a[j] for a in per_axis]), device=device) for j in range(3))
+        while len(_zoom_device_tables) >= 32:
+            _zoom_device_tables.pop(next(iter(_zoom_device_tables)))
+        _zoom_device_tables[key] = t
+    return t
+
+
+def _scipy_zoom_linear(x, zoom):
+    from scipy import ndimage
+    return ndimage.zoom(x, zoom, order=1)
+
+
+def zoom_linear(x, zoom):
+    """scipy.ndimage.zoom(x, zoom, order=1): the resampling behind predict_instances(scale=).  numpy in -> numpy out, scipy's own call.
+    A uint8 / uint16 / float32 tensor of rank <= 4 on a HIP device in -> a tensor of the same type on that device out, equal to scipy's
+    result bit for bit (csrc/zoom.hip: float64 sum in scipy's order, per-axis tables from the host), asynchronously and with no copy to
+    the host; a non-contiguous tensor is made contiguous first.  Non-finite pixels spread as in scipy: a NaN or an infinity makes every
+    output element NaN that reads it with weight 0 -- along an axis of factor 1 too, and at the far edge through the mirrored sample
+    scipy reads there -- only the sign and payload of such a NaN are not scipy's.  Any other tensor (dtype, rank, a host tensor), a zoom
+    that is not one plain number per axis and an empty output go through scipy, which raises its own errors."""
+    if not type(x).__module__.startswith("torch"):
+        return _scipy_zoom_linear(x, zoom)
+    out_shape = _zoom_out_shape(tuple(x.shape), zoom) if (x.is_cuda and str(x.dtype) in _DEVICE_DTYPE_CODE) else None
+    if out_shape is None:
+        return _via_host(_scipy_zoom_linear, x, zoom)
+    import ctypes
+    import torch
+    from .lib import _native as N
+    x = x.contiguous()
+    i0, w0, w1 = _zoom_tables_on(x.device, x.shape, out_shape)
+    out = torch.empty(out_shape, dtype=x.dtype, device=x.device)
+    shapes = (ctypes.c_int * len(out_shape))(*x.shape), (ctypes.c_int * len(out_shape))(*out_shape)
+    N.dcall(x, "sd_zoom_linear_device", ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), _DEVICE_DTYPE_CODE[str(x.dtype)],
+            len(out_shape), ctypes.cast(shapes[0], ctypes.c_void_p), ctypes.cast(shapes[1], ctypes.c_void_p),
+            ctypes.c_void_p(i0.data_ptr()), ctypes.c_void_p(w0.data_ptr()), ctypes.c_void_p(w1.data_ptr()))
+    return out
 
 
 # ----------------------------------------------------------------------------- normalisers for predict(..., normalizer=)

@@ -13,7 +13,7 @@
 //
 // render_mode 0 ("full") in the reference is   kernel OR (hull AND union-of-tetrahedra)
 // (:1474-1477) where `hull` are Qhull's convex-hull half-spaces of the same vertices; render_mode 2
-// ("hull") paints the hull itself.  The hulls come from the gift-wrapping kernel of the 3D NMS (nms3d.hip
+// ("hull") paints the hull itself.  The hulls come from the gift-wrapping kernel of the 3D NMS (nms3d_hull.h
 // k_hull, fp64, facets verified against every vertex), not from Qhull: same facets, planes not normalised
 // (the sign test is scale invariant), so a voxel can differ only if it lies within rounding distance
 // (~1e-12 voxel) of a hull facet -- see DESIGN.md ("3D rasteriser: hull test").  A polyhedron whose hull
@@ -21,15 +21,10 @@
 // and fails loudly in mode 2.
 #include "common.h"
 #include "geom3d.h"
+#include "nms3d_shared.h"
 #include "../../include/stardist_hip.h"
 #include <limits.h>
 #include <vector>
-
-namespace sd {
-int hull_planes(const float* d_dist, const float* d_points, const float* d_verts, int n, int R, double** planes, int** count, int* cap_out,
-                hipStream_t s);
-int cone_map(const float* d_verts, const int* d_faces, int F, sd3::ConeMap* out, hipStream_t s);
-}
 
 namespace {
 
@@ -177,12 +172,12 @@ extern "C" int sd_polyhedron_to_label_window_device(const float* d_dist, const f
   const long long nvox = (long long)nz * ny * nx;
   sd::Arena& A = sd::arena();
   if (A.begin(s)) return -1;
-  double* hullPlanes = nullptr; int* hullCount = nullptr; int hullCap = 0;
+  sd::HullPlanes hull{nullptr, nullptr, nullptr, 0};
   int* hullFail = A.take_n<int>(1);
   if (!hullFail) return -1;
   SD_CHECK(hipMemsetAsync(hullFail, 0, sizeof(int), s));
   if (need_hull && n_rays >= 4) {
-    if (sd::hull_planes(d_dist, d_points, d_verts, n_polys, n_rays, &hullPlanes, &hullCount, &hullCap, s)) return -1;
+    if (sd::hull_planes(d_dist, d_points, d_verts, n_polys, n_rays, &hull, s)) return -1;
   } else if (render_mode == 2) { sd::set_error("sd_polyhedron_to_label: render_mode 'hull' needs n_rays >= 4"); return -1; }
   sd3::ConeMap cmap{nullptr, nullptr};
   if (render_mode == 0 && sd::cone_map(d_verts, d_faces, n_faces, &cmap, s)) return -1;
@@ -200,7 +195,7 @@ extern "C" int sd_polyhedron_to_label_window_device(const float* d_dist, const f
     SD_CHECK(hipMemsetAsync(count, 0, nvox * sizeof(int), s));
     const int blocks = n_polys < 8192 ? n_polys : 8192;
     hipLaunchKernelGGL(k_paint3d, dim3(blocks), dim3(256), lds, s, d_dist, d_points, d_verts, d_faces, 0, n_polys, n_rays, n_faces,
-                       NZ, NY, NX, z0, y0, x0, nz, ny, nx, render_mode, first, count, d_result, hullPlanes, hullCount, hullCapL, hullFail, cmap);
+                       NZ, NY, NX, z0, y0, x0, nz, ny, nx, render_mode, first, count, d_result, hull.planes, hull.count, hullCapL, hullFail, cmap);
     SD_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_resolve3d, dim3(gb), dim3(256), 0, s, d_result, first, count, nvox, d_labels, use_overlap_label, overlap_label);
     SD_LAUNCH_CHECK();
@@ -210,7 +205,7 @@ extern "C" int sd_polyhedron_to_label_window_device(const float* d_dist, const f
       hipLaunchKernelGGL(k_fill, dim3(gb), dim3(256), 0, s, first, nvox, INT_MAX);
       SD_CHECK(hipMemsetAsync(count, 0, nvox * sizeof(int), s));
       hipLaunchKernelGGL(k_paint3d, dim3(1), dim3(256), lds, s, d_dist, d_points, d_verts, d_faces, p, p + 1, n_rays, n_faces, NZ, NY, NX,
-                         z0, y0, x0, nz, ny, nx, render_mode, first, count, d_result, hullPlanes, hullCount, hullCapL, hullFail, cmap);
+                         z0, y0, x0, nz, ny, nx, render_mode, first, count, d_result, hull.planes, hull.count, hullCapL, hullFail, cmap);
       hipLaunchKernelGGL(k_resolve3d_seq, dim3(gb), dim3(256), 0, s, d_result, first, count, nvox, h_labels[p], use_overlap_label, overlap_label);
       SD_LAUNCH_CHECK();
     }

@@ -1,4 +1,4 @@
-"""CPU: the inscribed / circumscribed polytope bounds used by the 3D NMS (nms3d.hip::hiv_bounds_wave) are rigorous.
+"""CPU: the inscribed / circumscribed polytope bounds used by the 3D NMS (nms3d_hiv.h::hiv_bounds_wave) are rigorous.
 numpy restatement of the bound construction, checked against exact half-space-intersection volumes from scipy's Qhull
 (independent of the product code and of the oracle build)."""
 import numpy as np

@@ -510,3 +510,67 @@ def test_nms3d_cone_map_does_not_change_survivors(refmods, monkeypatch, n_rays, 
     assert np.array_equal(keep_map.cpu().numpy(), keep_full.cpu().numpy()) and np.array_equal(keep_full.cpu().numpy(), ref_keep)
     assert st_map[3] > 0, "no pair reached the render stage: %s" % st_map.tolist()
     assert np.array_equal(st_map[[0, 1, 2, 3, 6, 7]], st_full[[0, 1, 2, 3, 6, 7]])
+
+
+@pytest.mark.parametrize("n_rays", [172, 228, 256, 300])
+def test_nms3d_many_rays_survivors(refmods, n_rays):
+    """ray counts at which the LDS layouts of the volume stages (csrc/nms3d_lds.h) take another branch: 172 and 228 rays are the first at
+    which the direction mesh refined twice / once no longer fits its workspace, from 252 rays on the stages need the opt-in for more
+    than 64 KiB of dynamic LDS, at 300 the four-wave exact pass no longer fits.  Survivors equal the compiled reference's; where the
+    four-wave pass fits, every nms3d_split_exact / nms3d_bounds_lean form gives the same keep flags"""
+    import torch
+    from stardist_amd.lib import _native as N, stardist3d as sd3
+    rays = _rays(n_rays)
+    V, F = rays.vertices, rays.faces.astype(np.int32)
+    d, p, s = _random_candidates((14, 20, 24), n_rays, 0.3, seed=n_rays, prob_thresh=0.96, radius=6)
+    assert 100 < len(d) < 200
+    refmods.stardist3d(); refmods.set_threads(1)
+    ref_keep = refmods.stardist3d().c_non_max_suppression_inds(d, p, V, F, s, 1, 1, 0, np.float32(0.3))
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+    args = (t(d), t(p), t(np.float32(V)), t(F), t(s), 1, 1, 0, np.float32(0.3))
+    keep, stats = sd3.c_non_max_suppression_inds(*args, return_stats=True)
+    keep = keep.cpu().numpy()
+    diff = np.flatnonzero(keep != ref_keep)
+    assert len(diff) == 0, "survivor mismatch at %s of %d (stats %s)" % (diff[:10], len(d), stats.tolist())
+    assert 0 < keep.sum() < len(d) and stats[2] > 100 and stats[11] > 100, stats.tolist()      # the kernel and hull stages ran
+    if n_rays <= 256:
+        for split in (0, 1, 2):
+            for lean in (0, 1):
+                with N.option("nms3d_split_exact", split), N.option("nms3d_bounds_lean", lean):
+                    k = sd3.c_non_max_suppression_inds(*args).cpu().numpy()
+                assert np.array_equal(k, keep), (split, lean)
+
+
+@pytest.mark.parametrize("n_rays", [256, 300])
+def test_pair_volumes_match_qhull_many_rays(refmods, n_rays):
+    """test_pair_volumes_match_qhull on a few hundred pairs at ray counts beyond 64 KiB of LDS per workgroup (256: the four-wave exact
+    pass fits and must give the one-wave routine's volumes bit for bit; 300: it does not fit, only the one-wave routine runs)"""
+    from stardist_amd.lib import _native as N, stardist3d as sd3
+    rays = _rays(n_rays)
+    V, F = rays.vertices, rays.faces.astype(np.int32)
+    rng = np.random.RandomState(n_rays)
+    n = 400
+    d = (8.0 * (1 + 0.3 * rng.uniform(-1, 1, (n, n_rays)))).astype(np.float32)
+    p = rng.uniform(20, 44, (n, 3)).astype(np.float32)
+    i = rng.randint(0, n, 1200); j = rng.randint(0, n, 1200)
+    sep = np.sqrt(((p[i] - p[j]) ** 2).sum(1))
+    sel = np.flatnonzero((i != j) & (sep < 14))[:300]
+    pairs = np.stack([i[sel], j[sel]], 1).astype(np.int32)
+    assert len(pairs) >= 250
+    rk, rh = refmods.pair_volumes(d, p, V, F, pairs)
+    gk, gh = sd3.hiv_pair_volumes(d, p, V, F, pairs)
+    assert np.array_equal(rk == 0, gk.astype(np.float32) == 0), np.flatnonzero((rk == 0) != (gk.astype(np.float32) == 0))[:10]
+    nz = rk != 0
+    relk = np.abs(gk[nz] - rk[nz]) / np.maximum(np.abs(rk[nz]), 1e-3)
+    bigh = rh > 1e9
+    assert np.array_equal(bigh, gh > 1e9), np.flatnonzero(bigh != (gh > 1e9))[:10]
+    relh = np.abs(gh[~bigh] - rh[~bigh]) / np.maximum(np.abs(rh[~bigh]), 1e-3)
+    print("kernel volumes: %d non-zero, max rel diff %.3g; hull volumes: %d finite, max rel diff %.3g" % (nz.sum(), relk.max() if nz.any() else 0, (~bigh).sum(), relh.max()))
+    assert nz.sum() > 10 and (~bigh).sum() > 100                                # neither comparison is vacuous
+    assert (relk.max() if nz.any() else 0) < 2e-6 and relh.max() < 2e-6         # the reference returns float32
+    if n_rays == 256:
+        vols = {}
+        for split in (0, 2):
+            with N.option("nms3d_split_exact", split):
+                vols[split] = [np.asarray(v) for v in sd3.hiv_pair_volumes(d, p, np.float32(V), F, pairs)]
+        assert np.array_equal(vols[2][0], vols[0][0]) and np.array_equal(vols[2][1], vols[0][1])

@@ -131,6 +131,10 @@ int sd_clip_pairs_device(const int32_t* d_xa, const int32_t* d_ya, const int32_t
  * closer than one lattice step. */
 int sd_area_bounds_pairs_device(const int32_t* d_xa, const int32_t* d_ya, const int32_t* d_xb, const int32_t* d_yb, int n_pairs,
                                 int n_verts, float* d_out_area, float* d_out_band, int32_t* d_out_info, void* stream);
+/* The largest grid (blocks of four waves, two pairs per wave and trip) sd_area_bounds_pairs_device launches on the current device:
+ * the number of blocks resident at once by the occupancy query; -1 when the query fails.  Tests size inputs with it so that a wave
+ * takes several trips. */
+int sd_area_bounds_pairs_grid(void);
 
 /* Test probe of the 2D NMS's per-polygon pass for n_verts <= 32 (stardist_amd/csrc/poly_pass.h), exactly as the NMS launches it:
  * d_props (n_polys) records of 32 bytes (area_bounds.h PolyProps; n_verts 3..32) and / or d_prep (n_polys) PolyPrep<32> records, each

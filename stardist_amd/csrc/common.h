@@ -49,6 +49,13 @@ Arena& arena();
 // stream for a while (fork / join by events).  nullptr + error set when there is no current device or the stream cannot be created.
 hipStream_t side_stream();
 
+// The grid at which every block of `kernel` (block size `threads`, no dynamic LDS) is resident at once on the current device: the
+// occupancy query's blocks per CU x the device's CU count.  Asked once per device and kept in the caller's `cache[kMaxDevices]`
+// (zero-initialised, one per kernel); 0 + error set when the query fails.  For grid-stride kernels whose blocks do equal work: a larger grid's
+// second batch of blocks runs on a partly empty device.
+enum { kMaxDevices = 64 };
+int resident_grid(const void* kernel, int threads, int* cache);
+
 static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // Result-preserving switches between equivalent formulations (set through sd_set_option of the C ABI, documented there): the parity

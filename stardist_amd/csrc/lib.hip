@@ -26,7 +26,6 @@ int tuning_env(const char* name, int dflt) { const char* e = getenv(name); retur
 
 // one workspace arena per HIP device: a call carves its slices from the arena of the device that is current when it runs
 // (the Python wrappers make the tensors' device current, stardist_amd/lib/_native.py dcall)
-enum { kMaxDevices = 64 };
 static Arena g_arena[kMaxDevices];
 Arena& arena() {
   int d = 0;
@@ -42,6 +41,23 @@ hipStream_t side_stream() {
   std::lock_guard<std::mutex> lock(mu);
   if (!st[d] && hipStreamCreateWithFlags(&st[d], hipStreamNonBlocking) != hipSuccess) { st[d] = nullptr; set_error("side_stream: cannot create a stream"); }
   return st[d];
+}
+
+int resident_grid(const void* kernel, int threads, int* cache) {
+  static std::mutex mu;
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) { set_error("resident_grid: no current device"); return 0; }
+  std::lock_guard<std::mutex> lock(mu);
+  if (!cache[d]) {
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || per_cu <= 0 || cus <= 0) {
+      set_error("resident_grid: occupancy query failed");
+      return 0;
+    }
+    cache[d] = per_cu * cus;
+  }
+  return cache[d];
 }
 
 size_t Arena::capacity() const { size_t t = 0; for (int i = 0; i < n_; ++i) t += cap_[i]; return t; }

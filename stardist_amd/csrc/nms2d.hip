@@ -517,18 +517,18 @@ __global__ void __launch_bounds__(256) k_pairs_decide(const int2* __restrict__ p
                                                       const sdarea::PolyProps* __restrict__ props, const float* __restrict__ area, float thr,
                                                       unsigned char* __restrict__ state, unsigned char* __restrict__ supp,
                                                       unsigned char* __restrict__ decided, unsigned int* __restrict__ nDecided) {
-  __shared__ float2 sq[4][2][32];
+  __shared__ float4 rec[4][2][sdarea::REC_FLOAT4];
   const int lane = threadIdx.x & 63, half = lane >> 5, l = lane & 31, wv = threadIdx.x >> 6;
   const unsigned long long n = *nPtr, first = firstPtr ? (unsigned long long)*firstPtr : 0ull;
-  const unsigned long long nw = (unsigned long long)gridDim.x * 4;
+  const unsigned long long step = 2ull * gridDim.x * 4;
   unsigned int mine = 0;
-  for (unsigned long long base = first + 2ull * ((unsigned long long)blockIdx.x * 4 + wv); base < n; base += 2ull * nw) {
+  for (unsigned long long base = first + 2ull * ((unsigned long long)blockIdx.x * 4 + wv); base < n; base += step) {
     const unsigned long long t = base + half;
     const bool active = t < n;
     const int2 ij = active ? pairs[t] : make_int2(0, 0);
-    const sdarea::PolyProps pp = props[ij.x], pq = props[ij.y];
-    const sdarea::Enclosure E = sdarea::pair_enclosure(vx + (size_t)ij.x * R, vy + (size_t)ij.x * R, vx + (size_t)ij.y * R, vy + (size_t)ij.y * R, R, pp, pq,
-                                                       active, sq[wv][half], l, half);             // clip = i, subject = j (:157-158)
+    const sdarea::PairOperands o = sdarea::load_operands(vx + (size_t)ij.x * R, vy + (size_t)ij.x * R, vx + (size_t)ij.y * R, vy + (size_t)ij.y * R,
+                                                         props + ij.x, props + ij.y, active && l < R, l);   // clip = i, subject = j (:157-158)
+    const sdarea::Enclosure E = sdarea::pair_enclosure(o, R, active, rec[wv][half], l, half);
     if (active && l == 0) {
       const int dec = sdarea::decide(E, area[ij.x], area[ij.y], thr);
       decided[t] = (unsigned char)dec;
@@ -1128,6 +1128,9 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
   if (!U0 || !U1 || !K || !pairs || !spillPairs || !exactPairs || !Sl || !d_cnt || !bucketHist || !nOrdered || (pairSort && R <= 32 && !pairOrder)) return -1;
   unsigned char* decided = (areaBounds && pairOrder) ? A.take_n<unsigned char>(pairCap) : nullptr;       // (the shortcut filters through the ordered index list)
   if (areaBounds && pairOrder && !decided) return -1;
+  static int decideGridOf[sd::kMaxDevices] = {};
+  const int decideGrid = decided ? sd::resident_grid((const void*)k_pairs_decide, 256, decideGridOf) : 0;   // every launched wave resident, equal work
+  if (decided && decideGrid <= 0) return -1;
   i64 totalDecided = 0, totalSkipped = 0;      // pairs decided by the area enclosure; pairs not swept because j was suppressed meanwhile
   int nU = N, rounds = 0;
   i64 totalPairs = 0, totalExact = 0, totalSpill = 0;
@@ -1187,7 +1190,7 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
         const PairKey key{(const char*)prep, prepStride, 1.f / (4.f * (max_dist + 1.f)), md[0], md[1], md[2]};   // offsets lie in (-2 max_dist, 2 max_dist)
         SD_CHECK(hipMemsetAsync(bucketHist, 0, PAIR_BUCKETS * sizeof(unsigned int), s));
         if (decided)
-          hipLaunchKernelGGL(k_pairs_decide, dim3(256 * 8), dim3(256), 0, s, pairs, &d_cnt->nPairs, first, vx, vy, R, props, area, threshold, state, suppOut,
+          hipLaunchKernelGGL(k_pairs_decide, dim3(decideGrid), dim3(256), 0, s, pairs, &d_cnt->nPairs, first, vx, vy, R, props, area, threshold, state, suppOut,
                              decided, &d_cnt->nDecided);
         if (!suppOut && deferFrom > 0 && rounds >= deferFrom)      // few undecided pairs: they wait for the tail batch's sweep launch
           hipLaunchKernelGGL(k_defer_undecided, dim3(256), dim3(256), 0, s, pairs, &d_cnt->nPairs, &d_cnt->nDecided, deferMax, decided, state, dfr, defKind, &d_cnt->nErr);

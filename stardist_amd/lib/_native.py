@@ -39,6 +39,7 @@ SIGNATURES = {
     "sd_nms2d_old_device": (_i, [_vp, _i, _i, _vp, _i, _i, _f, _i, _i, _i, _i, _vp, _vp]),
     "sd_clip_pairs_device": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "sd_area_bounds_pairs_device": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "sd_area_bounds_pairs_grid": (_i, []),
     "sd_prepare_polys_device": (_i, [_vp, _vp, _i, _i, _vp, ctypes.c_int64, _vp]),
     "sd_poly_pass_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "sd_star_dist2d_host": (_i, [_vp, _i, _i, _i, _i, _i, _vp]),

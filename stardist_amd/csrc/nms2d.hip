@@ -842,9 +842,12 @@ struct Counters { int nU, nK, nS, left; unsigned long long nPairs; unsigned int 
 template <int MAXV, int SPREP>
 struct BeamPath {
   typedef sdclip::PolyPrep<MAXV> Prep;
-  static int prepare(const int* vx, const int* vy, int N, int R, void* prep, hipStream_t s) {
-    if constexpr (MAXV == 32) {                     // n_rays <= 32: the per-polygon pass (poly_pass.h), prepared polygons only
-      if (sdpass::launch_poly_pass(vx, vy, N, R, nullptr, prep, s)) { sd::set_error("sd_nms2d: launch of the per-polygon pass failed"); return -1; }
+  static constexpr size_t prep_stride = sizeof(Prep);
+  static constexpr bool two_tiers = MAXV == 32;     // n_rays <= 32: tier 1 in front of tier 2
+  // props (n_rays <= 32 only; may be null): the polygon properties of the decision shortcut (area_bounds.h), written by the same pass
+  static int prepare(const int* vx, const int* vy, int N, int R, sdarea::PolyProps* props, void* prep, hipStream_t s) {
+    if constexpr (MAXV == 32) {                     // n_rays <= 32: the per-polygon pass (poly_pass.h)
+      if (sdpass::launch_poly_pass(vx, vy, N, R, props, prep, s)) { sd::set_error("sd_nms2d: launch of the per-polygon pass failed"); return -1; }
       return 0;
     } else {
       const size_t lds = sdclip::PrepWork<sdclip::LdsStorage<SPREP>, MAXV>::lds_bytes() + 64;
@@ -887,9 +890,54 @@ struct BeamPath {
     return 0;
   }
 };
-}  // namespace
+// The one place that maps a ray count to its vertex capacity: f(BeamPath<...>{}) -> int
+template <class F>
+int with_beam_path(int R, F&& f) {
+  if (R <= 32) return f(BeamPath<32, 64>{});
+  if (R <= 64) return f(BeamPath<64, 64>{});
+  if (R <= 128) return f(BeamPath<128, 32>{});
+  return f(BeamPath<256, 16>{});
+}
+size_t prep_stride(int R) { return (size_t)with_beam_path(R, [](auto bp) { return (int)decltype(bp)::prep_stride; }); }
+int prepare_polys(const int* vx, const int* vy, int N, int R, sdarea::PolyProps* props, void* prep, hipStream_t s) {
+  return with_beam_path(R, [&](auto bp) { return decltype(bp)::prepare(vx, vy, N, R, props, prep, s); });
+}
 
-namespace {
+// What one sweep of the pair kernels works on: the polygons, the pair list, the two queues behind the tiers and where the decisions go
+// (supp == nullptr: a suppressing pair marks state[j]; else supp[pair index] = 1)
+struct Sweep {
+  hipStream_t s; int R; const int *vx, *vy; const void* prep; const float* area; float thr;
+  const int2* pairs; unsigned int *spillPairs, *exactPairs, qCap; Counters* d_cnt; unsigned char *state, *supp;
+};
+int general_path(const Sweep& w) {
+  return sd::clip_full_pairs(w.pairs, w.exactPairs, &w.d_cnt->nExact, w.qCap, w.R, w.vx, w.vy, w.area, w.thr, w.state, w.supp, &w.d_cnt->nErr, w.s);
+}
+// The sweep sequence of both drivers over pairs[idx[*first .. *n)] (idx, first: may be null): tier 1 (n_rays <= 32 only; capacity spills
+// -> q1.spill) -> tier 2 (what it cannot hold -> the general-path queue) -> general(): the general path over that queue, or what the caller
+// does with it instead.  pairTimer stops behind the first tier that runs.
+template <class General>
+int sweep_tiers(const Sweep& w, const unsigned int* idx, const unsigned long long* n, const unsigned int* first, Timer& pairTimer, General general) {
+  const PairQueues q1{w.spillPairs, &w.d_cnt->nSpill, w.exactPairs, &w.d_cnt->nExact, w.qCap};
+  const PairQueues q2{w.exactPairs, &w.d_cnt->nExact, w.exactPairs, &w.d_cnt->nExact, w.qCap};   // what tier 2 cannot hold goes to the general path
+  const int rc = with_beam_path(w.R, [&](auto bp) -> int {
+    typedef decltype(bp) BP;
+    if constexpr (BP::two_tiers) {
+      if (BP::tier1(w.pairs, idx, n, first, w.prep, w.area, w.thr, w.state, w.supp, q1, w.s) || pairTimer.stop(w.s)) return -1;
+      return BP::tier2(w.pairs, w.spillPairs, &w.d_cnt->nSpill, (const unsigned int*)nullptr, w.prep, w.area, w.thr, w.state, w.supp, q2, w.s);
+    } else {
+      if (BP::tier2(w.pairs, idx, n, first, w.prep, w.area, w.thr, w.state, w.supp, q2, w.s)) return -1;
+      return pairTimer.stop(w.s);
+    }
+  });
+  return rc ? -1 : general();
+}
+// the host's look at the counters a sweep left; who: the driver's prefix in messages, listOverflow: the caller's own pair list overflowed
+int check_sweep(const char* who, const Counters& h, unsigned int qCap, bool listOverflow, const char* alsoCounted) {
+  if (listOverflow || h.nSpill > qCap || h.nExact > qCap) { sd::set_error("%s: pair queue overflow (internal error)", who); return -1; }
+  if (h.nErr) { sd::set_error("%s: %u pairs exceeded the general path's fixed capacities%s", who, h.nErr, alsoCounted); return -1; }
+  return 0;
+}
+
 // The build step of sd_nms2d_device and of its probe sd_nms2d_build_device: the table of ray directions (host libm: the device never
 // evaluates sinf / cosf; stardist2d.cpp:419,454-455) and the initial gstats in ONE block and one copy -- every copy or fill command in front
 // of the neighbour lists costs 3-6 us and a gap on the critical path -- then k_build32 (n_rays <= 32) or k_build.  *gstatsOut: 8 ints.
@@ -932,382 +980,318 @@ extern "C" int sd_nms2d_build_device(const float* d_dist, const float* d_points,
   return 0;
 }
 
-extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n_polys, int n_rays, int use_kdtree,
-                               int use_bbox, int verbose, float threshold, uint8_t* d_keep, int64_t* stats,
-                               void* stream_) {
-  hipStream_t s = (hipStream_t)stream_;
-  const int N = n_polys, R = n_rays;
-  if (stats) memset(stats, 0, 16 * sizeof(int64_t));
-  if (N <= 0) return 0;
-  if (R < 1 || R > 256) { sd::set_error("sd_nms2d: n_rays=%d unsupported (1..256)", R); return -1; }
-  if (verbose) {
-    printf("Non Maximum Suppression (2D) ++++ \n");
-    printf("NMS: n_polys    = %d \nNMS: n_rays     = %d  \nNMS: thresh     = %.3f \nNMS: use_bbox   = %d\nNMS: use_kdtree = %d\n",
-           N, R, threshold, use_bbox, use_kdtree);
-    printf("NMS: using HIP (gfx950), uniform-grid broad phase + scan-beam pair kernel\n");
-  }
-  sd::Arena& A = sd::arena();
-  if (A.begin(s)) return -1;
-  // HIP events on the caller's stream: per-kernel durations for the roofline report (bench.py)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (stats) { SD_CHECK(hipEventCreate(&ev0)); SD_CHECK(hipEventCreate(&ev1)); }
-  struct EvGuard { hipEvent_t a, b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evguard{ev0, ev1};
-  double ns_pairs = 0, ns_full = 0, ns_pre = 0;
-  long long n_pair_launches = 0;
+namespace {
+// the two events the helper stream records behind the per-polygon work; the caller's stream waits for them at different points
+struct SideEvents {
+  hipEvent_t props = nullptr, prep = nullptr;
+  ~SideEvents() { if (props) (void)hipEventDestroy(props); if (prep) (void)hipEventDestroy(prep); }
+  int init() { SD_CHECK(hipEventCreateWithFlags(&props, hipEventDisableTiming)); SD_CHECK(hipEventCreateWithFlags(&prep, hipEventDisableTiming)); return 0; }
+};
 
-  // all-pairs configuration with a negative threshold: every pair (0, j) passes the reference's
-  // filters and overlap >= 0 > thr, so polygon 0 suppresses everything else.
-  if (!use_kdtree && !use_bbox && threshold < 0) {
-    SD_CHECK(hipMemsetAsync(d_keep, 0, N, s));
-    SD_CHECK(hipMemsetAsync(d_keep, 1, 1, s));
-    SD_CHECK(hipStreamSynchronize(s));
+// One call of sd_nms2d_device: what its phases hand to each other.  Every phase returns 0 or -1 (error set).
+struct Nms2d {
+  // the call
+  hipStream_t s; const float *dist, *pts; int N, R, use_kdtree, use_bbox; float thr; bool wantStats; sd::Arena& A;
+  // plan: options and tuning knobs, the helper stream and its events, the times of the statistics (events on the caller's stream)
+  bool areaBounds = false, singlePass = false, ordered = false, decide = false, deferOn = false, trace = false;
+  int tailT = -1, deferFrom = 0, keyMode = 2; unsigned int deferMax = 0;
+  hipStream_t side = nullptr; sd::SideJoin sideJoin; SideEvents sideEv;
+  Timer broadTimer, pairTimer, fullTimer, replayTimer;
+  double ns_pairs = 0, ns_full = 0, ns_pre = 0; long long n_pair_launches = 0;
+  // build: per candidate the integer vertices and what k_build derives from them; gstats: max_dist bits, extent of the centres; the
+  // prepared polygons and the properties of the decision shortcut (written by fork_side)
+  int *vx = nullptr, *vy = nullptr, *candCell = nullptr, *gstats = nullptr; int4* bbox = nullptr; float *radius = nullptr, *area = nullptr;
+  unsigned char* state = nullptr; void* prep = nullptr; size_t prepStride = 0; sdarea::PolyProps* props = nullptr;
+  // build_grid: the cell table, the storage of the list builder, the work list of round 1 and the deferred pairs' per-candidate arrays
+  GridP g; NmsFlags f; float max_dist = 0, reach = 0;
+  int by_bbox = 0, *cellStart = nullptr, *nbrCount = nullptr, *nbrLow = nullptr, *Ucur = nullptr; i64* nbrStart = nullptr; CellRec* cellRec = nullptr;
+  void* scanTmp = nullptr; size_t scanBytes = 0; Deferred dfr{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  // build_lists; totalNbr: ordered neighbour relations (the lists hold each unordered pair once, at its worse-scored end)
+  NbrLists L{}; i64 totalNbr = 0;
+  // begin_rounds: pair list, queues, counters, deferral storage
+  unsigned long long pairCap = 0, *nOrdered = nullptr; int2* pairs = nullptr; unsigned char *decided = nullptr, *defKind = nullptr;
+  unsigned int qCap = 0, *spillPairs = nullptr, *exactPairs = nullptr, *pairOrder = nullptr, *bucketHist = nullptr, *firstNew = nullptr, *nNewExact = nullptr, *nJoinDef = nullptr;
+  int *Unext = nullptr, *K = nullptr, *Sl = nullptr, decideGrid = 0; Counters *d_cnt = nullptr, h;
+  // the rounds; nDeferred: general-path pairs deferred so far; nUndecDeferredUpper: upper bound of the kind-1 deferred pairs so far (those
+  // whose j was suppressed meanwhile are skipped); totalDecided: pairs decided by the area enclosure; totalSkipped: pairs not swept
+  // because j was suppressed meanwhile
+  int nU = 0, rounds = 0; bool forceTail = false;
+  i64 nDeferred = 0, nUndecDeferredUpper = 0, totalPairs = 0, totalExact = 0, totalSpill = 0, totalUndecDeferred = 0, totalDecided = 0, totalSkipped = 0;
+  // tail_batch (taken on first use)
+  unsigned char* supp = nullptr; unsigned int* segStart = nullptr; int* segCnt = nullptr;
+
+  Nms2d(hipStream_t s_, const float* dist_, const float* pts_, int N_, int R_, int use_kdtree_, int use_bbox_, float thr_, bool wantStats_)
+      : s(s_), dist(dist_), pts(pts_), N(N_), R(R_), use_kdtree(use_kdtree_), use_bbox(use_bbox_), thr(thr_), wantStats(wantStats_), A(sd::arena()) {}
+
+  // validation, options and tuning knobs (read once); begins the arena pass
+  int plan() {
+    if (R < 1 || R > 256) { sd::set_error("sd_nms2d: n_rays=%d unsupported (1..256)", R); return -1; }
+    if (A.begin(s)) return -1;
+    if (wantStats && (broadTimer.init() || pairTimer.init() || fullTimer.init())) return -1;
+    trace = wantStats && sd::option(sd::OPT_TRACE) != 0;
+    // polygon properties of the decision shortcut (area_bounds.h)
+    areaBounds = R <= 32 && R >= 3 && sd::option(sd::OPT_NMS2D_AREA_BOUNDS) != 0 && sd::option(sd::OPT_NMS2D_STRICT) == 0;
+    // Neighbour lists in ONE pass (option "nms2d_neighbours_single_pass", default 1): every candidate gets a slot as large as the population
+    // of the cells its list is built from (known from the cell table: no candidate test needed), the lists -- the better-scored neighbours
+    // only -- are written into the slots from their front and the exact total is counted on the way.  The two-pass form
+    // (count, scan, fill: every candidate test done twice, 1.2 + 0.8 ms at 2048^2) remains for inputs whose slots would exceed 32-bit indices or the workspace.
+    singlePass = sd::option(sd::OPT_NMS2D_NBR_SINGLE) != 0;
+    // pair order (see k_pair_bucket_*): SD_NMS_PAIR_SORT=0 keeps emission order
+    static const bool pairSort = sd::tuning_env("SD_NMS_PAIR_SORT", 1) != 0;
+    static const int pairKey = sd::tuning_env("SD_NMS_PAIR_KEY", 2);
+    ordered = pairSort && R <= 32;
+    keyMode = pairKey;
+    decide = areaBounds && ordered;             // (the shortcut filters through the ordered index list)
+    // tail batch threshold: undecided candidates at or below which the remaining rounds are replayed on the device
+    static const int tailDiv = sd::tuning_env("SD_NMS_TAIL_DIV", 6);
+    static const int tailMax = sd::tuning_env("SD_NMS_TAIL_MAX", 65536);
+    tailT = tailDiv > 0 ? ((N / tailDiv) < tailMax ? (N / tailDiv) : tailMax) : -1;
+    // deferral of the general path to the tail batch (only with a tail batch to run it in)
+    static const bool deferEnv = sd::tuning_env("SD_NMS_DEFER", 1) != 0;
+    deferOn = tailT >= 0 && deferEnv;
+    // deferral of the enclosure's undecided pairs (see k_defer_undecided): from round 2 on by default (option nms2d_defer_undecided)
+    deferFrom = (deferOn && decide) ? sd::option(sd::OPT_NMS2D_DEFER_UNDECIDED) : 0;
+    deferMax = (unsigned int)(sd::option(sd::OPT_NMS2D_DEFER_MAX) > 0 ? sd::option(sd::OPT_NMS2D_DEFER_MAX) : 0);
+    side = sd::side_stream();
+    if (!side || sideEv.init()) return -1;
     return 0;
   }
 
-  int* vx = A.take_n<int>((size_t)N * R);
-  int* vy = A.take_n<int>((size_t)N * R);
-  int4* bbox = A.take_n<int4>(N);
-  float* radius = A.take_n<float>(N);
-  float* area = A.take_n<float>(N);
-  unsigned char* state = A.take_n<unsigned char>(N);
-  int* candCell = A.take_n<int>(N);
-  int* gstats = nullptr;
-  if (!vx || !vy || !bbox || !radius || !area || !state || !candCell) return -1;
-  if (launch_build(A, s, d_dist, d_points, N, R, vx, vy, bbox, radius, area, &gstats, stats ? ev0 : nullptr)) return -1;
+  // per candidate: integer vertices, bounding box, radius, area; the extent of the centres (launch_build); starts the broad-phase time
+  int build() {
+    vx = A.take_n<int>((size_t)N * R);
+    vy = A.take_n<int>((size_t)N * R);
+    bbox = A.take_n<int4>(N);
+    radius = A.take_n<float>(N);
+    area = A.take_n<float>(N);
+    state = A.take_n<unsigned char>(N);
+    candCell = A.take_n<int>(N);
+    prepStride = prep_stride(R);
+    prep = A.take((size_t)N * prepStride);
+    if (areaBounds) props = (sdarea::PolyProps*)A.take((size_t)N * sizeof(sdarea::PolyProps));
+    if (!vx || !vy || !bbox || !radius || !area || !state || !candCell || !prep || (areaBounds && !props)) return -1;
+    return launch_build(A, s, dist, pts, N, R, vx, vy, bbox, radius, area, &gstats, broadTimer.a);
+  }
+
   // ---- prepared polygons (Clipper::AddPath once per candidate), on a second stream: they depend on the integer vertices only, the
-  // grid and the neighbour lists that follow on the caller's stream do not need them (0.84 ms of independent work at 2048^2)
-  size_t prepStride;
-  if (R <= 32) prepStride = sizeof(sdclip::PolyPrep<32>); else if (R <= 64) prepStride = sizeof(sdclip::PolyPrep<64>);
-  else if (R <= 128) prepStride = sizeof(sdclip::PolyPrep<128>); else prepStride = sizeof(sdclip::PolyPrep<256>);
-  void* prep = A.take((size_t)N * prepStride);
-  if (!prep) return -1;
-  hipStream_t side = sd::side_stream();
-  if (!side) return -1;
-  hipEvent_t evFork = nullptr, evJoin = nullptr;
-  SD_CHECK(hipEventCreateWithFlags(&evFork, hipEventDisableTiming));
-  SD_CHECK(hipEventCreateWithFlags(&evJoin, hipEventDisableTiming));
-  EvGuard evguardFJ{evFork, evJoin};
-  // polygon properties of the decision shortcut (area_bounds.h) first: they also depend on the integer vertices only, and the
-  // decision kernel of the first round needs them before any sweep needs a prepared polygon (evProps / evPrep)
-  const bool areaBounds = R <= 32 && R >= 3 && sd::option(sd::OPT_NMS2D_AREA_BOUNDS) != 0 && sd::option(sd::OPT_NMS2D_STRICT) == 0;
-  sdarea::PolyProps* props = nullptr;
-  hipEvent_t evProps = nullptr, evPrep = nullptr;
-  SD_CHECK(hipEventCreateWithFlags(&evProps, hipEventDisableTiming));
-  SD_CHECK(hipEventCreateWithFlags(&evPrep, hipEventDisableTiming));
-  EvGuard evguardP{evProps, evPrep};
-  if (areaBounds) {
-    props = (sdarea::PolyProps*)A.take((size_t)N * sizeof(sdarea::PolyProps));
-    if (!props) return -1;
-  }
-  // The helper stream's work is enqueued once the LAST read-back of the grid set-up is behind us (launch_side below): it fills every
-  // wave slot of the chip, and an 8-byte device -> host copy of the caller's stream issued while it runs waits for a slot until it drains
-  // (measured: 0.69 ms for that copy, the neighbour-list kernel started 0.7 ms late; profiles/r05_step_timeline_2d.txt).
+  // grid and the neighbour lists that follow on the caller's stream do not need them (0.84 ms of independent work at 2048^2).
+  // The polygon properties of the decision shortcut with them: they also depend on the integer vertices only, and the decision kernel of
+  // the first round needs them before any sweep needs a prepared polygon (sideEv.props / sideEv.prep).
+  // The helper stream's work is enqueued once the LAST read-back of the grid set-up is behind us (build_neighbour_lists calls this): it
+  // fills every wave slot of the chip, and an 8-byte device -> host copy of the caller's stream issued while it runs waits for a slot
+  // until it drains (measured: 0.69 ms for that copy, the neighbour-list kernel started 0.7 ms late; profiles/r05_step_timeline_2d.txt).
   // n_rays <= 32: ONE pass writes the properties and the prepared polygons (poly_pass.h); more rays: k_prepare alone (no shortcut).
-  auto launch_side = [&]() -> int {
-    SD_CHECK(hipEventRecord(evFork, s));
-    SD_CHECK(hipStreamWaitEvent(side, evFork, 0));
-    int rc;
-    if (R <= 32) rc = sdpass::launch_poly_pass(vx, vy, N, R, props, prep, side);
-    else if (R <= 64) rc = BeamPath<64, 64>::prepare(vx, vy, N, R, prep, side);
-    else if (R <= 128) rc = BeamPath<128, 32>::prepare(vx, vy, N, R, prep, side);
-    else rc = BeamPath<256, 16>::prepare(vx, vy, N, R, prep, side);
-    if (rc) { sd::set_error("sd_nms2d: launch of the per-polygon pass failed"); return -1; }
-    SD_CHECK(hipEventRecord(evProps, side));
-    SD_CHECK(hipEventRecord(evPrep, side));
-    SD_CHECK(hipEventRecord(evJoin, side));
+  int fork_side() {
+    if (sideJoin.begin(s, side) || prepare_polys(vx, vy, N, R, props, prep, side)) return -1;
+    SD_CHECK(hipEventRecord(sideEv.props, side));
+    SD_CHECK(hipEventRecord(sideEv.prep, side));
     return 0;
-  };
-  int gs[8];
-  SD_CHECK(hipMemcpyAsync(gs, gstats, sizeof(gs), hipMemcpyDeviceToHost, s));
-  SD_CHECK(hipStreamSynchronize(s));
-  float max_dist;
-  memcpy(&max_dist, &gs[0], 4);
-
-  // ---- uniform grid
-  GridP g;
-  // cells of HALF the reach (max_dist + 1): a candidate's window (cell_window: its bounding box grown by the reach) then spans at most
-  // (2 (max_dist + 1) + 2 (max_dist + 1)) / cs + 2 = 10 rows; a grid that would exceed 2^26 cells gets coarser cells (fewer rows still)
-  const float reach = (max_dist + 1.f) * 1.0001f + 1e-3f;
-  const int by_bbox = (threshold >= 0.f || use_bbox) ? 1 : 0;
-  float cs = 0.5f * reach;
-  if (!(cs >= 1.f)) cs = 1.f;
-  for (;;) {
-    g.ny = (int)(((double)gs[2] - gs[1]) / cs) + 1;
-    g.nx = (int)(((double)gs[4] - gs[3]) / cs) + 1;
-    if ((long long)g.ny * g.nx <= (1ll << 26)) break;
-    cs *= 2.f;
   }
-  g.y0 = (float)gs[1]; g.x0 = (float)gs[3]; g.inv_cs = 1.f / cs;
-  const int nCells = g.ny * g.nx;
-  int* cellCount = A.take_n<int>(2 * ((size_t)nCells + 1));          // the two arrays that start at zero in one block: one fill
-  int* cellFill = cellCount ? cellCount + nCells + 1 : nullptr;
-  int* cellStart = A.take_n<int>(nCells + 1);
-  CellRec* cellRec = (CellRec*)A.take((size_t)N * sizeof(CellRec));
-  int* nbrCount = A.take_n<int>(N + 1);
-  i64* nbrStart = A.take_n<i64>(N + 1);
-  int* nbrLow = A.take_n<int>(N + 1);
-  if (!cellCount || !cellStart || !cellFill || !cellRec || !nbrCount || !nbrStart || !nbrLow) return -1;
-  SD_CHECK(hipMemsetAsync(cellCount, 0, 2 * ((size_t)nCells + 1) * sizeof(int), s));
-  hipLaunchKernelGGL(k_cell_count, dim3(sd::div_up(N, 256)), dim3(256), 0, s, d_points, N, g, cellCount, candCell);
-  SD_LAUNCH_CHECK();
-  size_t tmpBytes = 0, tmpBytes2 = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmpBytes, cellCount, cellStart, nCells + 1, s);
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmpBytes2, nbrCount, nbrStart, N + 1, s);
-  if (tmpBytes2 > tmpBytes) tmpBytes = tmpBytes2;
-  void* scanTmp = A.take(tmpBytes + 256);
-  if (!scanTmp) return -1;
-  SD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp, tmpBytes, cellCount, cellStart, nCells + 1, s));
-  // Neighbour lists in ONE pass (option "nms2d_neighbours_single_pass", default 1): every candidate gets a slot as large as the population
-  // of the cells its list is built from (known from the cell table: no candidate test needed), the lists -- the better-scored neighbours
-  // only -- are written into the slots from their front and the exact total is counted on the way.  The two-pass form
-  // (count, scan, fill: every candidate test done twice, 1.2 + 0.8 ms at 2048^2) remains for inputs whose slots would exceed 32-bit indices or the workspace.
-  const bool singlePass = sd::option(sd::OPT_NMS2D_NBR_SINGLE) != 0;
-  // (k_cell_fill writes every slot capacity and the closing zero; the two-pass form clears nbrCount itself)
-  hipLaunchKernelGGL(k_cell_fill, dim3(sd::div_up(N, 256)), dim3(256), 0, s, N, candCell, cellStart, cellFill, d_points, bbox, area, cellRec, g, by_bbox, reach,
-                     singlePass ? nbrCount : (int*)nullptr);
-  SD_LAUNCH_CHECK();
-  // The N-sized work lists of the greedy rounds are set up HERE, in front of the neighbour lists: behind the read-back of the list total
-  // their four small launches sat on the critical path in front of round 1 (~60 us of 5-us kernels and gaps)
-  int* U0 = A.take_n<int>(N);
-  unsigned char* pend0 = A.take_n<unsigned char>(N);
-  int* head0 = A.take_n<int>(N);
-  unsigned int* dcount0 = A.take_n<unsigned int>(1);
-  if (!U0 || !pend0 || !head0 || !dcount0) return -1;
-  hipLaunchKernelGGL(k_round_lists_init, dim3(sd::div_up(N, 256)), dim3(256), 0, s, N, U0, state, pend0, head0, dcount0);
 
-  NmsFlags f;
-  f.use_kdtree = use_kdtree; f.use_bbox = use_bbox; f.thr_nonneg = (threshold >= 0.f); f.thr = threshold; f.max_dist = max_dist;
-
-  // ---- neighbour CSR (build_neighbour_lists, nms_rounds.h)
-  const int nbBlocks = (sd::div_up(N, 4) + 7) & ~7;
-  NbrLists L{};
-  L.count = nbrCount; L.low = nbrLow; L.start = nbrStart; L.lowOnly = true;
-  auto launch_neighbours = [&](int mode, const NbrLists& l) {
-    if (mode == 0)
-      hipLaunchKernelGGL((k_neighbours<0>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nullptr, (int*)nullptr,
-                         (int*)nullptr, by_bbox, reach);
-    else if (mode == 1)
-      hipLaunchKernelGGL((k_neighbours<1>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nbrStart, l.nbr, l.waitOn, by_bbox, reach);
-    else
-      hipLaunchKernelGGL((k_neighbours<2>), dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, (const i64*)nbrStart, l.nbr, l.waitOn, by_bbox, reach);
-  };
-  const int rcLists = build_neighbour_lists(A, s, N, singlePass, scanTmp, tmpBytes, launch_neighbours, launch_side, L);
-  // capacity of one call: neighbour lists and pair queues are indexed with 32 bits.  Beyond it (about 13 M candidates at the density
-  // of the 2048^2 bench set) the input has to be sharded -- predict_instances_sharded / predict_instances_big do exactly that.
-  if (rcLists > 0) {
-    sd::set_error("sd_nms2d: %lld neighbour entries for %d candidates exceed the capacity of one call (2^31 - 1): shard the input "
-                  "(predict_instances_sharded / predict_instances_big)", (long long)L.total, N);
-    return -1;
+  // ---- uniform grid: cell size from the largest radius, cell table, the slot capacities of the single-pass lists
+  int build_grid() {
+    int gs[8];
+    SD_CHECK(hipMemcpyAsync(gs, gstats, sizeof(gs), hipMemcpyDeviceToHost, s));
+    SD_CHECK(hipStreamSynchronize(s));
+    memcpy(&max_dist, &gs[0], 4);
+    // cells of HALF the reach (max_dist + 1): a candidate's window (cell_window: its bounding box grown by the reach) then spans at most
+    // (2 (max_dist + 1) + 2 (max_dist + 1)) / cs + 2 = 10 rows; a grid that would exceed 2^26 cells gets coarser cells (fewer rows still)
+    reach = (max_dist + 1.f) * 1.0001f + 1e-3f;
+    by_bbox = (thr >= 0.f || use_bbox) ? 1 : 0;
+    float cs = 0.5f * reach;
+    if (!(cs >= 1.f)) cs = 1.f;
+    for (;;) {
+      g.ny = (int)(((double)gs[2] - gs[1]) / cs) + 1;
+      g.nx = (int)(((double)gs[4] - gs[3]) / cs) + 1;
+      if ((long long)g.ny * g.nx <= (1ll << 26)) break;
+      cs *= 2.f;
+    }
+    g.y0 = (float)gs[1]; g.x0 = (float)gs[3]; g.inv_cs = 1.f / cs;
+    const int nCells = g.ny * g.nx;
+    int* cellCount = A.take_n<int>(2 * ((size_t)nCells + 1));          // the two arrays that start at zero in one block: one fill
+    int* cellFill = cellCount ? cellCount + nCells + 1 : nullptr;
+    cellStart = A.take_n<int>(nCells + 1);
+    cellRec = (CellRec*)A.take((size_t)N * sizeof(CellRec));
+    nbrCount = A.take_n<int>(N + 1);
+    nbrStart = A.take_n<i64>(N + 1);
+    nbrLow = A.take_n<int>(N + 1);
+    if (!cellCount || !cellStart || !cellRec || !nbrCount || !nbrStart || !nbrLow) return -1;
+    SD_CHECK(hipMemsetAsync(cellCount, 0, 2 * ((size_t)nCells + 1) * sizeof(int), s));
+    hipLaunchKernelGGL(k_cell_count, dim3(sd::div_up(N, 256)), dim3(256), 0, s, pts, N, g, cellCount, candCell);
+    SD_LAUNCH_CHECK();
+    size_t scanBytes2 = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, cellCount, cellStart, nCells + 1, s);
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes2, nbrCount, nbrStart, N + 1, s);
+    if (scanBytes2 > scanBytes) scanBytes = scanBytes2;
+    scanTmp = A.take(scanBytes + 256);
+    if (!scanTmp) return -1;
+    SD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp, scanBytes, cellCount, cellStart, nCells + 1, s));
+    // (k_cell_fill writes every slot capacity and the closing zero; the two-pass form clears nbrCount itself)
+    hipLaunchKernelGGL(k_cell_fill, dim3(sd::div_up(N, 256)), dim3(256), 0, s, N, candCell, cellStart, cellFill, pts, bbox, area, cellRec, g, by_bbox, reach,
+                       singlePass ? nbrCount : (int*)nullptr);
+    SD_LAUNCH_CHECK();
+    // The N-sized work lists of the greedy rounds are set up HERE, in front of the neighbour lists: behind the read-back of the list total
+    // their four small launches sat on the critical path in front of round 1 (~60 us of 5-us kernels and gaps)
+    Ucur = A.take_n<int>(N);
+    dfr.pend = A.take_n<unsigned char>(N);
+    dfr.head = A.take_n<int>(N);
+    dfr.count = A.take_n<unsigned int>(1);
+    if (!Ucur || !dfr.pend || !dfr.head || !dfr.count) return -1;
+    hipLaunchKernelGGL(k_round_lists_init, dim3(sd::div_up(N, 256)), dim3(256), 0, s, N, Ucur, state, dfr.pend, dfr.head, dfr.count);
+    f.use_kdtree = use_kdtree; f.use_bbox = use_bbox; f.thr_nonneg = (thr >= 0.f); f.thr = thr; f.max_dist = max_dist;
+    return 0;
   }
-  if (rcLists) return -1;
-  const int* nbr = L.nbr;
-  int* waitOn = L.waitOn;
-  const i64 totalNbr = 2 * L.total;            // ordered neighbour relations: the lists hold each unordered pair once (at its worse-scored end)
 
-  // (the prepared polygons are being written on the side stream meanwhile; the sweep kernels are their first readers and wait for
-  // evPrep in run_pairs -- with the shortcut on, the decision kernel of round 1 runs before that and only needs the properties)
-  SD_CHECK(hipStreamWaitEvent(s, evProps, 0));
-  if (stats) { SD_CHECK(hipEventRecord(ev1, s)); SD_CHECK(hipEventSynchronize(ev1)); float ms = 0; SD_CHECK(hipEventElapsedTime(&ms, ev0, ev1)); ns_pre = ms * 1e6; }
+  // ---- neighbour CSR (build_neighbour_lists, nms_rounds.h), the helper stream's work forked from inside it; ends the broad-phase time
+  int build_lists() {
+    const int nbBlocks = (sd::div_up(N, 4) + 7) & ~7;
+    L.count = nbrCount; L.low = nbrLow; L.start = nbrStart; L.lowOnly = true;
+    auto launch_neighbours = [&](int mode, const NbrLists& l) {      // (the counting pass gets no lists)
+      auto go = [&](auto kern, const i64* start, int* nbr, int* waitOn) {
+        hipLaunchKernelGGL(kern, dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, start, nbr, waitOn, by_bbox, reach);
+      };
+      if (mode == 0) go(k_neighbours<0>, nullptr, nullptr, nullptr);
+      else if (mode == 1) go(k_neighbours<1>, nbrStart, l.nbr, l.waitOn);
+      else go(k_neighbours<2>, nbrStart, l.nbr, l.waitOn);
+    };
+    const int rc = build_neighbour_lists(A, s, N, singlePass, scanTmp, scanBytes, launch_neighbours, [&]() { return fork_side(); }, L);
+    // capacity of one call: neighbour lists and pair queues are indexed with 32 bits.  Beyond it (about 13 M candidates at the density
+    // of the 2048^2 bench set) the input has to be sharded -- predict_instances_sharded / predict_instances_big do exactly that.
+    if (rc > 0)
+      sd::set_error("sd_nms2d: %lld neighbour entries for %d candidates exceed the capacity of one call (2^31 - 1): shard the input "
+                    "(predict_instances_sharded / predict_instances_big)", (long long)L.total, N);
+    if (rc) return -1;
+    totalNbr = 2 * L.total;
+    // (the prepared polygons are being written on the side stream meanwhile; the sweep kernels are their first readers and wait for
+    // sideEv.prep in sweep_pairs -- with the shortcut on, the decision kernel of round 1 runs before that and only needs the properties)
+    SD_CHECK(hipStreamWaitEvent(s, sideEv.props, 0));
+    float ms = 0;
+    if (broadTimer.stop(s) || broadTimer.wait() || broadTimer.ms(&ms)) return -1;
+    ns_pre = ms * 1e6;
+    return 0;
+  }
 
   // ---- greedy rounds: every kernel of a round takes its work-list length from device memory; ONE host round trip per
   // round (the undecided / survivor counts that end the loop)
-  const unsigned long long pairCap = (unsigned long long)(totalNbr / 2 + 64);
-  int* U1 = A.take_n<int>(N);
-  int* K = A.take_n<int>(N);
-  int2* pairs = A.take_n<int2>(pairCap);
-  const unsigned int qCap = (unsigned int)(pairCap < (1ull << 30) ? pairCap : (1ull << 30));
-  unsigned int* spillPairs = A.take_n<unsigned int>(qCap);
-  unsigned int* exactPairs = A.take_n<unsigned int>(qCap);
-  int* Sl = A.take_n<int>(N);
-  Counters* d_cnt = (Counters*)A.take(sizeof(Counters));
-  // pair order (see k_pair_bucket_*): SD_NMS_PAIR_SORT=0 keeps emission order
-  static const bool pairSort = sd::tuning_env("SD_NMS_PAIR_SORT", 1) != 0;
-  unsigned int* pairOrder = pairSort && R <= 32 ? A.take_n<unsigned int>(qCap) : nullptr;
-  unsigned int* bucketHist = A.take_n<unsigned int>(2 * PAIR_BUCKETS);
-  unsigned long long* nOrdered = A.take_n<unsigned long long>(1);
-  if (!U0 || !U1 || !K || !pairs || !spillPairs || !exactPairs || !Sl || !d_cnt || !bucketHist || !nOrdered || (pairSort && R <= 32 && !pairOrder)) return -1;
-  unsigned char* decided = (areaBounds && pairOrder) ? A.take_n<unsigned char>(pairCap) : nullptr;       // (the shortcut filters through the ordered index list)
-  if (areaBounds && pairOrder && !decided) return -1;
-  static int decideGridOf[sd::kMaxDevices] = {};
-  const int decideGrid = decided ? sd::resident_grid((const void*)k_pairs_decide, 256, decideGridOf) : 0;   // every launched wave resident, equal work
-  if (decided && decideGrid <= 0) return -1;
-  i64 totalDecided = 0, totalSkipped = 0;      // pairs decided by the area enclosure; pairs not swept because j was suppressed meanwhile
-  int nU = N, rounds = 0;
-  i64 totalPairs = 0, totalExact = 0, totalSpill = 0;
-  int* Ucur = U0; int* Unext = U1;
-  Counters h;
-  hipEvent_t ev2 = nullptr, ev3 = nullptr;
-  if (stats) { SD_CHECK(hipEventCreate(&ev2)); SD_CHECK(hipEventCreate(&ev3)); }
-  EvGuard evguard2{ev2, ev3};
-  // tail batch threshold: undecided candidates at or below which the remaining rounds are replayed on the device
-  static const int tailDiv = sd::tuning_env("SD_NMS_TAIL_DIV", 6);
-  static const int tailMax = sd::tuning_env("SD_NMS_TAIL_MAX", 65536);
-  const int tailT = tailDiv > 0 ? ((N / tailDiv) < tailMax ? (N / tailDiv) : tailMax) : -1;
-  unsigned char* supp = nullptr; unsigned int* segStart = nullptr; int* segCnt = nullptr;
-  // deferral of the general path to the tail batch (only with a tail batch to run it in)
-  static const bool deferEnv = sd::tuning_env("SD_NMS_DEFER", 1) != 0;
-  const bool deferOn = tailT >= 0 && deferEnv;
-  Deferred dfr{nullptr, nullptr, nullptr, nullptr, nullptr, qCap};
-  unsigned int* firstNew = A.take_n<unsigned int>(1);
-  dfr.pend = pend0; dfr.head = head0; dfr.count = dcount0;          // (allocated and cleared in front of the neighbour lists)
-  if (!firstNew) return -1;
-  if (deferOn) {
-    dfr.pairs = A.take_n<int2>(qCap);
-    dfr.next = A.take_n<int>(qCap);
-    if (!dfr.pairs || !dfr.next) return -1;
+  int begin_rounds() {
+    pairCap = (unsigned long long)(totalNbr / 2 + 64);
+    qCap = (unsigned int)(pairCap < (1ull << 30) ? pairCap : (1ull << 30));
+    Unext = A.take_n<int>(N);
+    K = A.take_n<int>(N);
+    pairs = A.take_n<int2>(pairCap);
+    spillPairs = A.take_n<unsigned int>(qCap);
+    exactPairs = A.take_n<unsigned int>(qCap);
+    Sl = A.take_n<int>(N);
+    d_cnt = (Counters*)A.take(sizeof(Counters));
+    if (ordered) pairOrder = A.take_n<unsigned int>(qCap);
+    bucketHist = A.take_n<unsigned int>(2 * PAIR_BUCKETS);
+    nOrdered = A.take_n<unsigned long long>(1);
+    if (decide) decided = A.take_n<unsigned char>(pairCap);
+    firstNew = A.take_n<unsigned int>(1);
+    nNewExact = A.take_n<unsigned int>(1);
+    if (!Unext || !K || !pairs || !spillPairs || !exactPairs || !Sl || !d_cnt || !bucketHist || !nOrdered || !firstNew || !nNewExact || (ordered && !pairOrder) ||
+        (decide && !decided)) return -1;
+    static int decideGridOf[sd::kMaxDevices] = {};
+    decideGrid = decide ? sd::resident_grid((const void*)k_pairs_decide, 256, decideGridOf) : 0;   // every launched wave resident, equal work
+    if (decide && decideGrid <= 0) return -1;
+    dfr.cap = qCap;
+    if (deferOn) {
+      dfr.pairs = A.take_n<int2>(qCap);
+      dfr.next = A.take_n<int>(qCap);
+      if (!dfr.pairs || !dfr.next) return -1;
+    }
+    if (deferFrom > 0) {
+      defKind = A.take_n<unsigned char>(qCap); nJoinDef = A.take_n<unsigned int>(1);
+      if (!defKind || !nJoinDef) return -1;
+      SD_CHECK(hipMemsetAsync(defKind, 0, qCap, s));
+    }
+    nU = N;
+    return 0;
   }
-  i64 nDeferred = 0;
-  bool sideGeneral = false;                   // tail batch: the deferred pairs' general-path launch runs on the helper stream
-  unsigned int* nNewExact = A.take_n<unsigned int>(1);
-  if (!nNewExact) return -1;
-  // deferral of the enclosure's undecided pairs (see k_defer_undecided): from round 2 on by default (option nms2d_defer_undecided)
-  const int deferFrom = (deferOn && decided) ? sd::option(sd::OPT_NMS2D_DEFER_UNDECIDED) : 0;
-  const unsigned int deferMax = (unsigned int)(sd::option(sd::OPT_NMS2D_DEFER_MAX) > 0 ? sd::option(sd::OPT_NMS2D_DEFER_MAX) : 0);
-  unsigned char* defKind = nullptr; unsigned int* nJoinDef = nullptr;
-  if (deferFrom > 0) {
-    defKind = A.take_n<unsigned char>(qCap); nJoinDef = A.take_n<unsigned int>(1);
-    if (!defKind || !nJoinDef) return -1;
-    SD_CHECK(hipMemsetAsync(defKind, 0, qCap, s));
+
+  // The ordered-pair path in front of a sweep (n_rays <= 32): the decision shortcut, the deferral of what it leaves undecided, and the
+  // offset-ordered index list of the pairs that remain (pairOrder[0 .. *nOrdered)).
+  int order_pairs(unsigned char* suppOut, const unsigned int* first) {
+    // measured on the 2048^2 bench set (pair kernels incl. the bucketing, ms): emission order 9.9 | 32x32 7.85 | 64x16 7.38 | 64x64 6.70 |
+    // 16 local-minima classes x 16x16 8.53: resolution of the offset is what counts (64x64 = whole pixels at radius 10)
+    static const int modes[6][3] = {{1, 32, 32}, {1, 64, 16}, {1, 64, 64}, {16, 16, 16}, {16, 32, 8}, {4, 32, 32}};
+    const int* md = modes[keyMode >= 0 && keyMode < 6 ? keyMode : 2];
+    const PairKey key{(const char*)prep, prepStride, 1.f / (4.f * (max_dist + 1.f)), md[0], md[1], md[2]};   // offsets lie in (-2 max_dist, 2 max_dist)
+    SD_CHECK(hipMemsetAsync(bucketHist, 0, PAIR_BUCKETS * sizeof(unsigned int), s));
+    if (decided)
+      hipLaunchKernelGGL(k_pairs_decide, dim3(decideGrid), dim3(256), 0, s, pairs, &d_cnt->nPairs, first, vx, vy, R, props, area, thr, state, suppOut,
+                         decided, &d_cnt->nDecided);
+    if (!suppOut && deferFrom > 0 && rounds >= deferFrom)      // few undecided pairs: they wait for the tail batch's sweep launch
+      hipLaunchKernelGGL(k_defer_undecided, dim3(256), dim3(256), 0, s, pairs, &d_cnt->nPairs, &d_cnt->nDecided, deferMax, decided, state, dfr, defKind, &d_cnt->nErr);
+    // tail batch with deferred undecided pairs: they sit in the list's prefix with decided[] = 0 and are bucketed with the rest
+    const unsigned int* bfirst = (suppOut && deferFrom > 0) ? nullptr : first;
+    SD_CHECK(hipStreamWaitEvent(s, sideEv.prep, 0));          // the prepared polygons (side stream; complete long before, except in round 1)
+    const unsigned char* liveState = suppOut ? nullptr : state;      // normal round: pairs whose j is suppressed by now are not swept
+    hipLaunchKernelGGL(k_pair_bucket_count, dim3(512), dim3(256), 0, s, pairs, &d_cnt->nPairs, bfirst, pts, key, bucketHist, decided, liveState,
+                       &d_cnt->nSkipped);
+    hipLaunchKernelGGL(k_pair_bucket_scan, dim3(1), dim3(1024), 0, s, bucketHist, bucketHist + PAIR_BUCKETS, nOrdered);
+    hipLaunchKernelGGL(k_pair_bucket_scatter, dim3(512), dim3(256), 0, s, pairs, &d_cnt->nPairs, bfirst, pts, key, bucketHist + PAIR_BUCKETS,
+                       pairOrder, qCap, decided, liveState);
+    SD_LAUNCH_CHECK();
+    return 0;
   }
-  i64 totalUndecDeferred = 0;
-  i64 nUndecDeferredUpper = 0;               // upper bound of the kind-1 deferred pairs so far (those whose j was suppressed meanwhile are skipped)
+
   // one beam-path pass over the current pair list (tier 1, tier 2, then the general path -- or its deferral); suppOut == nullptr
   // applies decisions to state (normal round), else records them per pair (tail batch, whose first *firstNew entries are the
   // deferred pairs, already queued for the general path)
-  auto run_pairs = [&](unsigned char* suppOut) -> int {
+  int sweep_pairs(unsigned char* suppOut) {
     const unsigned int* first = suppOut ? firstNew : nullptr;
-    if (stats) SD_CHECK(hipEventRecord(ev0, s));
-    PairQueues q1{spillPairs, &d_cnt->nSpill, exactPairs, &d_cnt->nExact, qCap};
-    PairQueues q2{exactPairs, &d_cnt->nExact, exactPairs, &d_cnt->nExact, qCap};   // what tier 2 cannot hold goes to the general path
-    int rc;
-    if (R <= 32) {
-      if (pairOrder) {
-        // measured on the 2048^2 bench set (pair kernels incl. the bucketing, ms): emission order 9.9 | 32x32 7.85 | 64x16 7.38 | 64x64 6.70 |
-        // 16 local-minima classes x 16x16 8.53: resolution of the offset is what counts (64x64 = whole pixels at radius 10)
-        static const int keyMode = sd::tuning_env("SD_NMS_PAIR_KEY", 2);
-        static const int modes[6][3] = {{1, 32, 32}, {1, 64, 16}, {1, 64, 64}, {16, 16, 16}, {16, 32, 8}, {4, 32, 32}};
-        const int* md = modes[keyMode >= 0 && keyMode < 6 ? keyMode : 2];
-        const PairKey key{(const char*)prep, prepStride, 1.f / (4.f * (max_dist + 1.f)), md[0], md[1], md[2]};   // offsets lie in (-2 max_dist, 2 max_dist)
-        SD_CHECK(hipMemsetAsync(bucketHist, 0, PAIR_BUCKETS * sizeof(unsigned int), s));
-        if (decided)
-          hipLaunchKernelGGL(k_pairs_decide, dim3(decideGrid), dim3(256), 0, s, pairs, &d_cnt->nPairs, first, vx, vy, R, props, area, threshold, state, suppOut,
-                             decided, &d_cnt->nDecided);
-        if (!suppOut && deferFrom > 0 && rounds >= deferFrom)      // few undecided pairs: they wait for the tail batch's sweep launch
-          hipLaunchKernelGGL(k_defer_undecided, dim3(256), dim3(256), 0, s, pairs, &d_cnt->nPairs, &d_cnt->nDecided, deferMax, decided, state, dfr, defKind, &d_cnt->nErr);
-        // tail batch with deferred undecided pairs: they sit in the list's prefix with decided[] = 0 and are bucketed with the rest
-        const unsigned int* bfirst = (suppOut && deferFrom > 0) ? nullptr : first;
-        SD_CHECK(hipStreamWaitEvent(s, evPrep, 0));          // the prepared polygons (side stream; complete long before, except in round 1)
-        const unsigned char* liveState = suppOut ? nullptr : state;      // normal round: pairs whose j is suppressed by now are not swept
-        hipLaunchKernelGGL(k_pair_bucket_count, dim3(512), dim3(256), 0, s, pairs, &d_cnt->nPairs, bfirst, d_points, key, bucketHist, decided, liveState,
-                           &d_cnt->nSkipped);
-        hipLaunchKernelGGL(k_pair_bucket_scan, dim3(1), dim3(1024), 0, s, bucketHist, bucketHist + PAIR_BUCKETS, nOrdered);
-        hipLaunchKernelGGL(k_pair_bucket_scatter, dim3(512), dim3(256), 0, s, pairs, &d_cnt->nPairs, bfirst, d_points, key, bucketHist + PAIR_BUCKETS,
-                           pairOrder, qCap, decided, liveState);
+    if (pairTimer.start(s)) return -1;
+    if (!ordered) SD_CHECK(hipStreamWaitEvent(s, sideEv.prep, 0));
+    else if (order_pairs(suppOut, first)) return -1;
+    const Sweep w{s, R, vx, vy, prep, area, thr, pairs, spillPairs, exactPairs, qCap, d_cnt, state, suppOut};
+    auto general = [&]() -> int {
+      if (fullTimer.start(s)) return -1;
+      if (!suppOut && deferOn) {
+        hipLaunchKernelGGL(k_defer, dim3(64), dim3(256), 0, s, pairs, exactPairs, &d_cnt->nExact, qCap, dfr, &d_cnt->nErr);
         SD_LAUNCH_CHECK();
-        rc = BeamPath<32, 64>::tier1(pairs, pairOrder, nOrdered, (const unsigned int*)nullptr, prep, area, threshold, state, suppOut, q1, s);
-      } else {
-        SD_CHECK(hipStreamWaitEvent(s, evPrep, 0));
-        rc = BeamPath<32, 64>::tier1(pairs, (const unsigned int*)nullptr, &d_cnt->nPairs, first, prep, area, threshold, state, suppOut, q1, s);
-      }
-      if (stats) SD_CHECK(hipEventRecord(ev1, s));
-      if (!rc) rc = BeamPath<32, 64>::tier2(pairs, spillPairs, &d_cnt->nSpill, (const unsigned int*)nullptr, prep, area, threshold, state, suppOut, q2, s);
-    } else {
-      SD_CHECK(hipStreamWaitEvent(s, evPrep, 0));
-      if (R <= 64) rc = BeamPath<64, 64>::tier2(pairs, (const unsigned int*)nullptr, &d_cnt->nPairs, first, prep, area, threshold, state, suppOut, q2, s);
-      else if (R <= 128) rc = BeamPath<128, 32>::tier2(pairs, (const unsigned int*)nullptr, &d_cnt->nPairs, first, prep, area, threshold, state, suppOut, q2, s);
-      else rc = BeamPath<256, 16>::tier2(pairs, (const unsigned int*)nullptr, &d_cnt->nPairs, first, prep, area, threshold, state, suppOut, q2, s);
-      if (stats) SD_CHECK(hipEventRecord(ev1, s));
-    }
-    if (rc) return -1;
-    if (stats) SD_CHECK(hipEventRecord(ev2, s));
-    if (!suppOut && deferOn) {
-      hipLaunchKernelGGL(k_defer, dim3(64), dim3(256), 0, s, pairs, exactPairs, &d_cnt->nExact, qCap, dfr, &d_cnt->nErr);
-      SD_LAUNCH_CHECK();
-    } else if (suppOut && sideGeneral) {
-      // tail batch: the deferred pairs (the first nDeferred queue entries) are being evaluated on the helper stream since the batch
-      // began; here only what the two tiers added behind them, then join
-      hipLaunchKernelGGL(k_count_after, dim3(1), dim3(1), 0, s, nNewExact, &d_cnt->nExact, deferFrom > 0 ? nJoinDef : firstNew);
-      SD_LAUNCH_CHECK();
-      if (sd::clip_full_pairs(pairs, exactPairs + nDeferred, nNewExact, qCap - (unsigned int)nDeferred, R, vx, vy, area, threshold, state, suppOut, &d_cnt->nErr, s)) return -1;
-      SD_CHECK(hipStreamWaitEvent(s, evJoin, 0));
-    } else if (sd::clip_full_pairs(pairs, exactPairs, &d_cnt->nExact, qCap, R, vx, vy, area, threshold, state, suppOut, &d_cnt->nErr, s)) return -1;
-    if (stats) SD_CHECK(hipEventRecord(ev3, s));
-    return 0;
-  };
-  auto account = [&](const char* what) -> int {
-    if (h.nPairs > pairCap || h.nSpill > qCap || h.nExact > qCap) { sd::set_error("sd_nms2d: pair queue overflow (internal error)"); return -1; }
-    if (h.nErr) { sd::set_error("sd_nms2d: %u pairs exceeded the general path's fixed capacities or the deferred-pair list (with more than 64 rays: at least that many; the launch stops at the first)", h.nErr); return -1; }
+      } else if (suppOut && sideJoin.pending) {
+        // tail batch: the deferred pairs (the first nDeferred queue entries) are being evaluated on the helper stream since the batch
+        // began; here only what the two tiers added behind them, then join
+        hipLaunchKernelGGL(k_count_after, dim3(1), dim3(1), 0, s, nNewExact, &d_cnt->nExact, deferFrom > 0 ? nJoinDef : firstNew);
+        SD_LAUNCH_CHECK();
+        if (sd::clip_full_pairs(pairs, exactPairs + nDeferred, nNewExact, qCap - (unsigned int)nDeferred, R, vx, vy, area, thr, state, suppOut, &d_cnt->nErr, s)) return -1;
+        if (sideJoin.join(s)) return -1;
+      } else if (general_path(w)) return -1;
+      return fullTimer.stop(s);
+    };
+    if (ordered) return sweep_tiers(w, pairOrder, nOrdered, nullptr, pairTimer, general);
+    return sweep_tiers(w, nullptr, &d_cnt->nPairs, first, pairTimer, general);
+  }
+
+  // the counters of a round or of the tail batch, read back: refuse overflows, add to the totals and the times
+  int account(const char* what) {
+    if (check_sweep("sd_nms2d", h, qCap, h.nPairs > pairCap,
+                    " or the deferred-pair list (with more than 64 rays: at least that many; the launch stops at the first)")) return -1;
     totalPairs += (i64)h.nPairs; totalExact += h.nExact; totalSpill += h.nSpill; totalDecided += h.nDecided; totalSkipped += h.nSkipped;
-    if (stats) {
+    if (wantStats) {
       float ms = 0, ms2 = 0;
-      SD_CHECK(hipEventElapsedTime(&ms, ev0, ev1)); SD_CHECK(hipEventElapsedTime(&ms2, ev2, ev3));
+      if (pairTimer.ms(&ms) || fullTimer.ms(&ms2)) return -1;
       if (h.nPairs) { ns_pairs += ms * 1e6; ++n_pair_launches; }
       ns_full += ms2 * 1e6;
-      if (sd::option(sd::OPT_TRACE)) printf("%s %d: nU=%d nK=%d pairs=%llu decided by the area enclosure=%u j already suppressed=%u spill=%u exact=%u pair_kernel=%.3f ms general_path=%.3f ms\n", what, rounds, h.nU, h.nK, h.nPairs, h.nDecided, h.nSkipped, h.nSpill, h.nExact, ms, ms2);
+      if (trace) printf("%s %d: nU=%d nK=%d pairs=%llu decided by the area enclosure=%u j already suppressed=%u spill=%u exact=%u pair_kernel=%.3f ms general_path=%.3f ms\n", what, rounds, h.nU, h.nK, h.nPairs, h.nDecided, h.nSkipped, h.nSpill, h.nExact, ms, ms2);
     }
     return 0;
-  };
-  bool forceTail = false;
-  while (nU > 0) {
+  }
+
+  // one greedy round: triage and list scan of the undecided, the new survivors' pairs, their sweep -- or, once few enough candidates
+  // are left (or all of them wait for deferred pairs), the tail batch
+  int run_round() {
     ++rounds;
-    if (tailT >= 0 && ((nU <= tailT && rounds > 1) || forceTail)) {
-      // ---- tail batch: every remaining (undecided, undecided) pair at once, then the greedy rounds replayed on the device
-      if (!supp) { supp = A.take_n<unsigned char>(pairCap); segStart = A.take_n<unsigned int>(N); segCnt = A.take_n<int>(N); }
-      if (!supp || !segStart || !segCnt) return -1;
-      SD_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(Counters), s));
-      SD_CHECK(hipMemsetAsync(supp, 0, pairCap, s));
-      const int wg = sd::div_up(nU, 4) < 2048 ? sd::div_up(nU, 4) : 2048;
-      if (deferFrom > 0) {
-        hipLaunchKernelGGL(k_tail_init2, dim3(64), dim3(256), 0, s, dfr, defKind, pairs, exactPairs, &d_cnt->nPairs, &d_cnt->nExact, firstNew, decided, state,
-                           &d_cnt->nSkipped);
-        hipLaunchKernelGGL(k_copy_u32, dim3(1), dim3(1), 0, s, nJoinDef, &d_cnt->nExact);
-      } else
-        hipLaunchKernelGGL(k_tail_init, dim3(64), dim3(256), 0, s, dfr, pairs, exactPairs, &d_cnt->nPairs, &d_cnt->nExact, firstNew);
-      // The deferred pairs all need the general path (a latency-bound launch of ~1 ms over a few thousand pairs, a fraction of the
-      // chip): it starts NOW on the helper stream, next to the emission of the remaining pairs and the two bound-slot tiers; decisions
-      // are recorded per pair (supp[]), so the two streams write disjoint bytes.  Joined in run_pairs.
-      sideGeneral = deferOn && nDeferred > 0 && nDeferred < (i64)qCap && side != nullptr;
-      if (sideGeneral) {
-        SD_CHECK(hipEventRecord(evFork, s));
-        SD_CHECK(hipStreamWaitEvent(side, evFork, 0));
-        if (sd::clip_full_pairs(pairs, exactPairs, deferFrom > 0 ? nJoinDef : firstNew, qCap, R, vx, vy, area, threshold, state, supp, &d_cnt->nErr, side)) return -1;
-        SD_CHECK(hipEventRecord(evJoin, side));
-      }
-      hipLaunchKernelGGL(k_tail_emit, dim3(wg), dim3(256), 0, s, Ucur, nU, state, nbrStart, nbrLow, nbr, f, d_points, bbox, radius, area, pairs,
-                         &d_cnt->nPairs, pairCap, segStart, segCnt);
-      SD_LAUNCH_CHECK();
-      if (run_pairs(supp)) return -1;
-      hipEvent_t evr0 = nullptr, evr1 = nullptr;
-      const bool tr = stats && sd::option(sd::OPT_TRACE);
-      if (tr) { SD_CHECK(hipEventCreate(&evr0)); SD_CHECK(hipEventCreate(&evr1)); SD_CHECK(hipEventRecord(evr0, s)); }
-      for (int it = 0; it < 10; ++it)
-        hipLaunchKernelGGL(k_tail_step, dim3(sd::div_up(nU, 256)), dim3(256), 0, s, Ucur, nU, state, pairs, supp, segStart, segCnt, pairCap, dfr.head, dfr.next);
-      hipLaunchKernelGGL(k_tail_resolve, dim3(1), dim3(1024), 0, s, Ucur, nU, state, pairs, supp, segStart, segCnt, pairCap, &d_cnt->left, dfr.head, dfr.next);
-      SD_LAUNCH_CHECK();
-      if (tr) { SD_CHECK(hipEventRecord(evr1, s)); SD_CHECK(hipEventSynchronize(evr1)); float ms = 0; SD_CHECK(hipEventElapsedTime(&ms, evr0, evr1));
-                printf("tail replay (10 steps + resolve loop): %.3f ms\n", ms); (void)hipEventDestroy(evr0); (void)hipEventDestroy(evr1); }
-      unsigned int hDefTotal = (unsigned int)nDeferred;
-      SD_CHECK(hipMemcpyAsync(&h, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s));
-      if (deferFrom > 0) SD_CHECK(hipMemcpyAsync(&hDefTotal, dfr.count, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-      SD_CHECK(hipStreamSynchronize(s));
-      h.nU = nU; h.nK = 0;
-      if (deferFrom > 0) { totalUndecDeferred = (i64)hDefTotal - nDeferred; if ((unsigned long long)hDefTotal <= h.nPairs) h.nPairs -= hDefTotal; }
-      else
-      if ((i64)h.nPairs >= nDeferred) h.nPairs -= (unsigned long long)nDeferred;      // the deferred pairs were counted in their rounds
-      if ((i64)h.nExact >= nDeferred) h.nExact -= (unsigned int)nDeferred;
-      if (account("tail batch after round")) return -1;
-      if (h.left) { sd::set_error("sd_nms2d: tail batch left candidates undecided (internal error)"); return -1; }
-      nU = 0;
-      break;
-    }
+    if (tailT >= 0 && ((nU <= tailT && rounds > 1) || forceTail)) return tail_batch();
     SD_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(Counters), s));
-    hipLaunchKernelGGL(k_round_triage, dim3(sd::div_up(nU, 1024)), dim3(1024), 0, s, Ucur, nU, state, waitOn, Unext, K, Sl, (int*)d_cnt, dfr.pend);
+    hipLaunchKernelGGL(k_round_triage, dim3(sd::div_up(nU, 1024)), dim3(1024), 0, s, Ucur, nU, state, L.waitOn, Unext, K, Sl, (int*)d_cnt, dfr.pend);
     const int wgrid = sd::div_up(nU, 4) < 2048 ? sd::div_up(nU, 4) : 2048;
-    hipLaunchKernelGGL(k_round_scan, dim3(wgrid), dim3(256), 0, s, Sl, state, nbrStart, nbrLow, nbr, waitOn, Unext, K, (int*)d_cnt, dfr.pend);
-    hipLaunchKernelGGL(k_round_emit, dim3(wgrid), dim3(256), 0, s, K, &d_cnt->nK, state, g, cellRec, cellStart, by_bbox, reach, f, d_points, bbox,
+    hipLaunchKernelGGL(k_round_scan, dim3(wgrid), dim3(256), 0, s, Sl, state, nbrStart, nbrLow, L.nbr, L.waitOn, Unext, K, (int*)d_cnt, dfr.pend);
+    hipLaunchKernelGGL(k_round_emit, dim3(wgrid), dim3(256), 0, s, K, &d_cnt->nK, state, g, cellRec, cellStart, by_bbox, reach, f, pts, bbox,
                        radius, area, pairs, &d_cnt->nPairs, pairCap);
     SD_LAUNCH_CHECK();
-    if (run_pairs(nullptr)) return -1;
+    if (sweep_pairs(nullptr)) return -1;
     SD_CHECK(hipMemcpyAsync(&h, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s));
     SD_CHECK(hipStreamSynchronize(s));
     if (h.nK == 0 && h.nU > 0) {
@@ -1319,19 +1303,105 @@ extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n
     if (account("round")) return -1;
     nU = h.nU;
     int* t = Ucur; Ucur = Unext; Unext = t;
+    return 0;
   }
-  hipLaunchKernelGGL(k_keep, dim3(sd::div_up(N, 256)), dim3(256), 0, s, state, d_keep, N);
-  SD_LAUNCH_CHECK();
-  SD_CHECK(hipStreamSynchronize(s));
-  if (stats) { stats[0] = totalPairs; stats[1] = totalExact; stats[2] = rounds; stats[3] = totalNbr;
-               stats[4] = (int64_t)ns_pairs; stats[5] = n_pair_launches; stats[6] = (int64_t)ns_full; stats[7] = (int64_t)ns_pre;
-               stats[8] = totalSpill; stats[9] = totalDecided; stats[10] = totalUndecDeferred; stats[11] = totalSkipped; }
+
+  // ---- tail batch: every remaining (undecided, undecided) pair at once, then the greedy rounds replayed on the device; ends the rounds
+  int tail_batch() {
+    if (!supp) { supp = A.take_n<unsigned char>(pairCap); segStart = A.take_n<unsigned int>(N); segCnt = A.take_n<int>(N); }
+    if (!supp || !segStart || !segCnt) return -1;
+    SD_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(Counters), s));
+    SD_CHECK(hipMemsetAsync(supp, 0, pairCap, s));
+    if (deferFrom > 0) {
+      hipLaunchKernelGGL(k_tail_init2, dim3(64), dim3(256), 0, s, dfr, defKind, pairs, exactPairs, &d_cnt->nPairs, &d_cnt->nExact, firstNew, decided, state,
+                         &d_cnt->nSkipped);
+      hipLaunchKernelGGL(k_copy_u32, dim3(1), dim3(1), 0, s, nJoinDef, &d_cnt->nExact);
+    } else
+      hipLaunchKernelGGL(k_tail_init, dim3(64), dim3(256), 0, s, dfr, pairs, exactPairs, &d_cnt->nPairs, &d_cnt->nExact, firstNew);
+    // The deferred pairs all need the general path (a latency-bound launch of ~1 ms over a few thousand pairs, a fraction of the
+    // chip): it starts NOW on the helper stream, next to the emission of the remaining pairs and the two bound-slot tiers; decisions
+    // are recorded per pair (supp[]), so the two streams write disjoint bytes.  Joined in sweep_pairs.
+    if (deferOn && nDeferred > 0 && nDeferred < (i64)qCap) {
+      if (sideJoin.begin(s, side)) return -1;
+      if (sd::clip_full_pairs(pairs, exactPairs, deferFrom > 0 ? nJoinDef : firstNew, qCap, R, vx, vy, area, thr, state, supp, &d_cnt->nErr, side)) return -1;
+      if (sideJoin.end(side)) return -1;
+    }
+    const int wg = sd::div_up(nU, 4) < 2048 ? sd::div_up(nU, 4) : 2048;
+    hipLaunchKernelGGL(k_tail_emit, dim3(wg), dim3(256), 0, s, Ucur, nU, state, nbrStart, nbrLow, L.nbr, f, pts, bbox, radius, area, pairs,
+                       &d_cnt->nPairs, pairCap, segStart, segCnt);
+    SD_LAUNCH_CHECK();
+    if (sweep_pairs(supp)) return -1;
+    if (trace && (replayTimer.init() || replayTimer.start(s))) return -1;
+    for (int it = 0; it < 10; ++it)
+      hipLaunchKernelGGL(k_tail_step, dim3(sd::div_up(nU, 256)), dim3(256), 0, s, Ucur, nU, state, pairs, supp, segStart, segCnt, pairCap, dfr.head, dfr.next);
+    hipLaunchKernelGGL(k_tail_resolve, dim3(1), dim3(1024), 0, s, Ucur, nU, state, pairs, supp, segStart, segCnt, pairCap, &d_cnt->left, dfr.head, dfr.next);
+    SD_LAUNCH_CHECK();
+    if (trace) {
+      float ms = 0;
+      if (replayTimer.stop(s) || replayTimer.wait() || replayTimer.ms(&ms)) return -1;
+      printf("tail replay (10 steps + resolve loop): %.3f ms\n", ms);
+    }
+    unsigned int hDefTotal = (unsigned int)nDeferred;      // all deferred pairs, the undecided ones included
+    SD_CHECK(hipMemcpyAsync(&h, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s));
+    if (deferFrom > 0) SD_CHECK(hipMemcpyAsync(&hDefTotal, dfr.count, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    SD_CHECK(hipStreamSynchronize(s));
+    h.nU = nU; h.nK = 0;
+    if (deferFrom > 0) totalUndecDeferred = (i64)hDefTotal - nDeferred;
+    // pairs: the deferred ones in the list's prefix were counted in their rounds -- every deferred pair where the undecided ones are
+    // deferred too (hDefTotal), the general-path ones otherwise
+    const unsigned long long counted = deferFrom > 0 ? (unsigned long long)hDefTotal : (unsigned long long)nDeferred;
+    if (counted <= h.nPairs) h.nPairs -= counted;
+    // general-path pairs: the queue's deferred prefix was counted in its rounds, whatever else was deferred
+    if ((i64)h.nExact >= nDeferred) h.nExact -= (unsigned int)nDeferred;
+    if (account("tail batch after round")) return -1;
+    if (h.left) { sd::set_error("sd_nms2d: tail batch left candidates undecided (internal error)"); return -1; }
+    nU = 0;
+    return 0;
+  }
+
+  int report(uint8_t* d_keep, int64_t* stats, int verbose) {
+    hipLaunchKernelGGL(k_keep, dim3(sd::div_up(N, 256)), dim3(256), 0, s, state, d_keep, N);
+    SD_LAUNCH_CHECK();
+    SD_CHECK(hipStreamSynchronize(s));
+    if (stats) { stats[0] = totalPairs; stats[1] = totalExact; stats[2] = rounds; stats[3] = totalNbr;
+                 stats[4] = (int64_t)ns_pairs; stats[5] = n_pair_launches; stats[6] = (int64_t)ns_full; stats[7] = (int64_t)ns_pre;
+                 stats[8] = totalSpill; stats[9] = totalDecided; stats[10] = totalUndecDeferred; stats[11] = totalSkipped; }
+    if (verbose) {
+      printf("NMS: %lld pair intersections (%lld on the exact-join path), %d greedy rounds, %lld neighbour entries\n",
+             (long long)totalPairs, (long long)totalExact, rounds, (long long)totalNbr);
+      fflush(stdout);
+    }
+    return 0;
+  }
+};
+}  // namespace
+
+extern "C" int sd_nms2d_device(const float* d_dist, const float* d_points, int n_polys, int n_rays, int use_kdtree,
+                               int use_bbox, int verbose, float threshold, uint8_t* d_keep, int64_t* stats,
+                               void* stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  if (stats) memset(stats, 0, 16 * sizeof(int64_t));
+  if (n_polys <= 0) return 0;
+  Nms2d c(s, d_dist, d_points, n_polys, n_rays, use_kdtree, use_bbox, threshold, stats != nullptr);
+  if (c.plan()) return -1;
   if (verbose) {
-    printf("NMS: %lld pair intersections (%lld on the exact-join path), %d greedy rounds, %lld neighbour entries\n",
-           (long long)totalPairs, (long long)totalExact, rounds, (long long)totalNbr);
-    fflush(stdout);
+    printf("Non Maximum Suppression (2D) ++++ \n");
+    printf("NMS: n_polys    = %d \nNMS: n_rays     = %d  \nNMS: thresh     = %.3f \nNMS: use_bbox   = %d\nNMS: use_kdtree = %d\n",
+           n_polys, n_rays, threshold, use_bbox, use_kdtree);
+    printf("NMS: using HIP (gfx950), uniform-grid broad phase + scan-beam pair kernel\n");
   }
-  return 0;
+  // all-pairs configuration with a negative threshold: every pair (0, j) passes the reference's
+  // filters and overlap >= 0 > thr, so polygon 0 suppresses everything else.
+  if (!use_kdtree && !use_bbox && threshold < 0) {
+    SD_CHECK(hipMemsetAsync(d_keep, 0, n_polys, s));
+    SD_CHECK(hipMemsetAsync(d_keep, 1, 1, s));
+    SD_CHECK(hipStreamSynchronize(s));
+    return 0;
+  }
+  if (c.build() || c.build_grid() || c.build_lists() || c.begin_rounds()) return -1;
+  while (c.nU > 0)
+    if (c.run_round()) return -1;
+  return c.report(d_keep, stats, verbose);
 }
 
 // ---- the legacy variant: c_non_max_suppression_inds_old (stardist2d.cpp:173-386; caller stardist/nms.py:20-74, reference test
@@ -1466,43 +1536,23 @@ extern "C" int sd_nms2d_old_device(const int32_t* d_polys, int n_polys, int n_ra
     unsigned char* supp = A.take_n<unsigned char>((size_t)total + 64);
     unsigned int* spillPairs = A.take_n<unsigned int>(qCap);
     unsigned int* exactPairs = A.take_n<unsigned int>(qCap);
-    size_t prepStride;
-    if (R <= 32) prepStride = sizeof(sdclip::PolyPrep<32>); else if (R <= 64) prepStride = sizeof(sdclip::PolyPrep<64>);
-    else if (R <= 128) prepStride = sizeof(sdclip::PolyPrep<128>); else prepStride = sizeof(sdclip::PolyPrep<256>);
-    void* prep = A.take((size_t)N * prepStride);
+    void* prep = A.take((size_t)N * prep_stride(R));
     if (!pairs || !supp || !spillPairs || !exactPairs || !prep) return -1;
     SD_CHECK(hipMemsetAsync(supp, 0, (size_t)total + 64, s));
     hipLaunchKernelGGL((k_old_pairs<1>), dim3(sd::div_up(N, 4)), dim3(256), 0, s, N, o, d_mapping, bbox, gmax, cnt, (const i64*)start, pairs);
     SD_LAUNCH_CHECK();
     const unsigned long long nP = (unsigned long long)total;
     SD_CHECK(hipMemcpyAsync(&d_cnt->nPairs, &nP, sizeof(nP), hipMemcpyHostToDevice, s));
-    PairQueues q1{spillPairs, &d_cnt->nSpill, exactPairs, &d_cnt->nExact, qCap};
-    PairQueues q2{exactPairs, &d_cnt->nExact, exactPairs, &d_cnt->nExact, qCap};
-    int rc;
-    const unsigned int* none = nullptr;
-    if (R <= 32) {
-      rc = BeamPath<32, 64>::prepare(vx, vy, N, R, prep, s);
-      if (!rc) rc = BeamPath<32, 64>::tier1(pairs, none, &d_cnt->nPairs, none, prep, area, threshold, state, supp, q1, s);
-      if (!rc) rc = BeamPath<32, 64>::tier2(pairs, spillPairs, &d_cnt->nSpill, none, prep, area, threshold, state, supp, q2, s);
-    } else if (R <= 64) {
-      rc = BeamPath<64, 64>::prepare(vx, vy, N, R, prep, s);
-      if (!rc) rc = BeamPath<64, 64>::tier2(pairs, none, &d_cnt->nPairs, none, prep, area, threshold, state, supp, q2, s);
-    } else if (R <= 128) {
-      rc = BeamPath<128, 32>::prepare(vx, vy, N, R, prep, s);
-      if (!rc) rc = BeamPath<128, 32>::tier2(pairs, none, &d_cnt->nPairs, none, prep, area, threshold, state, supp, q2, s);
-    } else {
-      rc = BeamPath<256, 16>::prepare(vx, vy, N, R, prep, s);
-      if (!rc) rc = BeamPath<256, 16>::tier2(pairs, none, &d_cnt->nPairs, none, prep, area, threshold, state, supp, q2, s);
-    }
-    if (rc) return -1;
-    if (sd::clip_full_pairs(pairs, exactPairs, &d_cnt->nExact, qCap, R, vx, vy, area, threshold, state, supp, &d_cnt->nErr, s)) return -1;
+    const Sweep w{s, R, vx, vy, prep, area, threshold, pairs, spillPairs, exactPairs, qCap, d_cnt, state, supp};
+    Timer untimed;
+    if (prepare_polys(vx, vy, N, R, nullptr, prep, s)) return -1;
+    if (sweep_tiers(w, nullptr, &d_cnt->nPairs, nullptr, untimed, [&]() { return general_path(w); })) return -1;
     hipLaunchKernelGGL(k_old_replay, dim3(1), dim3(1024), 0, s, N, (const i64*)start, (const int2*)pairs, (const unsigned char*)supp, state);
     SD_LAUNCH_CHECK();
     Counters h;
     SD_CHECK(hipMemcpyAsync(&h, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s));
     SD_CHECK(hipStreamSynchronize(s));
-    if (h.nSpill > qCap || h.nExact > qCap) { sd::set_error("sd_nms2d_old: pair queue overflow (internal error)"); return -1; }
-    if (h.nErr) { sd::set_error("sd_nms2d_old: %u pairs exceeded the general path's fixed capacities", h.nErr); return -1; }
+    if (check_sweep("sd_nms2d_old", h, qCap, false, "")) return -1;
   }
   hipLaunchKernelGGL(k_keep, dim3(sd::div_up(N, 256)), dim3(256), 0, s, state, d_keep, N);
   SD_LAUNCH_CHECK();

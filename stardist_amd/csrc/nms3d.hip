@@ -881,16 +881,6 @@ int cone_map_build(const float* d_verts, const int* d_faces, int F, sd3::ConeMap
 }  // namespace
 
 namespace sd {
-SideJoin::~SideJoin() {
-  if (pending) (void)hipEventSynchronize(done);       // (an error return: the helper stream still writes into the arena)
-  if (fork) (void)hipEventDestroy(fork);
-  if (done) (void)hipEventDestroy(done);
-}
-int SideJoin::join(hipStream_t s) {
-  if (pending) { SD_CHECK(hipStreamWaitEvent(s, done, 0)); pending = false; }
-  return 0;
-}
-
 int hull_planes(const float* d_dist, const float* d_points, const float* d_verts, int n, int R, HullPlanes* out, hipStream_t s) {
   if (R < 4 || R > 800) { sd::set_error("hull_planes: n_rays=%d unsupported (4..800)", R); return -1; }
   const sdl::HullLds lds{R, 2 * R};
@@ -916,15 +906,9 @@ int cone_map(const float* d_verts, const int* d_faces, int F, sd3::ConeMap* out,
   out->list = nullptr; out->count = nullptr;
   if (F > 65535 || sd::option(sd::OPT_NMS3D_CONE_MAP) == 0) return 0;
   hipStream_t side = fork ? sd::side_stream() : nullptr;          // (nullptr: everything stays on the caller's stream)
-  if (side) {
-    SD_CHECK(hipEventCreateWithFlags(&fork->fork, hipEventDisableTiming));
-    SD_CHECK(hipEventCreateWithFlags(&fork->done, hipEventDisableTiming));
-    SD_CHECK(hipEventRecord(fork->fork, s));
-    SD_CHECK(hipStreamWaitEvent(side, fork->fork, 0));
-  }
+  if (side && fork->begin(s, side)) return -1;
   if (cone_map_build(d_verts, d_faces, F, out, side ? side : s)) return -1;
-  if (side) { SD_CHECK(hipEventRecord(fork->done, side)); fork->pending = true; }
-  return 0;
+  return side ? fork->end(side) : 0;
 }
 }  // namespace sd
 
@@ -1027,17 +1011,6 @@ extern "C" int sd_inside_polyhedron_device(const float* d_dist, const float* d_c
 
 // ------------------------------------------------------------------ the driver
 namespace {
-
-// event pair around a stretch of the stream (the stage and broad-phase times of the statistics); does nothing before init()
-struct Timer {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~Timer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  int init() { SD_CHECK(hipEventCreate(&a)); SD_CHECK(hipEventCreate(&b)); return 0; }
-  int start(hipStream_t s) { if (a) SD_CHECK(hipEventRecord(a, s)); return 0; }
-  int stop(hipStream_t s) { if (a) SD_CHECK(hipEventRecord(b, s)); return 0; }
-  int wait() { if (a) SD_CHECK(hipEventSynchronize(b)); return 0; }
-  int ms(float* out) { *out = 0; if (a) SD_CHECK(hipEventElapsedTime(out, a, b)); return 0; }      // after the stream or wait() has reached stop()
-};
 
 struct Mesh { const float* verts; const int* faces; int R, F; };
 struct Counters { int nU, nK, nS; unsigned int nP3, nP4, nP5, nHull, nX3, nX4; };     // (the first three: k_round_triage / k_round_scan)

@@ -12,14 +12,7 @@ namespace sd {
 struct HullPlanes { double* planes; unsigned short* adj; int* count; int cap; };
 int hull_planes(const float* d_dist, const float* d_points, const float* d_verts, int n, int R, HullPlanes* out, hipStream_t s);
 
-// A launch forked onto the helper stream (sd::side_stream()): the caller's stream goes on and joins before it reads the result; the
-// destructor waits for a launch nobody joined (an error return: the helper stream still writes into the arena).
-struct SideJoin {
-  hipEvent_t fork = nullptr, done = nullptr;
-  bool pending = false;
-  ~SideJoin();
-  int join(hipStream_t s);
-};
+struct SideJoin;     // nms_rounds.h
 // Cone map of a ray mesh (geom3d.h); *out stays {nullptr, nullptr} when the map is switched off (sd_set_option("nms3d_cone_map", 0))
 // or the mesh has too many faces for its 16-bit face ids.  fork != nullptr: built on the helper stream, next to what follows on s.
 int cone_map(const float* d_verts, const int* d_faces, int F, sd3::ConeMap* out, hipStream_t s, SideJoin* fork = nullptr);

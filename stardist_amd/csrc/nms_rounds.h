@@ -1,12 +1,43 @@
 // nms_rounds.h -- what the greedy rounds of the 2D and the 3D NMS have in common (nms2d.hip, nms3d.hip): candidate states and wait
 // markers, the small list kernels, the round's triage and list scan, and the host routine that builds the neighbour lists.  The
 // dimension-specific parts stay with their file: the cell grid, k_neighbours / k_neighbours3, the emission and pair kernels and the
-// tail replays.  Everything lives in an anonymous namespace: each translation unit gets its own copy with internal linkage.
+// tail replays.  The drivers' two event holders (Timer, sd::SideJoin) are here as well.  Everything but sd::SideJoin lives in an
+// anonymous namespace: each translation unit gets its own copy with internal linkage.
 #pragma once
 #include "common.h"
 #include <hipcub/hipcub.hpp>
 
+namespace sd {
+// A launch forked onto the helper stream (sd::side_stream()): begin() lets `side` continue behind what `s` holds now, end() marks what
+// `side` holds then, and the caller's stream joins before it reads the result; the destructor waits for a launch nobody joined (an
+// error return: the helper stream still writes into the arena).
+struct SideJoin {
+  hipEvent_t fork = nullptr, done = nullptr;
+  bool pending = false;
+  ~SideJoin() { if (pending) (void)hipEventSynchronize(done); if (fork) (void)hipEventDestroy(fork); if (done) (void)hipEventDestroy(done); }
+  int begin(hipStream_t s, hipStream_t side) {
+    if (!fork) { SD_CHECK(hipEventCreateWithFlags(&fork, hipEventDisableTiming)); SD_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming)); }
+    SD_CHECK(hipEventRecord(fork, s));
+    SD_CHECK(hipStreamWaitEvent(side, fork, 0));
+    return 0;
+  }
+  int end(hipStream_t side) { SD_CHECK(hipEventRecord(done, side)); pending = true; return 0; }
+  int join(hipStream_t s) { if (pending) { SD_CHECK(hipStreamWaitEvent(s, done, 0)); pending = false; } return 0; }
+};
+}  // namespace sd
+
 namespace {
+
+// event pair around a stretch of the stream (the stage and broad-phase times of the statistics); does nothing before init()
+struct Timer {
+  hipEvent_t a = nullptr, b = nullptr;
+  ~Timer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  int init() { SD_CHECK(hipEventCreate(&a)); SD_CHECK(hipEventCreate(&b)); return 0; }
+  int start(hipStream_t s) { if (a) SD_CHECK(hipEventRecord(a, s)); return 0; }
+  int stop(hipStream_t s) { if (a) SD_CHECK(hipEventRecord(b, s)); return 0; }
+  int wait() { if (a) SD_CHECK(hipEventSynchronize(b)); return 0; }
+  int ms(float* out) { *out = 0; if (a) SD_CHECK(hipEventElapsedTime(out, a, b)); return 0; }      // after the stream or wait() has reached stop()
+};
 
 enum { ST_UNDECIDED = 0, ST_KEPT = 1, ST_SUPPRESSED = 2 };
 

@@ -56,6 +56,13 @@ hipStream_t side_stream();
 enum { kMaxDevices = 64 };
 int resident_grid(const void* kernel, int threads, int* cache);
 
+// Persistent-grid launches (one workgroup, or a fixed few, per CU): the CU count of the current device, asked once per device (256
+// where the query reports none); -1 + error set when a HIP call fails.
+int cu_count();
+// Allow the `n` kernels `bytes` of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize) on the current device, once per device:
+// `done` is the caller's record, `done[kMaxDevices]`, zero-initialised, one per set of kernels.  0, or -1 + error set.
+int allow_dynamic_lds(const void* const* kernels, int n, int bytes, bool* done);
+
 static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // Result-preserving switches between equivalent formulations (set through sd_set_option of the C ABI, documented there): the parity

@@ -3,9 +3,9 @@
 // Replaces Keras Conv2D / Conv3D(kernel 3, 'same') + bias + ReLU of the csbdeep unet_block the reference builds in
 // stardist/models/model2d.py:310-349 and model3d.py:360-399 (and the UpSampling + Concatenate in front of the first convolution
 // of an up level):
-//   * k_conv3<NT>: input channels in chunks of 32, each chunk from its own source tensor so that Concatenate([up, skip]) never
+//   * k_conv3: input channels in chunks of 32, each chunk from its own source tensor so that Concatenate([up, skip]) never
 //     exists in memory; a source may be half resolution along any axis = nearest 2x up-sampling folded into the operand fetch;
-//     32*NT output channels per workgroup, bias + activation in the epilogue.  A 3x3x3 convolution is the sum of three z planes
+//     32 output channels per workgroup, bias + activation in the epilogue.  A 3x3x3 convolution is the sum of three z planes
 //     of 3x3 taps: the work list of an output tile is (chunk, kz) "units", each = one halo tile + one 9-tap weight block in LDS.
 //     Layout and k order: conv3x3_layout.h.  Persistent workgroups (one per CU); the next unit's halo tile and weight block are
 //     fetched (tile: into registers, weights: LDS-direct into the second weight buffer) while the matrix cores work on the current one.  Exact float32: every output is ONE fma chain in a fixed order (bias first), so results do not depend on
@@ -13,14 +13,14 @@
 //   * k_conv3_c1: the first layer (1 input channel, K = 9 or 27): HBM-write bound, plain FMAs.
 // Bound: MFMA (f32: 64 FLOP/clk/SIMD); algorithmic bytes 4*(C_in + C_out) per pixel.
 #include "common.h"
-#include "conv3x3_device.h"
+#include "conv3x3_host.h"
 #include "stardist_hip.h"
 
 namespace {
 
 using namespace sdconvdev;
 
-constexpr int WUNIT = 9 * 4 * 2 * 32 * 4;     // floats of one weight block (NT = 1)
+constexpr int WUNIT = WUNIT_FLOATS;            // floats of one weight block
 constexpr int WMAIN = 8 * 4 * 2 * 32 * 4;     // ... of its taps 0..7
 
 // Per-thread staging constants, computed once per kernel: where this thread's PRE_F4 float4 elements of a halo tile live in LDS,
@@ -43,7 +43,6 @@ __device__ __forceinline__ void stage_init(const Params& P, Stage& st, int tid) 
 }
 
 // Halo tile of unit u of output tile t -> registers (halo_fetch), the unit's weight block -> LDS.
-template <int NT>
 __device__ __forceinline__ void load_unit(const Params& P, const Stage& st, int g, int t, int u, v4f (&pre)[PRE_F4], v4f& w8,
                                           float* __restrict__ Wnext, int tid, int wave) {
   halo_fetch(P, st.goff, t, u, pre, tid);
@@ -69,28 +68,20 @@ __device__ __forceinline__ void store_unit(const Stage& st, float* __restrict__ 
     if (n < PRE_F4 - 1 || tid < TILE_F4 - (PRE_F4 - 1) * THREADS) *(v4f*)(tileL + st.lds[n]) = pre[n];
 }
 
-// the two accumulator tiles of a wave as the plain array store_tile takes (NT == 1)
-template <int NT>
-__device__ __forceinline__ const f32x16 (&acc_rows(const f32x16 (&acc)[2][NT]))[2] {
-  static_assert(NT == 1, "");
-  return reinterpret_cast<const f32x16(&)[2]>(acc);
-}
-
 __device__ __forceinline__ float comp(const float4& v, int e) { return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w)); }
 
 // One unit: 12 operand groups (dx, j); a group = the four halo rows the wave's two output rows touch (A) and the three taps dy of
 // that column (B) = 7 ds_read_b128 feeding 24 MFMAs.  The operands of group g+1 are read while the matrix cores work on group g
 // (two register sets).
-template <int NT>
-__device__ __forceinline__ void compute_unit(const float* __restrict__ tileL, const float* __restrict__ wl, const float* __restrict__ w8, f32x16 (&acc)[2][NT],
+__device__ __forceinline__ void compute_unit(const float* __restrict__ tileL, const float* __restrict__ wl, const float* __restrict__ w8, f32x16 (&acc)[2],
                                              int wave, int i, int h) {
-  float4 A[2][4], B[2][3][NT];
+  float4 A[2][4], B[2][3];
 #define SD_LOAD_GROUP(gi, buf)                                                                          \
   do {                                                                                                   \
     const int dx_ = (gi) >> 2, j_ = (gi) & 3;                                                            \
     _Pragma("unroll") for (int rr = 0; rr < 4; ++rr) A[buf][rr] = *(const float4*)(tileL + a_off(wave * 2, rr, dx_, j_, i, h)); \
     _Pragma("unroll") for (int dy = 0; dy < 3; ++dy)                                                     \
-      _Pragma("unroll") for (int ct = 0; ct < NT; ++ct) B[buf][dy][ct] = *(const float4*)((dy * 3 + dx_ == 8 ? w8 - WMAIN : wl) + wl_off(dy * 3 + dx_, j_, h, ct, i, NT)); \
+      B[buf][dy] = *(const float4*)((dy * 3 + dx_ == 8 ? w8 - WMAIN : wl) + wl_off(dy * 3 + dx_, j_, h, i)); \
   } while (0)
   SD_LOAD_GROUP(0, 0);
 #pragma unroll
@@ -101,13 +92,11 @@ __device__ __forceinline__ void compute_unit(const float* __restrict__ tileL, co
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct) {
-          const float bv = comp(B[buf][dy][ct], e);
-          acc[0][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(A[buf][dy], e), bv, acc[0][ct], 0, 0, 0);
-          acc[1][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(A[buf][dy + 1], e), bv, acc[1][ct], 0, 0, 0);
-        }
+      for (int e = 0; e < 4; ++e) {
+        const float bv = comp(B[buf][dy], e);
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(A[buf][dy], e), bv, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(A[buf][dy + 1], e), bv, acc[1], 0, 0, 0);
+      }
     __builtin_amdgcn_sched_barrier(0);
   }
 #undef SD_LOAD_GROUP
@@ -117,21 +106,19 @@ __device__ __forceinline__ void compute_unit(const float* __restrict__ tileL, co
 // matrix cores on the current unit (tile + `wcur`), then move the fetched tile into LDS.  The LDS regions are disjoint; the
 // __restrict__ qualifiers carry that to the waitcnt insertion, which otherwise orders every ds_read behind the in-flight
 // LDS-direct loads (vmcnt(0) in front of the first MFMA group = no overlap).
-template <int NT>
 __device__ __forceinline__ void unit_step(const Params& P, const Stage& st, int g, bool have, int tn, int un, float* __restrict__ tileL,
                                           const float* __restrict__ wcur, const float* __restrict__ w8cur, float* __restrict__ wnext,
-                                          float* __restrict__ w8next, f32x16 (&acc)[2][NT], int tid, int wave, int i, int h) {
+                                          float* __restrict__ w8next, f32x16 (&acc)[2], int tid, int wave, int i, int h) {
   v4f pre[PRE_F4], w8 = {0.f, 0.f, 0.f, 0.f};
-  if (have) load_unit<NT>(P, st, g, tn, un, pre, w8, wnext, tid, wave);
+  if (have) load_unit(P, st, g, tn, un, pre, w8, wnext, tid, wave);
   __builtin_amdgcn_sched_barrier(0);
-  compute_unit<NT>(tileL, wcur, w8cur, acc, wave, i, h);
+  compute_unit(tileL, wcur, w8cur, acc, wave, i, h);
   __syncthreads();
   if (have) store_unit(st, tileL, w8next, pre, w8, tid);
   __syncthreads();
 }
 
 // One workgroup per CU by LDS footprint (120 KiB): one wave per SIMD, so the whole register file is this wave's
-template <int NT>
 __global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(1, 1))) k_conv3(const Params P) {
   extern __shared__ float4 smem4[];
   // LDS map (floats): [0, 2 WMAIN) the two weight buffers' taps 0..7 (DMA destinations, below 64 KiB), then their tap-8 blocks, then the halo tile
@@ -143,38 +130,37 @@ __global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(1,
   int g, q, Q;
   wg_slot(P, g, q, Q);
   if (q >= P.n_tiles) return;
-  float bias_r[NT];
-#pragma unroll
-  for (int ct = 0; ct < NT; ++ct) bias_r[ct] = P.bias ? P.bias[g * 32 * NT + ct * 32 + i] : 0.f;
-  static_assert(NT == 1, "LDS map and weight staging are written for 32 output channels per workgroup");
+  // (a loop of one trip, left from the time the kernel was written for NT tiles of 32 output channels: as a plain initialiser the
+  // compiler encodes the `P.bias ?` branch the other way round and allocates the registers behind it differently -- the same work, but
+  // not the instruction stream that was measured; whoever straightens this line measures the kernel again)
+  float bias_r = 0.f;
+  for (int once = 0; once < 1; ++once) bias_r = P.bias ? P.bias[g * 32 + i] : 0.f;
   Stage st;
   stage_init(P, st, tid);
   {
     v4f pre[PRE_F4], w8;
-    load_unit<NT>(P, st, g, q, 0, pre, w8, Wl, tid, wave);
+    load_unit(P, st, g, q, 0, pre, w8, Wl, tid, wave);
     store_unit(st, tileL, W8, pre, w8, tid);
   }
   __syncthreads();                                     // (the compiler drains the LDS-direct loads before the barrier)
   int wb = 0;
   for (int t = q; t < P.n_tiles; t += Q) {
-    f32x16 acc[2][NT];
+    f32x16 acc[2];
 #pragma unroll
     for (int p = 0; p < 2; ++p)
 #pragma unroll
-      for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[p][ct][r] = bias_r[ct];
+      for (int r = 0; r < 16; ++r) acc[p][r] = bias_r;
     for (int u = 0; u < P.n_units; ++u) {
       const bool last = u == P.n_units - 1;
       const int tn = last ? t + Q : t, un = last ? 0 : u + 1;
-      unit_step<NT>(P, st, g, tn < P.n_tiles, tn, un, tileL, Wl + wb * WMAIN, W8 + wb * (WUNIT - WMAIN), Wl + (wb ^ 1) * WMAIN,
+      unit_step(P, st, g, tn < P.n_tiles, tn, un, tileL, Wl + wb * WMAIN, W8 + wb * (WUNIT - WMAIN), Wl + (wb ^ 1) * WMAIN,
                     W8 + (wb ^ 1) * (WUNIT - WMAIN), acc, tid, wave, i, h);
       wb ^= 1;
     }
     // epilogue (store_tile): scratch = the weight buffer the matrix cores have just finished with (every wave is past the barrier
     // behind that compute); a wave uses exactly the eight 1-KiB chunks n*4 + wave that its own LDS-direct loads refill in the next
     // step, so no barrier is needed -- program order within the wave is enough.  The stores drain while the next tile is computed.
-    store_tile<1024>(P, acc_rows(acc), Wl + (wb ^ 1) * WMAIN + wave * 256, g, t, wave, lane);
+    store_tile<1024>(P, acc, Wl + (wb ^ 1) * WMAIN + wave * 256, g, t, wave, lane);
   }
 }
 
@@ -290,28 +276,16 @@ __global__ void __launch_bounds__(256) k_conv3_c1x32(const float* __restrict__ x
   }
 }
 
-template <int NT>
+constexpr char kForm[] = "sd_conv3_ndhwc";
+
+// one persistent workgroup per CU
 int launch_conv(const Params& P, hipStream_t s) {
-  static bool attr_set[16] = {};
-  static int n_cu[16] = {};
-  int dev = 0;
-  SD_CHECK(hipGetDevice(&dev));
-  const size_t lds = (size_t)(TILE_FLOATS + 2 * wunit_floats(NT)) * sizeof(float);
-  if (dev >= 16 || !attr_set[dev]) {
-    SD_CHECK(hipFuncSetAttribute((const void*)k_conv3<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (dev < 16) attr_set[dev] = true;
-  }
-  int cus = dev < 16 ? n_cu[dev] : 0;
-  if (cus <= 0) {
-    SD_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (cus <= 0) cus = 256;
-    if (dev < 16) n_cu[dev] = cus;
-  }
-  long long blocks = (long long)(cus / P.groups) * P.groups;      // one persistent workgroup per CU, a whole number per group
-  if (blocks < P.groups) blocks = P.groups;
-  const long long want = (long long)P.n_tiles * P.groups;
-  if (blocks > want) blocks = want;
-  hipLaunchKernelGGL((k_conv3<NT>), dim3((unsigned)blocks), dim3(THREADS), lds, s, P);
+  static bool attr_done[sd::kMaxDevices] = {};
+  const void* const kern[] = {(const void*)k_conv3};
+  const size_t lds = (size_t)(TILE_FLOATS + 2 * WUNIT) * sizeof(float);
+  unsigned blocks = 0;
+  if (sdconvhost::persistent_grid(kern, attr_done, lds, P, 1, blocks)) return -1;
+  hipLaunchKernelGGL(k_conv3, dim3(blocks), dim3(THREADS), lds, s, P);
   SD_LAUNCH_CHECK();
   return 0;
 }
@@ -347,11 +321,9 @@ extern "C" int sd_conv3_res_ndhwc_device(const float* d_src0, int c0, int stride
   hipStream_t s = (hipStream_t)stream_;
   if (D <= 0 || H <= 0 || W <= 0) return 0;
   const int c_in = c0 + (d_src1 ? c1 : 0);
-  if (!d_src0 || !d_wpacked || !d_out || (act != 0 && act != 1) || sd_conv3_packed_floats(c_in, c_out, kz) < 0 || (kz == 1 && D != 1) ||
-      (((uintptr_t)d_src0 | (uintptr_t)d_src1 | (uintptr_t)d_wpacked | (uintptr_t)d_out | (uintptr_t)d_bias) & 15)) {
-    sd::set_error("sd_conv3_ndhwc: unsupported channel counts (%d + %d -> %d), kz, act or misaligned pointers", c0, d_src1 ? c1 : 0, c_out);
-    return -1;
-  }
+  const long long n_packed = sd_conv3_packed_floats(c_in, c_out, kz);
+  const sdconvhost::Args a = {{{d_src0, c0, stride0, up0}, {d_src1, c1, stride1, up1}}, D, H, W, kz, d_wpacked, d_bias, d_res, res_stride, c_out, act, d_out};
+  if (sdconvhost::check_args(kForm, a, n_packed)) return -1;      // (the one-channel layer stops before prepare(), which begins with this check)
   if (d_res && (c_in == 1 || res_stride < c_out || (res_stride & 3) || ((uintptr_t)d_res & 15))) {
     sd::set_error("sd_conv3_ndhwc: the residual needs a 32-channel-chunk layer, 16-byte alignment and a stride >= c_out");
     return -1;
@@ -379,39 +351,9 @@ extern "C" int sd_conv3_res_ndhwc_device(const float* d_src0, int c0, int stride
     SD_LAUNCH_CHECK();
     return 0;
   }
-  const int ups[2] = {up0, d_src1 ? up1 : 0};
-  for (int k = 0; k < 2; ++k) {
-    const int up = ups[k];
-    if (up < 0 || up > 7 || ((up & 1) && (W & 1)) || ((up & 2) && (H & 1)) || ((up & 4) && (D & 1))) {
-      sd::set_error("sd_conv3_ndhwc: up is a bit mask (1: x, 2: y, 4: z); an up-sampled axis needs an even output size");
-      return -1;
-    }
-  }
-  if ((c0 % 32) || (d_src1 && (c1 % 32)) || stride0 < c0 || (stride0 & 3) || (d_src1 && (stride1 < c1 || (stride1 & 3)))) {
-    sd::set_error("sd_conv3_ndhwc: sources must hold multiples of 32 channels, strides multiples of 4 floats");
-    return -1;
-  }
   Params P;
-  int nc = 0;
-  P.kind[0] = make_src(d_src0, stride0, up0, H, W);
-  P.kind[1] = d_src1 ? make_src(d_src1, stride1, up1, H, W) : P.kind[0];
-  for (int k = 0; k < MAX_CHUNKS; ++k) { P.chunk_kind[k] = 0; P.chunk_choff[k] = 0; }
-  for (int k = 0; k < c0 / 32; ++k) { P.chunk_kind[nc] = 0; P.chunk_choff[nc++] = k * 32; }
-  if (d_src1) for (int k = 0; k < c1 / 32; ++k) { P.chunk_kind[nc] = 1; P.chunk_choff[nc++] = k * 32; }
-  P.D = D; P.H = H; P.W = W; P.kz = kz; P.n_units = nc * kz; P.n_chunks0 = c0 / 32;
-  P.zero = d_wpacked + sdconv::packed_floats(c_in, c_out, kz);
-  P.res = d_res; P.res_stride = res_stride;
-  P.dotw = nullptr; P.dotp = nullptr;
-  P.wp = d_wpacked; P.bias = d_bias; P.out = d_out; P.c_out = c_out; P.act = act;
-  P.tiles_x = (W + TW - 1) / TW;
-  P.tiles_plane = P.tiles_x * ((H + TH - 1) / TH);
-  const long long nt_ll = (long long)P.tiles_plane * D;
-  if (nt_ll > 0x7fffffffLL) { sd::set_error("sd_conv3_ndhwc: too many tiles"); return -1; }
-  P.n_tiles = (int)nt_ll;
-  const int nt = sdconv::nt_for(c_out);
-  P.groups = c_out / (32 * nt);
-  (void)nt;
-  return launch_conv<1>(P, s);
+  if (sdconvhost::prepare(kForm, a, n_packed, P)) return -1;
+  return launch_conv(P, s);
 }
 
 // first layer (one input channel -> 32) with the output written as a split16 tensor: what sd_conv3_f16x3_fmt_ndhwc_device reads with in_split16

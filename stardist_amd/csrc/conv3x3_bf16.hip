@@ -1,6 +1,6 @@
 // conv3x3_bf16.hip -- the 3x3 / 3x3x3 convolution of conv3x3.hip with every f32 product evaluated as six bf16 x bf16 products on
-// v_mfma_f32_32x32x16_bf16 (f32 accumulation).  The network's default kernel (models/unet.py conv_mode(); STARDIST_AMD_CONV=hand
-// selects the exact-f32 kernel of conv3x3.hip).
+// v_mfma_f32_32x32x16_bf16 (f32 accumulation).  No range limit: the form the network is re-evaluated with when the default f16x3 form
+// (conv3x3_f16.hip) meets a value outside the fp16 range; STARDIST_AMD_CONV=bf16x6 selects it outright (models/native_layers.py conv_mode()).
 //
 // Why: the exact kernel runs at the f32-MFMA roof (conv3x3.hip: 116-122 TFLOP/s of a 157 spec / ~126 sustained), and bf16 MFMA is
 // 16x that rate.  With x = hi + mid + lo (three bf16 terms, the remainders exact in f32) the six leading cross products reproduce the
@@ -26,25 +26,11 @@
 #include <stdlib.h>
 
 #include "common.h"
-#include "conv3x3_device.h"
+#include "conv3x3_host.h"
 #include "stardist_hip.h"
 
-// phase timing for tools/conv_phase_profile.hip (never defined in the library build)
-#ifdef SD_CONV_PROFILE
-__device__ unsigned long long g_conv_prof[16];   // [0] total, [1..14] phases, [15] units
-#define PROF_DECL unsigned long long pf_t = __builtin_amdgcn_s_memtime(), pf_acc[14] = {}; const unsigned long long pf_t0 = pf_t; unsigned long long pf_units = 0
-#define PROF(k) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); pf_acc[k] += n_ - pf_t; pf_t = n_; } while (0)
-#define PROF_UNIT() (++pf_units)
-#define PROF_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define PROF_END() do { if (threadIdx.x == 0) { atomicAdd(&g_conv_prof[0], __builtin_amdgcn_s_memtime() - pf_t0); \
-  for (int k_ = 0; k_ < 14; ++k_) atomicAdd(&g_conv_prof[1 + k_], pf_acc[k_]); atomicAdd(&g_conv_prof[15], pf_units); } } while (0)
-#else
-#define PROF_DECL
-#define PROF(k)
-#define PROF_UNIT()
-#define PROF_DRAIN()
-#define PROF_END()
-#endif
+#define SD_CONV_PROF_PHASES 14      // tools/conv_phase_profile.hip
+#include "conv3x3_profile.h"
 
 namespace {
 
@@ -320,67 +306,16 @@ extern "C" int sd_conv3_bf16x6_res_ndhwc_device(const float* d_src0, int c0, int
                                                 const float* d_res, int res_stride, int c_out, int act, float* d_out, void* stream_) {
   hipStream_t s = (hipStream_t)stream_;
   if (D <= 0 || H <= 0 || W <= 0) return 0;
-  const int c_in = c0 + (d_src1 ? c1 : 0);
-  const long long n_packed = sd_conv3_bf16x6_packed_floats(c_in, c_out, kz);
-  if (!d_src0 || !d_wpacked || !d_out || (act != 0 && act != 1) || n_packed < 0 || (kz == 1 && D != 1) ||
-      (((uintptr_t)d_src0 | (uintptr_t)d_src1 | (uintptr_t)d_wpacked | (uintptr_t)d_out | (uintptr_t)d_bias) & 15)) {
-    sd::set_error("sd_conv3_bf16x6: unsupported channel counts (%d + %d -> %d), kz, act or misaligned pointers", c0, d_src1 ? c1 : 0, c_out);
-    return -1;
-  }
-  const int ups[2] = {up0, d_src1 ? up1 : 0};
-  for (int k = 0; k < 2; ++k)
-    if (ups[k] < 0 || ups[k] > 7 || ((ups[k] & 1) && (W & 1)) || ((ups[k] & 2) && (H & 1)) || ((ups[k] & 4) && (D & 1))) {
-      sd::set_error("sd_conv3_bf16x6: up is a bit mask (1: x, 2: y, 4: z); an up-sampled axis needs an even output size");
-      return -1;
-    }
-  if ((c0 % 32) || (d_src1 && (c1 % 32)) || stride0 < c0 || (stride0 & 3) || (d_src1 && (stride1 < c1 || (stride1 & 3)))) {
-    sd::set_error("sd_conv3_bf16x6: sources must hold multiples of 32 channels, strides multiples of 4 floats");
-    return -1;
-  }
+  const sdconvhost::Args a = {{{d_src0, c0, stride0, up0}, {d_src1, c1, stride1, up1}}, D, H, W, kz, d_wpacked, d_bias, d_res, res_stride, c_out, act, d_out};
   Params P;
-  int nc = 0;
-  P.kind[0] = make_src(d_src0, stride0, up0, H, W);
-  P.kind[1] = d_src1 ? make_src(d_src1, stride1, up1, H, W) : P.kind[0];
-  for (int k = 0; k < MAX_CHUNKS; ++k) { P.chunk_kind[k] = 0; P.chunk_choff[k] = 0; }
-  for (int k = 0; k < c0 / 32; ++k) { P.chunk_kind[nc] = 0; P.chunk_choff[nc++] = k * 32; }
-  if (d_src1) for (int k = 0; k < c1 / 32; ++k) { P.chunk_kind[nc] = 1; P.chunk_choff[nc++] = k * 32; }
-  P.D = D; P.H = H; P.W = W; P.kz = kz; P.n_units = nc * kz; P.n_chunks0 = c0 / 32;
-  P.zero = d_wpacked + (n_packed - 4);
-  if (d_res && (res_stride < c_out || (res_stride & 3) || ((uintptr_t)d_res & 15))) {
-    sd::set_error("sd_conv3_bf16x6: the residual needs 16-byte alignment and a stride >= c_out");
-    return -1;
-  }
-  P.res = d_res; P.res_stride = res_stride;
-  P.dotw = nullptr; P.dotp = nullptr;
-  P.wp = d_wpacked; P.bias = d_bias; P.out = d_out; P.c_out = c_out; P.act = act;
-  P.tiles_x = (W + TW - 1) / TW;
-  P.tiles_plane = P.tiles_x * ((H + TH - 1) / TH);
-  const long long nt_ll = (long long)P.tiles_plane * D;
-  if (nt_ll > 0x7fffffffLL) { sd::set_error("sd_conv3_bf16x6: too many tiles"); return -1; }
-  P.n_tiles = (int)nt_ll;
-  P.groups = c_out / 32;
-  static bool attr_set[16] = {};
-  static int n_cu[16] = {};
-  int dev = 0;
-  SD_CHECK(hipGetDevice(&dev));
-  const size_t lds = (size_t)2 * BWSUB_BYTES + BTILE_BYTES + 4 * 8192;     // 137 KiB
-  if (dev >= 16 || !attr_set[dev]) {
-    SD_CHECK(hipFuncSetAttribute((const void*)k_conv3_bf16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SD_CHECK(hipFuncSetAttribute((const void*)k_conv3_bf16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (dev < 16) attr_set[dev] = true;
-  }
-  int cus = dev < 16 ? n_cu[dev] : 0;
-  if (cus <= 0) {
-    SD_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (cus <= 0) cus = 256;
-    if (dev < 16) n_cu[dev] = cus;
-  }
-  long long blocks = (long long)(cus / P.groups) * P.groups;
-  if (blocks < P.groups) blocks = P.groups;
-  const long long want = (long long)P.n_tiles * P.groups;
-  if (blocks > want) blocks = want;
-  if (d_res) hipLaunchKernelGGL(k_conv3_bf16<true>, dim3((unsigned)blocks), dim3(THREADS), lds, s, P);
-  else hipLaunchKernelGGL(k_conv3_bf16<false>, dim3((unsigned)blocks), dim3(THREADS), lds, s, P);
+  if (sdconvhost::prepare("sd_conv3_bf16x6", a, sd_conv3_bf16x6_packed_floats(c0 + (d_src1 ? c1 : 0), c_out, kz), P)) return -1;
+  static bool attr_done[sd::kMaxDevices] = {};
+  const void* const kern[] = {(const void*)k_conv3_bf16<false>, (const void*)k_conv3_bf16<true>};
+  const size_t lds = (size_t)2 * BWSUB_BYTES + BTILE_BYTES + 4 * 8192;     // 137 KiB: one workgroup per CU
+  unsigned blocks = 0;
+  if (sdconvhost::persistent_grid(kern, attr_done, lds, P, 1, blocks)) return -1;
+  if (d_res) hipLaunchKernelGGL(k_conv3_bf16<true>, dim3(blocks), dim3(THREADS), lds, s, P);
+  else hipLaunchKernelGGL(k_conv3_bf16<false>, dim3(blocks), dim3(THREADS), lds, s, P);
   SD_LAUNCH_CHECK();
   return 0;
 }

@@ -1,5 +1,6 @@
-// conv3x3_device.h -- device-side pieces shared by the two convolution kernels (conv3x3.hip: exact f32 MFMA; conv3x3_bf16.hip:
-// split-bf16 MFMA): the launch descriptor, the workgroup -> (output-channel group, tile slot) map, and the halo fetch.
+// conv3x3_device.h -- device-side pieces shared by the three forms of the convolution (conv3x3.hip: exact f32 MFMA; conv3x3_bf16.hip:
+// split-bf16 MFMA; conv3x3_f16.hip: split-fp16 MFMA): the launch descriptor (filled by conv3x3_host.h), the workgroup ->
+// (output-channel group, tile slot) map, the halo fetch and the transposed epilogue.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -148,6 +149,8 @@ struct TileWalk {
   int sz, srow, scol;        // digits of the step Q
   int tiles_y;
 };
+// (the same record as tile_addr's from the walk's position.  Not one function: with tile_addr calling this one the compiler orders two
+// scalar instructions of k_conv3_bf16 differently)
 __device__ __forceinline__ void tile_at(const Params& P, const TileWalk& w, TileAddr& T) {
   T.tz = w.tz;
   T.ty0 = w.row * TH - 1;

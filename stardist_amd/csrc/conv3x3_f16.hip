@@ -21,30 +21,11 @@
 #include <stdlib.h>
 
 #include "common.h"
-#include "conv3x3_device.h"
+#include "conv3x3_host.h"
 #include "stardist_hip.h"
 
-#ifdef SD_CONV_PROFILE
-__device__ unsigned long long g_conv_prof[20];   // [0] total, [1..16] phases, [19] units
-#define PROF_DECL unsigned long long pf_t = __builtin_amdgcn_s_memtime(), pf_acc[16] = {}; const unsigned long long pf_t0 = pf_t; unsigned long long pf_units = 0
-#define PROF(k) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); pf_acc[k] += n_ - pf_t; pf_t = n_; } while (0)
-#define PROF_UNIT() (++pf_units)
-#define PROF_END() do { if (threadIdx.x == 0) { atomicAdd(&g_conv_prof[0], __builtin_amdgcn_s_memtime() - pf_t0); \
-  for (int k_ = 0; k_ < 16; ++k_) atomicAdd(&g_conv_prof[1 + k_], pf_acc[k_]); atomicAdd(&g_conv_prof[19], pf_units); } } while (0)
-#else
-#define PROF_DECL
-#define PROF(k)
-#define PROF_UNIT()
-#define PROF_END()
-#endif
-
-// Build-time experiment switches (tools/build_variant.sh): bit 0 = per-thread halo offsets precomputed per source tensor and an
-// interior-tile fast path (split16 sources only: their staging keeps no split registers, so the 22 offsets fit)
-// bit 1 = matrix instructions issued so that consecutive ones never share an accumulator
-// bits 2, 3 = ENERGY PROBES, wrong results: only the first two operand groups of a sub-unit read their A (bit 2) / B (bit 3) operands from LDS
-#ifndef SD_CONV_EXP
-#define SD_CONV_EXP 3
-#endif
+#define SD_CONV_PROF_PHASES 16      // tools/conv_f16_phase_profile.hip
+#include "conv3x3_profile.h"
 
 namespace {
 
@@ -223,13 +204,9 @@ __device__ __forceinline__ void compute_sub(const char* __restrict__ tileH, cons
 #define SD_LOAD_GROUP_H(gi, buf)                                                                                        \
   do {                                                                                                                   \
     const int dx_ = (gi) >> 1, b_ = (gi) & 1;                                                                            \
-    if (!(SD_CONV_EXP & 4) || (gi) < 2) {                                                                               \
     _Pragma("unroll") for (int p = 0; p < 2; ++p)                                                                        \
       _Pragma("unroll") for (int pl = 0; pl < 2; ++pl) A[buf][p][pl] = *(const u32x4*)(arow + htile_off(p, i + dx_, pl, b_, h)); \
-    }                                                                                                                    \
-    if (!(SD_CONV_EXP & 8) || (gi) < 2) {                                                                               \
     _Pragma("unroll") for (int pl = 0; pl < 2; ++pl) B[buf][pl] = *(const u32x4*)(w + hw_off(dx_, b_, pl, h, i));        \
-    }                                                                                                                    \
   } while (0)
   SD_LOAD_GROUP_H(0, 0);
 #pragma unroll
@@ -245,21 +222,12 @@ __device__ __forceinline__ void compute_sub(const char* __restrict__ tileH, cons
     {
       const f16x8 a0h = __builtin_bit_cast(f16x8, A[buf][0][0]), a0l = __builtin_bit_cast(f16x8, A[buf][0][1]);
       const f16x8 a1h = __builtin_bit_cast(f16x8, A[buf][1][0]), a1l = __builtin_bit_cast(f16x8, A[buf][1][1]);
-#if SD_CONV_EXP & 2
       acc1[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, bl, acc1[0], 0, 0, 0);
       acc1[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, bl, acc1[1], 0, 0, 0);
       acc0[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, bh, acc0[0], 0, 0, 0);
       acc1[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0l, bh, acc1[0], 0, 0, 0);
       acc1[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1l, bh, acc1[1], 0, 0, 0);
       acc0[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, bh, acc0[1], 0, 0, 0);
-#else
-      acc1[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, bl, acc1[0], 0, 0, 0);
-      acc1[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0l, bh, acc1[0], 0, 0, 0);
-      acc0[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, bh, acc0[0], 0, 0, 0);
-      acc1[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, bl, acc1[1], 0, 0, 0);
-      acc1[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1l, bh, acc1[1], 0, 0, 0);
-      acc0[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, bh, acc0[1], 0, 0, 0);
-#endif
     }
     if (NV > 0 || NLD > 0) {
 #pragma unroll
@@ -408,7 +376,8 @@ __global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(WP
   const unsigned q4off = (unsigned)(tid & 7) * 16u;
   // split16 sources: the element offsets relative to the halo's first source pixel depend on the source tensor only (resolution flags,
   // strides), not on the tile -- kept per thread for both tensors; a tile whose halo lies inside the image then needs one select per element
-  constexpr bool PREOFF = INP && (SD_CONV_EXP & 1);
+  // (only there: the staging of split16 sources keeps no split registers, so the 22 offsets fit)
+  constexpr bool PREOFF = INP;
   unsigned offk[PREOFF ? 2 : 1][PREOFF ? PRE_F4 : 1];
   if constexpr (PREOFF) {
 #pragma unroll
@@ -699,6 +668,20 @@ extern "C" int sd_conv3_f16x3_pack_weights_host(const float* w, int c_in, int c_
   return 0;
 }
 
+// The kernel instances, by their properties: 9 layer forms x {two, one} workgroups per CU
+enum : unsigned { V_RES = 1, V_DOT = 2, V_IN = 4, V_OUT = 8, V_NOST = 16 };      // residual, fused head, split16 in, split16 out, head without the tile store
+typedef void (*kern_t)(const Params);
+struct Variant {
+  unsigned props;
+  kern_t kern[2];      // [one workgroup per CU]
+};
+template <unsigned V>
+static Variant variant() {      // (an impossible combination does not compile: k_conv3_f16's static_asserts)
+  return {V, {k_conv3_f16<(V & V_RES) != 0, 2, (V & V_DOT) != 0, (V & V_IN) != 0, (V & V_OUT) != 0, (V & V_NOST) != 0>,
+              k_conv3_f16<(V & V_RES) != 0, 1, (V & V_DOT) != 0, (V & V_IN) != 0, (V & V_OUT) != 0, (V & V_NOST) != 0>}};
+}
+constexpr int N_VARIANTS = 9;
+
 static int conv3_f16x3_launch(const float* d_src0, int c0, int stride0, int up0, const float* d_src1, int c1, int stride1,
                               int up1, int D, int H, int W, int kz, const float* d_wpacked, const float* d_bias,
                               const float* d_res, int res_stride, int c_out, int act, float* d_out, int* d_range_flag,
@@ -711,49 +694,16 @@ static int conv3_f16x3_launch(const float* d_src0, int c0, int stride0, int up0,
     return -1;
   }
   if (D <= 0 || H <= 0 || W <= 0) return 0;
-  const int c_in = c0 + (d_src1 ? c1 : 0);
-  const long long n_packed = sd_conv3_f16x3_packed_floats(c_in, c_out, kz);
-  if (!d_src0 || !d_wpacked || (!d_out && !no_store) || (act != 0 && act != 1) || n_packed < 0 || (kz == 1 && D != 1) ||
-      (((uintptr_t)d_src0 | (uintptr_t)d_src1 | (uintptr_t)d_wpacked | (uintptr_t)d_out | (uintptr_t)d_bias) & 15) || ((uintptr_t)d_range_flag & 3)) {
-    sd::set_error("sd_conv3_f16x3: unsupported channel counts (%d + %d -> %d), kz, act or misaligned pointers", c0, d_src1 ? c1 : 0, c_out);
-    return -1;
-  }
-  const int ups[2] = {up0, d_src1 ? up1 : 0};
-  for (int k = 0; k < 2; ++k)
-    if (ups[k] < 0 || ups[k] > 7 || ((ups[k] & 1) && (W & 1)) || ((ups[k] & 2) && (H & 1)) || ((ups[k] & 4) && (D & 1))) {
-      sd::set_error("sd_conv3_f16x3: up is a bit mask (1: x, 2: y, 4: z); an up-sampled axis needs an even output size");
-      return -1;
-    }
-  if ((c0 % 32) || (d_src1 && (c1 % 32)) || stride0 < c0 || (stride0 & 3) || (d_src1 && (stride1 < c1 || (stride1 & 3)))) {
-    sd::set_error("sd_conv3_f16x3: sources must hold multiples of 32 channels, strides multiples of 4 floats");
-    return -1;
-  }
+  const sdconvhost::Args a = {{{d_src0, c0, stride0, up0}, {d_src1, c1, stride1, up1}}, D, H, W, kz, d_wpacked, d_bias, d_res, res_stride, c_out, act, d_out,
+                              d_range_flag, no_store};
   Params P;
-  int nc = 0;
-  P.kind[0] = make_src(d_src0, stride0, up0, H, W);
-  P.kind[1] = d_src1 ? make_src(d_src1, stride1, up1, H, W) : P.kind[0];
-  for (int k = 0; k < MAX_CHUNKS; ++k) { P.chunk_kind[k] = 0; P.chunk_choff[k] = 0; }
-  for (int k = 0; k < c0 / 32; ++k) { P.chunk_kind[nc] = 0; P.chunk_choff[nc++] = k * 32; }
-  if (d_src1) for (int k = 0; k < c1 / 32; ++k) { P.chunk_kind[nc] = 1; P.chunk_choff[nc++] = k * 32; }
-  P.D = D; P.H = H; P.W = W; P.kz = kz; P.n_units = nc * kz; P.n_chunks0 = c0 / 32;
-  P.zero = d_wpacked + (n_packed - 4);
-  if (d_res && (res_stride < c_out || (res_stride & 3) || ((uintptr_t)d_res & 15))) {
-    sd::set_error("sd_conv3_f16x3: the residual needs 16-byte alignment and a stride >= c_out");
-    return -1;
-  }
-  P.res = d_res; P.res_stride = res_stride;
-  P.wp = d_wpacked; P.bias = d_bias; P.out = d_out; P.c_out = c_out; P.act = act;
-  P.flag = d_range_flag;
+  if (sdconvhost::prepare("sd_conv3_f16x3", a, sd_conv3_f16x3_packed_floats(c0 + (d_src1 ? c1 : 0), c_out, kz), P)) return -1;
   if ((d_dot_w != nullptr) != (d_dot_partial != nullptr) || (d_dot_w && d_res) || ((uintptr_t)d_dot_w & 15) || ((uintptr_t)d_dot_partial & 3) ||
       (d_dot_w && (long long)W * c_out >= 0x7fffffffLL)) {
     sd::set_error("sd_conv3_f16x3: the fused head needs both its weights (16-byte aligned) and its partial-sum buffer, and no residual");
     return -1;
   }
   P.dotw = d_dot_w; P.dotp = d_dot_partial;
-  P.tiles_x = (W + TW - 1) / TW;
-  P.tiles_plane = P.tiles_x * ((H + TH - 1) / TH);
-  const long long nt_ll = (long long)P.tiles_plane * D;
-  if (nt_ll > 0x7fffffffLL) { sd::set_error("sd_conv3_f16x3: too many tiles"); return -1; }
   // 32-bit offsets inside one halo tile's rows (buffer loads) and inside one output row (buffer stores)
   const long long row0 = (long long)(W >> (up0 & 1)) * stride0 * 4, row1 = d_src1 ? (long long)(W >> (up1 & 1)) * stride1 * 4 : 0;
   if ((HALO_H + 1) * (row0 > row1 ? row0 : row1) >= 0x7fffffffLL || (long long)W * c_out * 4 >= 0x7fffffffLL ||
@@ -761,43 +711,29 @@ static int conv3_f16x3_launch(const float* d_src0, int c0, int stride0, int up0,
     sd::set_error("sd_conv3_f16x3: an image row of %d pixels is too long for 32-bit offsets", W);
     return -1;
   }
-  P.n_tiles = (int)nt_ll;
-  P.groups = c_out / 32;
-  static bool attr_set[16] = {};
-  static int n_cu[16] = {};
-  int dev = 0;
-  SD_CHECK(hipGetDevice(&dev));
+  static const Variant variants[N_VARIANTS] = {variant<0>(),                     // plain
+                                               variant<V_RES>(),
+                                               variant<V_DOT>(),
+                                               variant<V_IN>(),
+                                               variant<V_OUT>(),
+                                               variant<V_IN | V_OUT>(),
+                                               variant<V_IN | V_DOT>(),
+                                               variant<V_DOT | V_NOST>(),
+                                               variant<V_IN | V_DOT | V_NOST>()};
+  const unsigned props = (d_res ? V_RES : 0u) | (d_dot_w ? V_DOT : 0u) | (in_split ? V_IN : 0u) | (out_split ? V_OUT : 0u) | (no_store ? V_NOST : 0u);
+  const Variant* v = nullptr;
+  const void* all[2 * N_VARIANTS];
+  for (int k = 0; k < N_VARIANTS; ++k) {
+    if (variants[k].props == props) v = &variants[k];
+    all[2 * k] = (const void*)variants[k].kern[0]; all[2 * k + 1] = (const void*)variants[k].kern[1];
+  }
+  if (!v) { sd::set_error("sd_conv3_f16x3: no kernel instance with properties 0x%x", props); return -1; }    // (the checks above leave the nine)
+  static bool attr_done[sd::kMaxDevices] = {};
   const size_t lds = (size_t)2 * HWSUB_BYTES + HTILE_BYTES + 4 * 2048 + 128;    // 79.9 KiB: two workgroups per CU (the last 128 bytes: the fused head's weights)
-  typedef void (*kern_t)(const Params);
-  // [variant][one workgroup per CU]: plain, residual, fused head; then the split16 forms (in, out, in + out, in + fused head)
-  static const kern_t kern[9][2] = {
-      {k_conv3_f16<false, 2>, k_conv3_f16<false, 1>},
-      {k_conv3_f16<true, 2>, k_conv3_f16<true, 1>},
-      {k_conv3_f16<false, 2, true>, k_conv3_f16<false, 1, true>},
-      {k_conv3_f16<false, 2, false, true, false>, k_conv3_f16<false, 1, false, true, false>},
-      {k_conv3_f16<false, 2, false, false, true>, k_conv3_f16<false, 1, false, false, true>},
-      {k_conv3_f16<false, 2, false, true, true>, k_conv3_f16<false, 1, false, true, true>},
-      {k_conv3_f16<false, 2, true, true, false>, k_conv3_f16<false, 1, true, true, false>},
-      {k_conv3_f16<false, 2, true, false, false, true>, k_conv3_f16<false, 1, true, false, false, true>},
-      {k_conv3_f16<false, 2, true, true, false, true>, k_conv3_f16<false, 1, true, true, false, true>}};
-  if (dev >= 16 || !attr_set[dev]) {
-    for (int v = 0; v < 9; ++v)
-      for (int w = 0; w < 2; ++w) SD_CHECK(hipFuncSetAttribute((const void*)kern[v][w], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (dev < 16) attr_set[dev] = true;
-  }
-  int cus = dev < 16 ? n_cu[dev] : 0;
-  if (cus <= 0) {
-    SD_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (cus <= 0) cus = 256;
-    if (dev < 16) n_cu[dev] = cus;
-  }
   const int per_cu = sd::option(sd::OPT_CONV_F16_WGS) == 1 ? 1 : 2;          // (1: A/B probe of the one-workgroup-per-CU launch)
-  long long blocks = (long long)(per_cu * cus / P.groups) * P.groups;
-  if (blocks < P.groups) blocks = P.groups;
-  const long long want = (long long)P.n_tiles * P.groups;
-  if (blocks > want) blocks = want;
-  const int variant = d_dot_w ? ((in_split ? 6 : 2) + (no_store ? (in_split ? 2 : 5) : 0)) : d_res ? 1 : (in_split ? (out_split ? 5 : 3) : (out_split ? 4 : 0));
-  hipLaunchKernelGGL(kern[variant][per_cu == 1 ? 1 : 0], dim3((unsigned)blocks), dim3(THREADS), lds, s, P);
+  unsigned blocks = 0;
+  if (sdconvhost::persistent_grid(all, attr_done, lds, P, per_cu, blocks)) return -1;
+  hipLaunchKernelGGL(v->kern[per_cu == 1 ? 1 : 0], dim3(blocks), dim3(THREADS), lds, s, P);
   SD_LAUNCH_CHECK();
   return 0;
 }

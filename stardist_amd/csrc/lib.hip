@@ -60,6 +60,34 @@ int resident_grid(const void* kernel, int threads, int* cache) {
   return cache[d];
 }
 
+// (a device number beyond kMaxDevices is served without the record: asked, or set, on every call)
+int cu_count() {
+  static std::mutex mu;
+  static int n_cu[kMaxDevices] = {};
+  int d = 0;
+  SD_CHECK(hipGetDevice(&d));
+  const bool kept = d >= 0 && d < kMaxDevices;
+  std::lock_guard<std::mutex> lock(mu);
+  if (kept && n_cu[d] > 0) return n_cu[d];
+  int cus = 0;
+  SD_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d));
+  if (cus <= 0) cus = 256;
+  if (kept) n_cu[d] = cus;
+  return cus;
+}
+
+int allow_dynamic_lds(const void* const* kernels, int n, int bytes, bool* done) {
+  static std::mutex mu;
+  int d = 0;
+  SD_CHECK(hipGetDevice(&d));
+  const bool kept = d >= 0 && d < kMaxDevices;
+  std::lock_guard<std::mutex> lock(mu);
+  if (kept && done[d]) return 0;
+  for (int k = 0; k < n; ++k) SD_CHECK(hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  if (kept) done[d] = true;
+  return 0;
+}
+
 size_t Arena::capacity() const { size_t t = 0; for (int i = 0; i < n_; ++i) t += cap_[i]; return t; }
 int Arena::begin(hipStream_t stream) {
   if (n_ > 1) {

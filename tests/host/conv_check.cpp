@@ -19,12 +19,12 @@ static float frand() { return (float)rand() / RAND_MAX * 2.f - 1.f; }
 // one output tile of one output-channel group, emulating a workgroup
 static void emulate_tile(const SrcH* src, int n_chunks, int kz, int g, int D, int H, int W, const float* wp, const float* bias, int c_out, int act,
                          int t, int tiles_x, int tiles_plane, float* out) {
-  const int nt = nt_for(c_out), n_units = n_chunks * kz;
-  std::vector<float> tileL(TILE_FLOATS), Wl(wunit_floats(nt));
-  std::vector<float> acc((size_t)4 * 2 * nt * 64 * 16);
-  auto A = [&](int wave, int p, int ct, int lane, int r) -> float& { return acc[((((size_t)wave * 2 + p) * nt + ct) * 64 + lane) * 16 + r]; };
-  for (int wave = 0; wave < 4; ++wave) for (int p = 0; p < 2; ++p) for (int ct = 0; ct < nt; ++ct) for (int lane = 0; lane < 64; ++lane)
-    for (int r = 0; r < 16; ++r) A(wave, p, ct, lane, r) = bias ? bias[g * 32 * nt + ct * 32 + (lane & 31)] : 0.f;
+  const int n_units = n_chunks * kz;
+  std::vector<float> tileL(TILE_FLOATS), Wl(WUNIT_FLOATS);
+  std::vector<float> acc((size_t)4 * 2 * 64 * 16);
+  auto A = [&](int wave, int p, int lane, int r) -> float& { return acc[(((size_t)wave * 2 + p) * 64 + lane) * 16 + r]; };
+  for (int wave = 0; wave < 4; ++wave) for (int p = 0; p < 2; ++p) for (int lane = 0; lane < 64; ++lane)
+    for (int r = 0; r < 16; ++r) A(wave, p, lane, r) = bias ? bias[g * 32 + (lane & 31)] : 0.f;
   const int tz = t / tiles_plane, tr = t - tz * tiles_plane;
   const int ty0 = (tr / tiles_x) * TH - 1, tx0 = (tr % tiles_x) * TW - 1;
   for (int u = 0; u < n_units; ++u) {
@@ -45,30 +45,29 @@ static void emulate_tile(const SrcH* src, int n_chunks, int kz, int g, int D, in
         tileL[tile_off(ty, tx, q4 * 4) + k] = v;
       }
     }
-    for (int e = 0; e < wunit_floats(nt); ++e) Wl[e] = wp[((size_t)g * n_units + u) * wunit_floats(nt) + e];     // linear copy (LDS-direct)
+    for (int e = 0; e < WUNIT_FLOATS; ++e) Wl[e] = wp[((size_t)g * n_units + u) * WUNIT_FLOATS + e];     // linear copy (LDS-direct)
     const float* wl = Wl.data();
     for (int wave = 0; wave < 4; ++wave)
       for (int gi = 0; gi < 12; ++gi) {
         const int dx = gi >> 2, j = gi & 3;
         for (int dy = 0; dy < 3; ++dy)
           for (int e = 0; e < 4; ++e)
-            for (int ct = 0; ct < nt; ++ct)
-              for (int p = 0; p < 2; ++p) {
+            for (int p = 0; p < 2; ++p) {
                 // D[m][n] = fma(A[m][1], B[1][n], fma(A[m][0], B[0][n], C[m][n])); lane (i, h): a = A[i][h], b = B[h][i]
                 float a[64], b[64];
                 for (int lane = 0; lane < 64; ++lane) {
                   const int i = lane & 31, h = lane >> 5;
                   a[lane] = tileL[a_off(wave * 2, dy + p, dx, j, i, h) + e];
-                  b[lane] = wl[wl_off(dy * 3 + dx, j, h, ct, i, nt) + e];
+                  b[lane] = wl[wl_off(dy * 3 + dx, j, h, i) + e];
                 }
                 for (int lane = 0; lane < 64; ++lane) {
                   const int n = lane & 31, h = lane >> 5;
                   for (int r = 0; r < 16; ++r) {
                     const int m = acc_col(r, h);
-                    float v = A(wave, p, ct, lane, r);
+                    float v = A(wave, p, lane, r);
                     v = fmaf(a[m], b[n], v);
                     v = fmaf(a[32 + m], b[32 + n], v);
-                    A(wave, p, ct, lane, r) = v;
+                    A(wave, p, lane, r) = v;
                   }
                 }
               }
@@ -78,11 +77,11 @@ static void emulate_tile(const SrcH* src, int n_chunks, int kz, int g, int D, in
   for (int wave = 0; wave < 4; ++wave) for (int p = 0; p < 2; ++p) {
     const int y = (tr / tiles_x) * TH + wave * 2 + p;
     if (y >= H) continue;
-    for (int ct = 0; ct < nt; ++ct) for (int lane = 0; lane < 64; ++lane) for (int r = 0; r < 16; ++r) {
+    for (int lane = 0; lane < 64; ++lane) for (int r = 0; r < 16; ++r) {
       const int x = x0 + acc_col(r, lane >> 5);
-      float v = A(wave, p, ct, lane, r);
+      float v = A(wave, p, lane, r);
       if (act == 1) v = fmaxf(v, 0.f);
-      if (x < W) out[(((size_t)tz * H + y) * W + x) * c_out + g * 32 * nt + ct * 32 + (lane & 31)] = v;
+      if (x < W) out[(((size_t)tz * H + y) * W + x) * c_out + g * 32 + (lane & 31)] = v;
     }
   }
 }
@@ -179,7 +178,7 @@ static int run_case(int D, int H, int W, int kz, int c0, int up0, int c1, int up
   SrcH src[MAX_CHUNKS]; int nc = 0;
   for (int k = 0; k < c0 / 32; ++k) src[nc++] = SrcH{s0.data() + k * 32, c0, sh(up0, 2), sh(up0, 1), sh(up0, 0)};
   for (int k = 0; k < c1 / 32; ++k) src[nc++] = SrcH{s1.data() + k * 32, c1, sh(up1, 2), sh(up1, 1), sh(up1, 0)};
-  const int nt = nt_for(c_out), groups = c_out / (32 * nt);
+  const int groups = c_out / 32;
   const int tiles_x = (W + TW - 1) / TW, tiles_plane = tiles_x * ((H + TH - 1) / TH), n_tiles = tiles_plane * D;
   std::vector<float> out((size_t)D * H * W * c_out, NAN), outb((size_t)D * H * W * c_out, NAN);
   std::vector<unsigned short> wpb(bpacked_bytes(c_in, c_out, kz) / 2);

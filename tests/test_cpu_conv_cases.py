@@ -1,5 +1,5 @@
 """CPU: the case lists of test_gpu_conv_exact.py (_conv_cases.py) reach the regimes they were chosen for -- from the partition of the
-3x3 kernels restated there (conv3x3_layout.h constants, the launch code of conv3x3_f16.hip / conv3x3_bf16.hip) -- and the exactness
+3x3 kernels restated there (conv3x3_layout.h constants, the launch code of conv3x3_host.h) -- and the exactness
 preconditions of its two data families hold on the CPU references alone."""
 import os
 import re
@@ -19,9 +19,13 @@ def test_restated_constants_match_the_layout_header():
     assert (int(m.group(1)), int(m.group(2))) == (C.TH, C.TW)
     assert int(re.search(r"constexpr int CHUNK = (\d+);", src).group(1)) == C.CHUNK
     assert int(re.search(r"constexpr int MAX_CHUNKS = (\d+);", src).group(1)) == C.MAX_CHUNKS
+    # the grid of the persistent launches: one formula (conv3x3_host.h), two workgroups per CU for the f16 form (or one, by option), one for the others
+    host = open(os.path.join(CSRC, "conv3x3_host.h")).read()
+    assert "(long long)(per_cu * cus / P.groups) * P.groups" in host and "const long long want = (long long)P.n_tiles * P.groups;" in host
     f16 = open(os.path.join(CSRC, "conv3x3_f16.hip")).read()
-    assert "(long long)(per_cu * cus / P.groups) * P.groups" in f16 and "const long long want = (long long)P.n_tiles * P.groups;" in f16
-    assert "(long long)(cus / P.groups) * P.groups" in open(os.path.join(CSRC, "conv3x3_bf16.hip")).read()
+    assert "const int per_cu = sd::option(sd::OPT_CONV_F16_WGS) == 1 ? 1 : 2;" in f16 and "persistent_grid(all, attr_done, lds, P, per_cu, blocks)" in f16
+    for other in ("conv3x3_bf16.hip", "conv3x3.hip"):
+        assert "persistent_grid(kern, attr_done, lds, P, 1, blocks)" in open(os.path.join(CSRC, other)).read()
 
 
 def test_ragged_tile_regimes_are_reached():

@@ -35,7 +35,7 @@ static int run(int D, int H, int W, int c_in, int c_out, int kz) {
   }
   hipMemcpy(dw, hp.data(), (size_t)np * 4, hipMemcpyHostToDevice);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  unsigned long long zero[20] = {}, prof[20];
+  unsigned long long zero[18] = {}, prof[18];
   float ms = 0;
   for (int rep = 0; rep < 3; ++rep) {
     hipMemcpyToSymbol(HIP_SYMBOL(g_conv_prof), zero, sizeof(zero));
@@ -48,7 +48,7 @@ static int run(int D, int H, int W, int c_in, int c_out, int kz) {
   hipMemcpyFromSymbol(prof, HIP_SYMBOL(g_conv_prof), sizeof(prof));
   const double flops = 2.0 * D * H * W * (double)c_in * c_out * 9 * kz;
   printf("\n%dx%dx%d  %d -> %d  kz %d: %.3f ms  %.1f TFLOP/s f32-equivalent  (%llu workgroups, %llu units, %.0f ticks per unit; shader clock %.2f GHz = ticks of a workgroup / kernel time)\n", D, H, W, c_in, c_out, kz, ms,
-         flops / ms * 1e-9, (unsigned long long)g_wgs * 256ull, prof[19], (double)prof[0] / (double)(prof[19] ? prof[19] : 1), (double)prof[0] / ((double)g_wgs * 256.0) / ms * 1e-6);
+         flops / ms * 1e-9, (unsigned long long)g_wgs * 256ull, prof[17], (double)prof[0] / (double)(prof[17] ? prof[17] : 1), (double)prof[0] / ((double)g_wgs * 256.0) / ms * 1e-6);
   double acc = 0;
   for (int k = 0; k < 16; ++k) { printf("   %5.1f %%  %s\n", 100.0 * (double)prof[1 + k] / (double)prof[0], kPhase[k]); acc += (double)prof[1 + k]; }
   printf("   %5.1f %%  outside the unit loop (first tile's staging, last stores)\n", 100.0 * (1.0 - acc / (double)prof[0]));

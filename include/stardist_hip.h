@@ -637,6 +637,21 @@ int sd_normalize_mi_ma_device(const void* d_x, int dtype, long long n, int n_seg
 int sd_zoom_linear_device(const void* d_src, void* d_dst, int dtype, int rank, const int* h_in_shape, const int* h_out_shape,
                           const int32_t* d_i0, const double* d_w0, const double* d_w1, void* stream);
 
+/* ---- label-image helpers: bounding boxes and hole filling (csrc/fill_holes.hip, csrc/fill_holes.h) ----------------------------
+ * lbl (Z, Y, X) int32 label image (2D: Z = 1, and the z axis then takes no part), labels 1 .. max_label are objects, every other
+ * value is background.  Bad arguments (a null pointer, a non-positive extent, a negative max_label) set the error string and return -1.
+ * Nothing is copied to the host and the stream is not synchronised (the workspace grows on a first call of a larger size).
+ *
+ * Boxes, as scipy.ndimage.find_objects gives them: d_boxes is [max_label + 1][6] = z0, y0, x0, z1, y1, x1 with exclusive stops;
+ * entry 0 and absent labels hold the sentinel INT_MAX, INT_MAX, INT_MAX, 0, 0, 0 (start > stop).  One pass over the image. */
+int sd_label_boxes_device(const int32_t* d_lbl, int Z, int Y, int X, int max_label, int32_t* d_boxes, void* stream);
+
+/* replaces stardist.utils.fill_label_holes (stardist/utils.py:137-153, default structure): d_out = max(d_lbl, 0) (labels beyond
+ * max_label: 0), and every pixel of a hole of label L = a 4- (6-) connected set of pixels != L inside L's bounding box that holds no
+ * pixel of the box's outermost layer = gets max(d_out, L).  Integer arithmetic only, the same bits from call to call.  d_out must
+ * not be d_lbl. */
+int sd_fill_label_holes_device(const int32_t* d_lbl, int Z, int Y, int X, int max_label, int32_t* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

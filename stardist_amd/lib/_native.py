@@ -113,6 +113,8 @@ SIGNATURES = {
     "sd_percentiles_device": (_i, [_vp, _i, ctypes.c_longlong, _i, _vp, _i, _i, _vp, _vp]),
     "sd_normalize_mi_ma_device": (_i, [_vp, _i, ctypes.c_longlong, _i, _vp, _vp, _f, _i, _vp, _vp]),
     "sd_zoom_linear_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sd_label_boxes_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "sd_fill_label_holes_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "_LIB_non_maximum_suppression_2d": (None, [_vp, _vp, _i, _i, _f, _i, _i, _i, _vp]),
     "_LIB_polygon_to_label": (None, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "_LIB_star_dist": (None, [_vp, _i, _i, _i, _i, _i, _vp]),

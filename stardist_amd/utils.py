@@ -506,8 +506,8 @@ def export_imagej_rois(fname, polygons, set_position=True, subpixel=True, compre
 
 
 # ----------------------------------------------------------------------------- label-image helpers the reference package exports
-# (stardist/__init__.py:13: fill_label_holes, sample_points, calculate_extents).  Host-side preparation / inspection of label images,
-# not part of the prediction path; numpy + scipy like the reference's.
+# (stardist/__init__.py:13: fill_label_holes, sample_points, calculate_extents).  numpy + scipy like the reference's on host input;
+# fill_label_holes and calculate_extents also take label images on a HIP device (csrc/fill_holes.hip).
 
 def _object_boxes(lbl_img):
     """[(label id, bounding-box slices)] of the labels present, ascending (scipy.ndimage.find_objects: entry i - 1 belongs to label i)"""
@@ -515,12 +515,114 @@ def _object_boxes(lbl_img):
     return [(i, sl) for i, sl in enumerate(find_objects(lbl_img), 1) if sl is not None]
 
 
-def fill_label_holes(lbl_img, **kwargs):
+_DEVICE_LABEL_DTYPES = ("torch.uint8", "torch.int8", "torch.int16", "torch.int32", "torch.int64")
+
+
+def _ids_need_compaction(top, size):
+    """the id policy of edt_prob: the kernels keep one table entry per id up to the largest, in int32"""
+    return top >= 2 ** 31 or top > 4 * size + 1024
+
+
+def _device_labels(lbl, device=None):
+    """(contiguous int32 device tensor with the positive labels of lbl and 0 elsewhere, largest label, ids): lbl a numpy array (uploaded to
+    `device`) or a tensor (moved there if it is elsewhere).  ids is None where the labels are the image's own; otherwise they were
+    compacted to 1 .. n in ascending order (so the larger of two ids stays the larger) and ids[k] is the original of label k, ids[0] = 0,
+    as an array of lbl's kind."""
+    import torch
+    if isinstance(lbl, np.ndarray):
+        a = lbl
+        top = int(a.max()) if a.size else 0
+        ids = None
+        if _ids_need_compaction(top, a.size):
+            pos = a > 0
+            u, inv = np.unique(a[pos], return_inverse=True)
+            lab = np.zeros(a.shape, np.int32)
+            lab[pos] = inv.reshape(-1) + 1
+            ids = np.concatenate([np.zeros(1, a.dtype), u.astype(a.dtype, copy=False)])
+            top = len(u)
+        else:
+            lab = np.maximum(a, 0).astype(np.int32, copy=False) if a.dtype.kind != "u" else a.astype(np.int32)
+        return torch.as_tensor(np.ascontiguousarray(lab), device=torch.device("cuda" if device is None else device)), max(top, 0), ids
+    t = lbl if device is None else lbl.to(torch.device(device))
+    top = int(t.max()) if t.numel() else 0
+    if _ids_need_compaction(top, t.numel()):
+        pos = t > 0
+        u, inv = torch.unique(t[pos], return_inverse=True)
+        lab = torch.zeros(t.shape, dtype=torch.int32, device=t.device)
+        lab[pos] = (inv + 1).to(torch.int32)
+        return lab, int(u.numel()), torch.cat([torch.zeros(1, dtype=t.dtype, device=t.device), u])
+    return t.clamp(min=0).to(torch.int32).contiguous(), max(top, 0), None
+
+
+def _zyx(shape):
+    return ((1,) + tuple(shape)) if len(shape) == 2 else tuple(shape)
+
+
+def _fill_label_holes_device(lbl_img, device=None):
+    """fill_label_holes through sd_fill_label_holes_device; numpy in (uploaded to `device`) -> numpy out, tensor in -> tensor out, of the
+    input's dtype and shape; the input is never written"""
+    import ctypes
+    import torch
+    from .lib import _native as N
+    N.require_device()
+    as_np = isinstance(lbl_img, np.ndarray)
+    if lbl_img.ndim not in (2, 3):
+        raise ValueError("fill_label_holes: a label image on the device must be 2D or 3D")
+    lab, top, ids = _device_labels(lbl_img, device)
+    out = torch.empty_like(lab)
+    if lab.numel():
+        Z, Y, X = _zyx(lab.shape)
+        if lab.dim() == 3 and Z == 1:
+            # one plane given as a volume: along z every pixel lies on the box's outer layer, so nothing is a hole (the host function
+            # says the same); the library takes Z = 1 for a 2D image, so the plane goes in as the volume (Y, 1, X) -- the same memory
+            Z, Y = Y, 1
+        N.dcall(lab, "sd_fill_label_holes_device", ctypes.c_void_p(lab.data_ptr()), Z, Y, X, top, ctypes.c_void_p(out.data_ptr()))
+    if as_np:
+        res = out.cpu().numpy()
+        return ids[res] if ids is not None else res.astype(lbl_img.dtype, copy=False)
+    res = ids[out.long()] if ids is not None else out.to(lbl_img.dtype)
+    return res.to(lbl_img.device)
+
+
+def _label_boxes_device(t):
+    """(n present, ndim) int64 numpy array of the bounding-box sizes of the labels of a 2D / 3D device tensor, by ascending label
+    (sd_label_boxes_device; only the box table comes to the host)"""
+    import ctypes
+    import torch
+    from .lib import _native as N
+    N.require_device()
+    nd = t.dim()
+    if t.numel() == 0:
+        return np.zeros((0, nd), np.int64)
+    if str(t.dtype) not in _DEVICE_LABEL_DTYPES:
+        t = t.to(torch.int64)
+    lab, top, _ = _device_labels(t)
+    boxes = torch.empty((top + 1, 6), dtype=torch.int32, device=lab.device)
+    N.dcall(lab, "sd_label_boxes_device", ctypes.c_void_p(lab.data_ptr()), *_zyx(lab.shape), top, ctypes.c_void_p(boxes.data_ptr()))
+    b = boxes.cpu().numpy().astype(np.int64)
+    b = b[b[:, 5] > b[:, 2]]
+    return (b[:, 3:] - b[:, :3])[:, 3 - nd:]
+
+
+def fill_label_holes(lbl_img, *, device=None, **kwargs):
     """Fill the holes of every labelled object (stardist/utils.py:137-153): per object, `binary_fill_holes` of its mask on its bounding
     box grown by one pixel on every side that is not an image border -- a cavity that reaches the image border stays open, as there.
-    **kwargs go to scipy.ndimage.binary_fill_holes."""
-    from scipy.ndimage import binary_fill_holes
+    **kwargs go to scipy.ndimage.binary_fill_holes.
+
+    numpy in without `device` -> the host code.  A 2D / 3D integer tensor on a HIP device in -> a tensor of the same dtype and shape on
+    that device out, equal to the host result (csrc/fill_holes.hip: bounding boxes in one pass, then per object two bit planes and a
+    flood from the box's outer layer; the input is not written).  numpy in with `device=` -> uploaded, filled there, numpy out.  The
+    kernels implement the default structure: with any **kwargs a device tensor goes through the host function and comes back as a
+    tensor.  Ids beyond int32, or sparse huge ids, are compacted in ascending order for the call and mapped back."""
+    if type(lbl_img).__module__.startswith("torch"):
+        on_device = lbl_img.is_cuda or device is not None
+        if kwargs or not on_device or str(lbl_img.dtype) not in _DEVICE_LABEL_DTYPES:
+            return _via_host(fill_label_holes, lbl_img, **kwargs)
+        return _fill_label_holes_device(lbl_img, device)
     lbl_img = np.asarray(lbl_img)
+    if device is not None and not kwargs and lbl_img.dtype.kind in "iu":
+        return _fill_label_holes_device(lbl_img, device)
+    from scipy.ndimage import binary_fill_holes
     out = np.zeros_like(lbl_img)
     for lab, box in _object_boxes(lbl_img):
         room = [(s.start > 0, s.stop < n) for s, n in zip(box, lbl_img.shape)]
@@ -552,8 +654,16 @@ def sample_points(n_samples, mask, prob=None, b=2):
 
 def calculate_extents(lbl, func=np.median):
     """Aggregate (median by default) of the objects' bounding-box sizes per axis, for one 2D / 3D label image, or over a sequence / 4D
-    stack of them (stardist/utils.py:180-193)."""
+    stack of them (stardist/utils.py:180-193).  Label images that are tensors on a HIP device stay there: one sd_label_boxes_device call
+    per image, the box table comes to the host and `func` runs over the extents as for host input."""
     from collections.abc import Iterable
+    if _is_device_tensor(lbl):
+        if lbl.dim() == 4:
+            return func(np.stack([calculate_extents(one, func) for one in lbl], axis=0), axis=0)
+        if lbl.dim() not in (2, 3):
+            raise ValueError("label image should be 2- or 3-dimensional (or pass a list of these)")
+        extents = _label_boxes_device(lbl)
+        return func(extents, axis=0) if len(extents) else np.zeros(lbl.dim())
     if (isinstance(lbl, np.ndarray) and lbl.ndim == 4) or (not isinstance(lbl, np.ndarray) and isinstance(lbl, Iterable)):
         return func(np.stack([calculate_extents(one, func) for one in lbl], axis=0), axis=0)
     n = lbl.ndim

@@ -652,6 +652,33 @@ int sd_label_boxes_device(const int32_t* d_lbl, int Z, int Y, int X, int max_lab
  * not be d_lbl. */
 int sd_fill_label_holes_device(const int32_t* d_lbl, int Z, int Y, int X, int max_label, int32_t* d_out, void* stream);
 
+/* ---- star representation of a label image's objects (csrc/relabel_star.hip, csrc/relabel_star.h): what relabel_image_stardist /
+ * relabel_image_stardist3D (stardist/geometry/geom2d.py:200-211, geom3d.py:201-217) need besides the rasterisers ----------------
+ * lbl (Z, Y, X) int32 label image as above (2D: Z = 1).
+ *
+ * Centroid sums: d_sums is [max_label + 1][4] int64 = pixel count, sum of z, sum of y, sum of x of every label 1 .. max_label; the
+ * call zeroes it, entry 0 and absent labels stay 0 (every other value of lbl is background).  One pass over the image, 64-bit
+ * integer arithmetic and 64-bit offsets: the same bits from call to call.  Bad arguments (a null pointer, a non-positive extent, a
+ * negative max_label) set the error string and return -1.  Nothing is copied to the host and the stream is not synchronised. */
+int sd_label_centroid_sums_device(const int32_t* d_lbl, int Z, int Y, int X, int max_label, int64_t* d_sums, void* stream);
+
+/* Star distances at given pixels only: d_points (n, 2) [(n, 3)] int64 pixel coordinates (y, x) [(z, y, x)], d_dist (n, n_rays) float32.
+ * Row p is the row of sd_star_dist2d_device [sd_star_dist3d_device] (grid 1) at that pixel, bit for bit -- 0 for a background pixel --
+ * with one difference in what is read: the labels are int32 and are compared by their low 16 bits, the cast to unsigned short that the
+ * reference and the dense entry points' callers apply, so ids that agree modulo 65536 are one object to a ray and an id that is a
+ * multiple of 65536 is background.  3D: d_dz / d_dy / d_dx are the rays' components (n_rays floats each) and the result is
+ * max(dist, floor) (relabel_image_stardist3D clamps at 1e-3f; 0 = no clamp).  n = 0 returns 0 without a launch.  A point outside the
+ * image gets a row of zeros and the call returns -1; so do a non-positive extent, a negative n, n_rays outside 1 .. 4096, a null
+ * pointer and, in 3D, a ray that is zero or NaN in every component (its march would not end; its column is zeros).  The device entries read one flag back (the stream is synchronised); the _host entries take host arrays and compute on
+ * the host, with the same code for the march (no device is touched). */
+int sd_star_dist2d_points_device(const int32_t* d_lbl, int H, int W, const int64_t* d_points, int n, int n_rays, float* d_dist,
+                                 void* stream);
+int sd_star_dist3d_points_device(const int32_t* d_lbl, int Z, int Y, int X, const int64_t* d_points, int n, const float* d_dz,
+                                 const float* d_dy, const float* d_dx, int n_rays, float floor, float* d_dist, void* stream);
+int sd_star_dist2d_points_host(const int32_t* lbl, int H, int W, const int64_t* points, int n, int n_rays, float* dist);
+int sd_star_dist3d_points_host(const int32_t* lbl, int Z, int Y, int X, const int64_t* points, int n, const float* dz, const float* dy,
+                               const float* dx, int n_rays, float floor, float* dist);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,14 +111,25 @@ def dist_to_coord3D(dist, points, rays_vertices):
     return points[:, np.newaxis] + dist[..., np.newaxis] * rays_vertices
 
 
-def relabel_image_stardist3D(lbl, rays, verbose=False, **kwargs):
+def relabel_image_stardist3D(lbl, rays, verbose=False, *, device=None, **kwargs):
     """geom3d.py:201-217: relabel each label region in `lbl` with its star representation (star_dist3D at the truncated region
-    centroid, clamped below at 1e-3 -> polyhedron_to_label with the regions' own label ids)."""
-    from .geom2d import _check_label_array, _region_centroids
-    lbl = np.asarray(lbl)
-    _check_label_array(lbl, "lbl")
-    if not lbl.ndim == 3:
-        raise ValueError("lbl image should be 3 dimensional")
+    centroid, clamped below at 1e-3 -> polyhedron_to_label with the regions' own label ids).
+
+    numpy in without `device` -> the host code below.  An integer tensor on a HIP device in -> it stays there (geom2d.
+    _star_representation_device, then the tensor path of polyhedron_to_label with labels = the regions' ids); an int32 tensor on that
+    device out.  numpy in with `device=` -> uploaded, relabelled there, numpy out.  With any **kwargs (grid, mode) or ids that would be
+    compacted, a tensor goes through the host function and comes back as a tensor.  An image without objects gives what
+    polyhedron_to_label gives for no points (a uint16 numpy array of zeros, and its warning under `verbose`) on either path."""
+    from .geom2d import _region_centroids, _relabel_route, _star_representation_device
+    route, img = _relabel_route(lbl, 3, device, kwargs)
+    if route == "via_host":
+        from ..utils import _via_host
+        return _via_host(relabel_image_stardist3D, img, rays, verbose, **kwargs)
+    if route == "device":
+        labs, points, dist = _star_representation_device(img, rays)
+        out = polyhedron_to_label(dist, points, rays, shape=tuple(int(v) for v in img.shape), labels=labs, verbose=verbose)
+        return out if N.is_torch(lbl) or not N.is_torch(out) else out.cpu().numpy()
+    lbl = img
     dist_all = star_dist3D(lbl, rays, **kwargs)
     labs, cen = _region_centroids(lbl)
     points = cen.astype(int)

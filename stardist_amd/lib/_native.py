@@ -115,6 +115,11 @@ SIGNATURES = {
     "sd_zoom_linear_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sd_label_boxes_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "sd_fill_label_holes_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "sd_label_centroid_sums_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "sd_star_dist2d_points_device": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "sd_star_dist3d_points_device": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _vp, _vp]),
+    "sd_star_dist2d_points_host": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]),
+    "sd_star_dist3d_points_host": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _vp]),
     "_LIB_non_maximum_suppression_2d": (None, [_vp, _vp, _i, _i, _f, _i, _i, _i, _vp]),
     "_LIB_polygon_to_label": (None, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "_LIB_star_dist": (None, [_vp, _i, _i, _i, _i, _i, _vp]),

@@ -662,6 +662,29 @@ int sd_fill_label_holes_device(const int32_t* d_lbl, int Z, int Y, int X, int ma
  * negative max_label) set the error string and return -1.  Nothing is copied to the host and the stream is not synchronised. */
 int sd_label_centroid_sums_device(const int32_t* d_lbl, int Z, int Y, int X, int max_label, int64_t* d_sums, void* stream);
 
+/* ---- intensity statistics of labelled objects (csrc/measure.hip, csrc/measure.h): the part of stardist_amd.utils.measure_labels that
+ * reads the image; boxes, pixel counts and coordinate sums come from the two entry points above ------------------------------------
+ * lbl (Z, Y, X) int32 label image as above (2D: Z = 1); d_boxes: the table sd_label_boxes_device wrote for this lbl and max_label (it
+ * is read on the device; every box is clamped to the image, so no table can make the kernels read outside d_lbl or d_img).  d_img:
+ * (Z, Y, X, C) contiguous, channels last, 1 <= C <= 64; dtype: 0 = uint8, 1 = uint16, 2 = float32.  Over the pixels p of label l, with
+ * v = img[p][c]:
+ *   integer images  d_isum2[l][c] = {sum v, sum v * v} in int64 (exact, also beyond 2^53); d_minmax[l][c] = {min, max} as int32;
+ *                   d_fsum2 is not used and may be null
+ *   float32 images  d_fsum2[l][c] = {sum double(v), sum double(v) * double(v)} in float64 (every square is exact); d_minmax[l][c] =
+ *                   {min, max} as float32; d_isum2 is not used and may be null
+ * Every table is [max_label + 1][C][2] and the call writes every row: row 0 and the rows of absent labels hold the sentinel, sums 0
+ * and {min, max} = {INT32_MAX, INT32_MIN} or {+inf, -inf}.  A NaN pixel makes sum, sum of squares, min and max of its object and
+ * channel NaN (as numpy's do); +-inf follow IEEE (+inf and -inf in one object: the sums are NaN, min and max the infinities).
+ * The float64 sums are added in the fixed order csrc/measure.h states -- per-lane sums over the flattened (row, x) index of the box, a
+ * fixed cross-lane tree, a box of more than 65536 pixels in chunks of whole rows whose results are added in chunk order -- with no
+ * floating-point atomic anywhere: they depend on (extents, lbl, img) alone, the same bits from call to call, from process to
+ * process and on any grid.  64-bit offsets.  Bad arguments set the error string and return -1 before anything is launched: a null
+ * d_lbl, d_boxes, d_img or d_minmax, a null sum table of the dtype's kind, a non-positive extent, a negative max_label, a dtype outside
+ * 0 .. 2, C outside 1 .. 64, more than 2^40 pixels or Z * Y beyond int.  Nothing is copied to the host and the stream is not
+ * synchronised (the workspace grows on a first call of a larger size). */
+int sd_label_intensity_stats_device(const int32_t* d_lbl, int Z, int Y, int X, int max_label, const int32_t* d_boxes, const void* d_img,
+                                    int dtype, int C, int64_t* d_isum2, double* d_fsum2, void* d_minmax, void* stream);
+
 /* Star distances at given pixels only: d_points (n, 2) [(n, 3)] int64 pixel coordinates (y, x) [(z, y, x)], d_dist (n, n_rays) float32.
  * Row p is the row of sd_star_dist2d_device [sd_star_dist3d_device] (grid 1) at that pixel, bit for bit -- 0 for a background pixel --
  * with one difference in what is read: the labels are int32 and are compared by their low 16 bits, the cast to unsigned short that the

@@ -675,6 +675,252 @@ def calculate_extents(lbl, func=np.median):
     return func(np.array([[s.stop - s.start for s in box] for _, box in boxes]), axis=0)
 
 
+# ----------------------------------------------------------------------------- measure_labels: the per-object table
+# Both routes produce the same "raw" columns -- label (n,), area (n,), bbox (n, 2 nd), csum (n, nd) coordinate sums, all int64, and with
+# an image sum, sum2 (n, C) int64 / float64 and min, max (n, C) int64 / the image's float type -- as numpy arrays or as tensors;
+# _measure_columns derives the table from them, the one place where centroid, mean and std are computed.
+_MEASURE_RAW = ("label", "area", "bbox", "csum", "sum", "sum2", "min", "max")
+
+
+def _measure_shapes(lbl_shape, img_shape):
+    """(number of channels or None without an image, whether the image has a channel axis); raises the ValueErrors of measure_labels"""
+    nd = len(lbl_shape)
+    if nd not in (2, 3):
+        raise ValueError("measure_labels: the label image must be 2D or 3D, got %d axes" % nd)
+    if img_shape is None:
+        return None, False
+    if tuple(img_shape) == tuple(lbl_shape):
+        return 1, False
+    if len(img_shape) == nd + 1 and tuple(img_shape[:-1]) == tuple(lbl_shape) and img_shape[-1] >= 1:
+        return int(img_shape[-1]), True
+    raise ValueError("measure_labels: the image's shape %s is neither the label image's %s nor that plus a channel axis"
+                     % (tuple(img_shape), tuple(lbl_shape)))
+
+
+def _measure_pack(raw):
+    """the raw columns side by side as one (n, K) int64 array / tensor (floats as the bits of their float64 value): one copy moves it"""
+    wide = [raw[key] if raw[key].ndim == 2 else raw[key].reshape(raw[key].shape[0], 1) for key in _MEASURE_RAW if key in raw]
+    if type(raw["label"]).__module__.startswith("torch"):
+        import torch
+        return torch.cat([a.to(torch.float64).contiguous().view(torch.int64) if a.dtype.is_floating_point else a.to(torch.int64)
+                          for a in wide], dim=1).contiguous()
+    return np.ascontiguousarray(np.concatenate([np.ascontiguousarray(a, np.float64).view(np.int64) if a.dtype.kind == "f"
+                                                else a.astype(np.int64) for a in wide], axis=1))
+
+
+def _measure_unpack(packed, nd, C, sum_dtype, mm_dtype):
+    """the raw columns of _measure_pack's array; sum_dtype / mm_dtype: the names of the dtypes of sum, sum2 and of min, max"""
+    is_t = type(packed).__module__.startswith("torch")
+    widths = [("label", 1, "int64"), ("area", 1, "int64"), ("bbox", 2 * nd, "int64"), ("csum", nd, "int64")]
+    if C is not None:
+        widths += [("sum", C, sum_dtype), ("sum2", C, sum_dtype), ("min", C, mm_dtype), ("max", C, mm_dtype)]
+    raw, at = {}, 0
+    for key, w, dt in widths:
+        a = packed[:, at:at + w]
+        at += w
+        if is_t:
+            import torch
+            a = a.contiguous()
+            a = a.view(torch.float64).to(getattr(torch, dt)) if dt.startswith("float") else a
+        else:
+            a = np.ascontiguousarray(a)
+            a = a.view(np.float64).astype(dt) if dt.startswith("float") else a
+        raw[key] = a.reshape(-1) if key in ("label", "area") else a
+    return raw
+
+
+def _measure_columns(raw, nd, channel_axis):
+    """the table of measure_labels from the raw columns (numpy arrays or tensors): centroid = float64(coordinate sum) / count, mean =
+    float64(sum) / count, var = max(0, float64(sum2) / count - mean^2), std = sqrt(var), every operation rounded on its own"""
+    is_t = type(raw["label"]).__module__.startswith("torch")
+    if is_t:
+        import torch
+        f64, sqrt, col = (lambda a: a.to(torch.float64)), torch.sqrt, (lambda a: a.contiguous())
+    else:
+        f64, sqrt, col = (lambda a: a.astype(np.float64)), np.sqrt, np.ascontiguousarray
+    out = {"label": raw["label"], "area": raw["area"]}
+    for k in range(2 * nd):
+        out["bbox-%d" % k] = col(raw["bbox"][:, k])
+    count = f64(raw["area"])
+    for k in range(nd):
+        out["centroid-%d" % k] = f64(raw["csum"][:, k]) / count
+    if "sum" in raw:
+        with np.errstate(all="ignore"):
+            cnt = count[:, None]
+            mean = f64(raw["sum"]) / cnt
+            var = (f64(raw["sum2"]) / cnt - mean * mean).clip(min=0)
+            std = sqrt(var)
+        named = (("sum_intensity", raw["sum"]), ("mean_intensity", mean), ("min_intensity", raw["min"]), ("max_intensity", raw["max"]),
+                 ("std_intensity", std))
+        for name, a in named:
+            for c in range(a.shape[1]):
+                out[("%s-%d" % (name, c)) if channel_axis else name] = col(a[:, c])
+    return out
+
+
+def _measure_raw_host(lbl, img):
+    """the raw columns by numpy over scipy.ndimage.find_objects boxes; img: None or an array of lbl.shape (+ (C,))"""
+    if lbl.dtype.kind == "b":
+        lbl = lbl.astype(np.uint8)
+    if lbl.dtype.kind not in "iu":
+        raise ValueError("measure_labels: the label image must have an integer type, got %s" % lbl.dtype)
+    nd = lbl.ndim
+    top = int(lbl.max()) if lbl.size else 0
+    ids = None
+    if _ids_need_compaction(top, lbl.size):
+        pos = lbl > 0
+        ids, inv = np.unique(lbl[pos], return_inverse=True)
+        lab = np.zeros(lbl.shape, np.int32)
+        lab[pos] = inv.reshape(-1) + 1
+    else:
+        lab = np.maximum(lbl, 0) if lbl.dtype.kind != "u" else lbl
+    boxes = _object_boxes(lab) if lab.size else []
+    n = len(boxes)
+    raw = {"label": np.array([k for k, _ in boxes], np.int64).reshape(n), "area": np.zeros(n, np.int64),
+           "bbox": np.zeros((n, 2 * nd), np.int64), "csum": np.zeros((n, nd), np.int64)}
+    if ids is not None:
+        raw["label"] = ids.astype(np.int64)[raw["label"] - 1]
+    if img is not None:
+        C = 1 if img.ndim == nd else img.shape[-1]
+        exact = img.dtype.kind in "iub"
+        raw["sum"] = np.zeros((n, C), np.int64 if exact else np.float64)
+        raw["sum2"] = np.zeros((n, C), np.int64 if exact else np.float64)
+        raw["min"] = np.zeros((n, C), np.int64 if exact else img.dtype)
+        raw["max"] = np.zeros((n, C), np.int64 if exact else img.dtype)
+    with np.errstate(all="ignore"):
+        for k, (l, box) in enumerate(boxes):
+            mask = lab[box] == l
+            where = np.nonzero(mask)
+            area = len(where[0])
+            raw["area"][k] = area
+            raw["bbox"][k] = [s.start for s in box] + [s.stop for s in box]
+            raw["csum"][k] = [int(w.sum(dtype=np.int64)) + area * s.start for w, s in zip(where, box)]
+            if img is not None:
+                v = img[box][mask].reshape(area, C)
+                wide = v.astype(np.int64 if exact else np.float64)
+                raw["sum"][k] = wide.sum(axis=0)
+                raw["sum2"][k] = (wide * wide).sum(axis=0)
+                raw["min"][k] = v.min(axis=0)
+                raw["max"][k] = v.max(axis=0)
+    return raw
+
+
+def _measure_raw_device(lbl, img, C, device):
+    """the raw columns as tensors on the device: sd_label_boxes_device, sd_label_centroid_sums_device and, with an image,
+    sd_label_intensity_stats_device, then the rows of the labels present (one scalar, their number, comes to the host)"""
+    import ctypes
+    import torch
+    from .lib import _native as N
+    N.require_device()
+    lab, top, ids = _device_labels(lbl, device)
+    dev, nd = lab.device, lab.dim()
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    code = None
+    if img is not None:
+        img = (img if type(img).__module__.startswith("torch") else torch.as_tensor(np.ascontiguousarray(img))).to(dev).contiguous()
+        code = _DEVICE_DTYPE_CODE[str(img.dtype)]
+    sum_t, mm_t = (torch.float64, torch.float32) if code == 2 else (torch.int64, torch.int32)
+    if lab.numel() == 0 or top <= 0:
+        raw = {"label": torch.zeros(0, dtype=torch.int64, device=dev), "area": torch.zeros(0, dtype=torch.int64, device=dev),
+               "bbox": torch.zeros((0, 2 * nd), dtype=torch.int64, device=dev), "csum": torch.zeros((0, nd), dtype=torch.int64, device=dev)}
+        if img is not None:
+            raw.update(sum=torch.zeros((0, C), dtype=sum_t, device=dev), sum2=torch.zeros((0, C), dtype=sum_t, device=dev),
+                       min=torch.zeros((0, C), dtype=torch.float32 if code == 2 else torch.int64, device=dev),
+                       max=torch.zeros((0, C), dtype=torch.float32 if code == 2 else torch.int64, device=dev))
+        return raw
+    zyx = _zyx(lab.shape)
+    boxes = torch.empty((top + 1, 6), dtype=torch.int32, device=dev)
+    sums = torch.empty((top + 1, 4), dtype=torch.int64, device=dev)
+    N.dcall(lab, "sd_label_boxes_device", vp(lab), *zyx, top, vp(boxes))
+    N.dcall(lab, "sd_label_centroid_sums_device", vp(lab), *zyx, top, vp(sums))
+    if img is not None:
+        acc = torch.empty((top + 1, C, 2), dtype=sum_t, device=dev)
+        mm = torch.empty((top + 1, C, 2), dtype=mm_t, device=dev)
+        N.dcall(lab, "sd_label_intensity_stats_device", vp(lab), *zyx, top, vp(boxes), vp(img), code, C,
+                vp(acc) if code != 2 else None, vp(acc) if code == 2 else None, vp(mm))
+    present = torch.nonzero(sums[:, 0]).reshape(-1)
+    s = sums.index_select(0, present)
+    b = boxes.index_select(0, present).to(torch.int64)
+    if ids is None:
+        label = present
+    else:
+        ids = ids if type(ids).__module__.startswith("torch") else torch.as_tensor(ids.astype(np.int64), device=dev)
+        label = ids.to(torch.int64).index_select(0, present)
+    raw = {"label": label, "area": s[:, 0].contiguous(), "bbox": b if nd == 3 else b[:, [1, 2, 4, 5]], "csum": s[:, 4 - nd:]}
+    if img is not None:
+        a, m = acc.index_select(0, present), mm.index_select(0, present)
+        raw.update(sum=a[:, :, 0], sum2=a[:, :, 1], min=m[:, :, 0] if code == 2 else m[:, :, 0].to(torch.int64),
+                   max=m[:, :, 1] if code == 2 else m[:, :, 1].to(torch.int64))
+    return raw
+
+
+def measure_labels(lbl, img=None, *, device=None, as_tensors=False):
+    """Per-object table of a 2D / 3D integer label image (values <= 0 are background) and, optionally, of the image `img` that was
+    segmented: shape lbl.shape or lbl.shape + (C,) (channels last).  Returns a dict of 1-D columns, one row per label present,
+    ascending by label, named as scikit-image 0.18's regionprops_table names them:
+
+        label                  int64    the label's id
+        area                   int64    pixel count
+        bbox-0 .. bbox-(2nd-1) int64    starts, then exclusive stops (scipy.ndimage.find_objects)
+        centroid-0 .. -(nd-1)  float64  float64(coordinate sum) / count
+      with img (with a channel axis every name gets -0 .. -(C-1)):
+        sum_intensity          int64 (integer images) / float64
+        mean_intensity         float64  float64(sum) / count
+        min_intensity, max_intensity    int64 / the image's float type
+        std_intensity          float64  population standard deviation: sqrt(max(0, float64(sum of squares) / count - mean^2))
+
+    Arithmetic: integer images are summed (values and squares) in int64, exactly, also beyond 2^53; float images in float64, where
+    every square of a float32 is exact.  The derived columns are computed in one place for both routes, every operation rounded on
+    its own.  A NaN pixel makes sum, mean, min, max and std of its object and channel NaN, as numpy does; +-inf follow IEEE.  Without
+    objects every column is an empty array of its dtype.
+
+    Routing, as fill_label_holes: numpy in without `device` -> the host code (numpy over find_objects boxes).  A tensor on a HIP device
+    in -> the device path; numpy in with `device=` -> uploaded and measured there; an image that is elsewhere is moved to the labels'
+    device.  The device path takes integer labels and uint8 / uint16 / float32 images (csrc/measure.hip and the box and centroid-sum
+    kernels; the inputs are not written): its float64 sums are added in a fixed order without floating-point atomics, so they depend
+    on (shape, lbl, img) alone -- the same bits from call to call and from process to process -- and differ from the host's only by the
+    order of the additions.  Any other dtype goes through the host code.  Ids beyond int32, or sparse huge ids, are compacted in
+    ascending order for the call; `label` reports the originals.  as_tensors=True: the columns are tensors (on the device, for the
+    device path: besides what reading the largest label needs, one scalar comes to the host, the number of rows); otherwise numpy
+    arrays, which the device path reads back in one copy of the table.  A label image that is not 2D / 3D or an image of another shape
+    raises ValueError before anything runs."""
+    lbl_t = type(lbl).__module__.startswith("torch")
+    img_t = img is not None and type(img).__module__.startswith("torch")
+    if not lbl_t:
+        lbl = np.asarray(lbl)
+    if img is not None and not img_t:
+        img = np.asarray(img)
+    nd = len(lbl.shape)
+    C, channel_axis = _measure_shapes(tuple(lbl.shape), None if img is None else tuple(img.shape))
+    on_device = device is not None or (lbl_t and lbl.is_cuda)
+    lbl_ok = (str(lbl.dtype) in _DEVICE_LABEL_DTYPES) if lbl_t else (lbl.dtype.kind in "iu")
+    img_ok = img is None or (str(img.dtype) if img_t else "torch." + img.dtype.name) in _DEVICE_DTYPE_CODE
+    if on_device and lbl_ok and img_ok:
+        raw = _measure_raw_device(lbl, img, C, device)
+        if as_tensors:
+            return _measure_columns(raw, nd, channel_axis)
+        sum_dtype, mm_dtype = (str(raw["sum"].dtype)[6:], str(raw["min"].dtype)[6:]) if img is not None else (None, None)
+        return _measure_columns(_measure_unpack(to_host(_measure_pack(raw)), nd, C, sum_dtype, mm_dtype), nd, channel_axis)
+    if not as_tensors:
+        return _measure_columns(_measure_raw_host(lbl.cpu().numpy() if lbl_t else lbl, img.cpu().numpy() if img_t else img), nd, channel_axis)
+    # the host table as tensors where the labels are (or on `device`): the packed raw columns make the trip
+    import torch
+    host_packed = lambda l, i=None: _measure_pack(_measure_raw_host(l, i))
+    rest = () if img is None else (img,)
+    if lbl_t:
+        packed = _via_host(host_packed, lbl, *rest)
+        packed = packed if device is None else packed.to(torch.device(device))
+    else:
+        packed = torch.as_tensor(host_packed(lbl, *[i.cpu().numpy() if img_t else i for i in rest]),
+                                 device=torch.device("cpu" if device is None else device))
+    sum_dtype = mm_dtype = None
+    if img is not None:
+        name = str(img.dtype)[6:] if img_t else img.dtype.name
+        floating = name.startswith("float") or name.startswith("bfloat")
+        sum_dtype, mm_dtype = ("float64", name) if floating else ("int64", "int64")
+    return _measure_columns(_measure_unpack(packed, nd, C, sum_dtype, mm_dtype), nd, channel_axis)
+
+
 def mask_to_categorical(y, n_classes, classes, return_cls_dict=False):
     """The multi-channel class map of the integer label array y (stardist/utils.py:318-380): float32 of shape y.shape + (n_classes + 1,),
     the first channel the background.  classes: a dict label id -> class id (0 = background class, 1 ... n_classes = that object class,

@@ -40,6 +40,13 @@ inline BeamCounters& beam_counters() { static BeamCounters c = {}; return c; }
 #else
 #define BEAM_CNT(f, v) ((void)0)
 #endif
+// BEAM_PH(i): phase boundary of the sweep -- "what ran since the previous boundary belongs to phase i".  Nothing in the product; the
+// phase profile (tools/beam_phase_profile.hip) defines it as a clock stamp before it includes this header.
+#ifndef BEAM_PH
+#define BEAM_PH(i) ((void)0)
+#endif
+enum { BEAM_PH_PREP = 0, BEAM_PH_SETUP, BEAM_PH_LM, BEAM_PH_POP, BEAM_PH_HORZ, BEAM_PH_ILIST, BEAM_PH_ISECT, BEAM_PH_TOP_EDGES, BEAM_PH_TOP_HORZ,
+       BEAM_PH_TOP_UPDATE, BEAM_PH_END, BEAM_PH_COUNT };
 
 namespace sdclip {
 
@@ -307,7 +314,7 @@ struct BeamCore {
                             RIL = P::template coord_region<MAXIL>(), RILB = P::template region<signed char, MAXIL>(),
                             RG = P::template coord_region<GJ>(), RGF = P::template region<int, (FULLGJ ? GJ : 1)>(), R1 = P::template region<int, 1>(), R8 = P::template region<u64, 1>(), RO = P::template region<ord_t, 1>();
   static constexpr unsigned O_BOTX = 0, O_BOTY = O_BOTX + RI, O_TOPX = O_BOTY + RI, O_TOPY = O_TOPX + RI, O_CURX = O_TOPY + RI,
-                            O_CURY = O_CURX + RI, O_DX = O_CURY + RI, O_EID = O_DX + RD, O_WCNT = O_EID + RS, O_WCNT2 = O_WCNT + RB,
+                            O_DX = O_CURX + RI, O_EID = O_DX + RD, O_WCNT = O_EID + RS, O_WCNT2 = O_WCNT + RB,
                             O_OUTIDX = O_WCNT2 + RB, O_LMLC = O_OUTIDX + RB, O_WDELTA = O_LMLC + RB, O_PTYP = O_WDELTA + RB,
                             O_SIDE = O_PTYP + RB, O_ILX = O_SIDE + RB, O_ILY = O_ILX + RIL, O_ILE1 = O_ILY + RIL, O_ILE2 = O_ILE1 + RILB,
                             O_GJOP = O_ILE2 + RILB, O_GJX1 = O_GJOP + RGF, O_GJX2 = O_GJX1 + RG, O_GJY2 = O_GJX2 + RG,
@@ -315,12 +322,13 @@ struct BeamCore {
                             O_PA = O_MLM + P::template region<unsigned char, 16>(),
                             O_ORD = O_PA + 2 * R8, O_HSEL = O_ORD + RO, O_AFTER_ORD = O_HSEL + RO, O_PB = O_PA + R8, O_NAEL = O_AFTER_ORD, O_FREE = O_NAEL + R1, O_NLM = O_FREE + R1,
                             O_CURLM = O_NLM + R1, O_NIL = O_CURLM + R1, O_STATUS = O_NIL + R1, O_NJOINS = O_STATUS + R1,
-                            O_NGJ = O_NJOINS + R1, O_NXTRA = O_NGJ + R1, O_LMY = O_NXTRA + R1, O_ORGX = O_LMY + R1, O_ORGY = O_ORGX + R1, O_CORE_END = O_ORGY + R1;
+                            O_NGJ = O_NJOINS + R1, O_NXTRA = O_NGJ + R1, O_LMY = O_NXTRA + R1, O_ORGX = O_LMY + R1, O_ORGY = O_ORGX + R1, O_SCANY = O_ORGY + R1, O_RINGN = O_SCANY + R1,
+                            O_CORE_END = O_RINGN + P::template region<int, 2>();
   // ---- bound slots
   // (coordinates: plain ints, or 16-bit offsets from the pair's origin (orgx, orgy) with LdsStorage16; slopes: stored, or recomputed)
   typename P::template CoordArr<K, O_BOTX, O_ORGX, O_STATUS> botx; typename P::template CoordArr<K, O_BOTY, O_ORGY, O_STATUS> boty;
   typename P::template CoordArr<K, O_TOPX, O_ORGX, O_STATUS> topx; typename P::template CoordArr<K, O_TOPY, O_ORGY, O_STATUS> topy;
-  typename P::template CoordArr<K, O_CURX, O_ORGX, O_STATUS> curx; typename P::template CoordArr<K, O_CURY, O_ORGY, O_STATUS> cury;
+  typename P::template CoordArr<K, O_CURX, O_ORGX, O_STATUS> curx;
   typename P::template SlopeArr<K, O_DX, O_BOTX, O_BOTY, O_TOPX, O_TOPY> dx;
   typename P::template Arr<short, K, O_EID> eid;                 // current edge: poly * EID_POLY + index in that polygon's ring
   typename P::template Arr<signed char, K, O_WCNT> wcnt; typename P::template Arr<signed char, K, O_WCNT2> wcnt2;   // |winding| <= n_lm <= 16
@@ -347,6 +355,11 @@ struct BeamCore {
   typename P::template Scalar<int, O_NXTRA> n_xtra;
   typename P::template Scalar<int, O_LMY> next_lm_y;             // Y of local minimum cur_lm (valid while cur_lm < n_lm)
   typename P::template Scalar<int, O_ORGX> orgx; typename P::template Scalar<int, O_ORGY> orgy;   // origin of the 16-bit coordinate arrays
+  // Curr.Y of EVERY edge in the AEL: the scan line the sweep stands on.  Clipper keeps it per edge, but an edge enters the AEL with
+  // Curr = Bot on the scan line of its local minimum (:2000-2010), is replaced by its successor with Curr = Bot = the predecessor's Top on the
+  // scan line that ends it (:1442-1462), and otherwise gets Curr.Y = topY at the top of every scan-beam (:3034): one value.
+  typename P::template Scalar<int, O_SCANY> scan_y;
+  typename P::template Arr<int, 2, O_RINGN> ring_n;               // vertices of the two prepared rings (read at every step along a bound)
 
   static constexpr ord_t ALLF = (ord_t)~(ord_t)0;
   static constexpr ord_t ONES = (ord_t)0x1111111111111111ull, HIGHS = (ord_t)0x8888888888888888ull;
@@ -392,8 +405,8 @@ struct BeamCore {
 
   // ------------------------------------------------------------------ static edge data
   SD_HD const Prep* prep_of(int id) const { return (id >= EID_POLY) ? (const Prep*)prepB : (const Prep*)prepA; }
-  static SD_HD int ring_nx(const Prep* q, int i) { return i + 1 == q->n ? 0 : i + 1; }
-  static SD_HD int ring_pv(const Prep* q, int i) { return i == 0 ? q->n - 1 : i - 1; }
+  static SD_HD int ring_nx(int n, int i) { return i + 1 == n ? 0 : i + 1; }
+  static SD_HD int ring_pv(int n, int i) { return i == 0 ? n - 1 : i - 1; }
   struct ES { int bx, by, tx, ty, code; };
   static SD_HD ES edge_static(const Prep* q, int i) {
     BEAM_CNT(es_loads, 1);
@@ -409,9 +422,9 @@ struct BeamCore {
   SD_HD int lml_id(int id, int code) const {
     const int c = code & 3;
     if (!c) return -1;
-    const Prep* q = prep_of(id);
+    const int n = ring_n[id >= EID_POLY ? 1 : 0];
     const int base = id & ~(EID_POLY - 1), i = id & (EID_POLY - 1);
-    return base + (c == 1 ? ring_nx(q, i) : ring_pv(q, i));
+    return base + (c == 1 ? ring_nx(n, i) : ring_pv(n, i));
   }
   SD_HD ES es_of(int id) const { return edge_static(prep_of(id), id & (EID_POLY - 1)); }
   static SD_HD double es_dx(const ES& s) {
@@ -583,7 +596,7 @@ struct BeamCore {
     const int n = lml_id(id, lmlc[e]);
     if (n < 0) { status |= ST_FAIL; return e; }
     load_slot(e, n);
-    curx[e] = botx[e]; cury[e] = boty[e];
+    curx[e] = botx[e];                                                       // (Curr.Y = Bot.Y is the scan line: scan_y)
     return e;
   }
 
@@ -681,12 +694,12 @@ struct BeamCore {
       load_slot(lb, poly * EID_POLY + li);
       load_slot(rb, poly * EID_POLY + ri);
       // AddPath :1185-1189 + Reset :1260-1273
-      const signed char wl = (ring_nx(q, li) == ri) ? -1 : 1;
+      const signed char wl = (ring_nx(ring_n[poly], li) == ri) ? -1 : 1;
       wdelta[lb] = wl; wdelta[rb] = (signed char)-wl;
       const signed char pt = poly ? (signed char)kSubject : (signed char)kClip;
       ptyp[lb] = pt; ptyp[rb] = pt;
-      curx[lb] = botx[lb]; cury[lb] = boty[lb]; side[lb] = kLeft; outidx[lb] = kUnassigned; wcnt[lb] = 0; wcnt2[lb] = 0;
-      curx[rb] = botx[rb]; cury[rb] = boty[rb]; side[rb] = kRight; outidx[rb] = kUnassigned; wcnt[rb] = 0; wcnt2[rb] = 0;
+      curx[lb] = botx[lb]; side[lb] = kLeft; outidx[lb] = kUnassigned; wcnt[lb] = 0; wcnt2[lb] = 0;
+      curx[rb] = botx[rb]; side[rb] = kRight; outidx[rb] = kUnassigned; wcnt[rb] = 0; wcnt2[rb] = 0;
 
       int op1 = -1; bool have_op1 = false;
       insert_edge_into_ael(lb, -1);
@@ -709,7 +722,7 @@ struct BeamCore {
       }
       const int lp = aprev(lb);
       if (outidx[lb] >= 0 && lp >= 0 && curx[lp] == botx[lb] && outidx[lp] >= 0 &&
-          slopes_equal4(botx[lp], boty[lp], topx[lp], topy[lp], curx[lb], cury[lb], topx[lb], topy[lb]) &&
+          slopes_equal4(botx[lp], boty[lp], topx[lp], topy[lp], curx[lb], scan_y, topx[lb], topy[lb]) &&
           wdelta[lb] != 0 && wdelta[lp] != 0) {
         const int op2 = add_out_pt(lp, botx[lb], boty[lb]);
         add_join(op1, op2, topx[lb], topy[lb]);
@@ -717,7 +730,7 @@ struct BeamCore {
       if (anext(lb) != rb) {
         const int rp = aprev(rb);
         if (outidx[rb] >= 0 && rp >= 0 && outidx[rp] >= 0 &&
-            slopes_equal4(curx[rp], cury[rp], topx[rp], topy[rp], curx[rb], cury[rb], topx[rb], topy[rb]) &&
+            slopes_equal4(curx[rp], scan_y, topx[rp], topy[rp], curx[rb], scan_y, topx[rb], topy[rb]) &&
             wdelta[rb] != 0 && wdelta[rp] != 0) {
           const int op2 = add_out_pt(rp, botx[rb], boty[rb]);
           add_join(op1, op2, topx[rb], topy[rb]);
@@ -725,7 +738,7 @@ struct BeamCore {
         int e = anext(lb);
         int guard = 0;
         while (e >= 0 && e != rb) {
-          intersect_edges(rb, e, curx[lb], cury[lb]);
+          intersect_edges(rb, e, curx[lb], scan_y);
           e = anext(e);
           if (++guard > K) { status |= ST_ITER; break; }
         }
@@ -787,7 +800,7 @@ struct BeamCore {
           if (dx[e] < es_dx(s)) break;
         }
         if (outidx[horz] >= 0) {
-          op1 = add_out_pt(horz, curx[e], cury[e]);
+          op1 = add_out_pt(horz, curx[e], scan_y);
           have_op1 = true;
           horz_joins(horz, op1);
           add_ghost_join(op1, curx[e], botx[horz], boty[horz]);
@@ -798,8 +811,8 @@ struct BeamCore {
           delete_from_ael(e);
           return;
         }
-        if (l2r) intersect_edges(horz, e, curx[e], cury[horz]);
-        else intersect_edges(e, horz, curx[e], cury[horz]);
+        if (l2r) intersect_edges(horz, e, curx[e], scan_y);
+        else intersect_edges(e, horz, curx[e], scan_y);
         const int eNext = l2r ? anext(e) : aprev(e);
         swap_positions_in_ael(horz, e);
         e = eNext;
@@ -821,12 +834,12 @@ struct BeamCore {
         horz = update_edge_into_ael(horz);
         if (wdelta[horz] == 0) return;
         const int ePrev = aprev(horz), eNext = anext(horz);
-        if (ePrev >= 0 && curx[ePrev] == botx[horz] && cury[ePrev] == boty[horz] && wdelta[ePrev] != 0 &&
-            (outidx[ePrev] >= 0 && cury[ePrev] > topy[ePrev] && slopes_equal_e(horz, ePrev))) {
+        if (ePrev >= 0 && curx[ePrev] == botx[horz] && scan_y == boty[horz] && wdelta[ePrev] != 0 &&
+            (outidx[ePrev] >= 0 && scan_y > topy[ePrev] && slopes_equal_e(horz, ePrev))) {
           const int op2 = add_out_pt(ePrev, botx[horz], boty[horz]);
           add_join(op1, op2, topx[horz], topy[horz]);
-        } else if (eNext >= 0 && curx[eNext] == botx[horz] && cury[eNext] == boty[horz] && wdelta[eNext] != 0 &&
-                   outidx[eNext] >= 0 && cury[eNext] > topy[eNext] && slopes_equal_e(horz, eNext)) {
+        } else if (eNext >= 0 && curx[eNext] == botx[horz] && scan_y == boty[horz] && wdelta[eNext] != 0 &&
+                   outidx[eNext] >= 0 && scan_y > topy[eNext] && slopes_equal_e(horz, eNext)) {
           const int op2 = add_out_pt(eNext, botx[horz], boty[horz]);
           add_join(op1, op2, topx[horz], topy[horz]);
         }
@@ -852,7 +865,7 @@ struct BeamCore {
   SD_HDN void intersect_point(int e1, int e2, i64& ipx, i64& ipy) const {
     double b1, b2;
     const double d1 = dx[e1], d2 = dx[e2];
-    if (d1 == d2) { ipy = cury[e1]; ipx = top_x(e1, ipy); return; }
+    if (d1 == d2) { ipy = scan_y; ipx = top_x(e1, ipy); return; }
     else if (d1 == 0) {
       ipx = botx[e1];
       if (is_horz(e2)) ipy = boty[e2];
@@ -875,8 +888,8 @@ struct BeamCore {
       double a1 = d1 < 0 ? -d1 : d1, a2 = d2 < 0 ? -d2 : d2;
       if (a1 < a2) ipx = top_x(e1, ipy); else ipx = top_x(e2, ipy);
     }
-    if (ipy > cury[e1]) {
-      ipy = cury[e1];
+    if (ipy > scan_y) {
+      ipy = scan_y;
       double a1 = d1 < 0 ? -d1 : d1, a2 = d2 < 0 ? -d2 : d2;
       if (a1 > a2) ipx = top_x(e2, ipy); else ipx = top_x(e1, ipy);
     }
@@ -944,6 +957,7 @@ struct BeamCore {
     if (n_ael == 0) return true;
     n_il = 0;
     build_intersect_list(topY);
+    BEAM_PH(BEAM_PH_ILIST);
     const int n = n_il;
     if (n == 0) return true;
     BEAM_CNT(il_beams, 1); BEAM_CNT(isect_pt, n);
@@ -984,10 +998,16 @@ struct BeamCore {
       delete_from_ael(e); delete_from_ael(mp);
     } else status |= ST_FAIL;   // "DoMaxima error" -> Execute fails, empty solution
   }
+  // Both walks go by POSITION over a register copy of the AEL word (one shift per step instead of two LDS reads and a search for the
+  // current edge).  The first re-reads the word after do_maxima, the only thing in it that changes the AEL: that deletes e (and its
+  // pair, after carrying e to it through edges that all lie behind e), so what followed e's predecessor now stands at e's position.
+  // The second changes no position at all.
   SD_BLK void process_edges_at_top_of_scanbeam(int topY) {
-    int e = ael_head();
+    ord_t w = ord;
+    int n = n_ael, p = 0;
     int guard = 0;
-    while (e >= 0) {
+    while (p < n) {
+      int e = nib(w, p);
       if (++guard > 4 * MAXV) { status |= ST_ITER; break; }
       bool isMax = (topy[e] == topY && (lmlc[e] & 3) == 0);
       if (isMax) {
@@ -998,53 +1018,56 @@ struct BeamCore {
         isMax = (mp < 0 || !mpHorz);
       }
       if (isMax) {
-        const int ePrev = aprev(e);
         do_maxima(e);
         if (status & ST_FAIL) return;
-        e = (ePrev < 0) ? ael_head() : anext(ePrev);
+        w = ord; n = n_ael;
       } else {
         if (topy[e] == topY && (lmlc[e] & 8) != 0) {
           e = update_edge_into_ael(e);
           if (outidx[e] >= 0) add_out_pt(e, botx[e], boty[e]);
           add_edge_to_sel(e);
         } else {
-          curx[e] = (int)top_x(e, topY);
-          cury[e] = topY;
+          // Curr.X = TopX(e, topY) (:3034) is what build_intersect_list stored in curx[e] for this topY; nothing since has written
+          // curx, or the bot / top / slope of a slot that comes here.  BEAM_VERIFY_CURX: the host build that counts differences.
+#if defined(BEAM_VERIFY_CURX) && !defined(__HIP_DEVICE_COMPILE__)
+          { const int stored = curx[e]; curx[e] = (int)top_x(e, topY); sd_curx_checks()[0] += 1; sd_curx_checks()[1] += (stored != (int)curx[e]); }
+#endif
         }
-        e = anext(e);
+        ++p;
       }
     }
+    scan_y = topY;                                                           // Curr.Y of every edge that stays (:3034; nothing above reads it)
+    BEAM_PH(BEAM_PH_TOP_EDGES);
     process_horizontals();
-    e = ael_head();
-    guard = 0;
-    while (e >= 0) {
-      if (++guard > 4 * MAXV) { status |= ST_ITER; break; }
+    BEAM_PH(BEAM_PH_TOP_HORZ);
+    w = ord; n = n_ael;
+    for (p = 0; p < n; ++p) {
+      int e = nib(w, p);
       if (topy[e] == topY && (lmlc[e] & 3) != 0) {
         bool op = false; int oph = -1;
         if (outidx[e] >= 0) { oph = add_out_pt(e, topx[e], topy[e]); op = true; }
         e = update_edge_into_ael(e);
-        const int ePrev = aprev(e), eNext = anext(e);
-        if (ePrev >= 0 && curx[ePrev] == botx[e] && cury[ePrev] == boty[e] && op &&
-            outidx[ePrev] >= 0 && cury[ePrev] > topy[ePrev] &&
-            slopes_equal4(curx[e], cury[e], topx[e], topy[e], curx[ePrev], cury[ePrev], topx[ePrev], topy[ePrev]) &&
+        const int ePrev = p > 0 ? nib(w, p - 1) : -1, eNext = p + 1 < n ? nib(w, p + 1) : -1;
+        if (ePrev >= 0 && curx[ePrev] == botx[e] && scan_y == boty[e] && op &&
+            outidx[ePrev] >= 0 && scan_y > topy[ePrev] &&
+            slopes_equal4(curx[e], scan_y, topx[e], topy[e], curx[ePrev], scan_y, topx[ePrev], topy[ePrev]) &&
             wdelta[e] != 0 && wdelta[ePrev] != 0) {
           const int op2 = add_out_pt(ePrev, botx[e], boty[e]);
           add_join(oph, op2, topx[e], topy[e]);
-        } else if (eNext >= 0 && curx[eNext] == botx[e] && cury[eNext] == boty[e] && op &&
-                   outidx[eNext] >= 0 && cury[eNext] > topy[eNext] &&
-                   slopes_equal4(curx[e], cury[e], topx[e], topy[e], curx[eNext], cury[eNext], topx[eNext], topy[eNext]) &&
+        } else if (eNext >= 0 && curx[eNext] == botx[e] && scan_y == boty[e] && op &&
+                   outidx[eNext] >= 0 && scan_y > topy[eNext] &&
+                   slopes_equal4(curx[e], scan_y, topx[e], topy[e], curx[eNext], scan_y, topx[eNext], topy[eNext]) &&
                    wdelta[e] != 0 && wdelta[eNext] != 0) {
           const int op2 = add_out_pt(eNext, botx[e], boty[e]);
           add_join(oph, op2, topx[e], topy[e]);
         }
       }
-      e = anext(e);
     }
   }
 
   // ------------------------------------------------------------------ Execute  :1560-1621, 1247-1276
   SD_HD void reset_core(const Prep* a, const Prep* b) {
-    prepA = a; prepB = b;
+    prepA = a; prepB = b; ring_n[0] = a->n; ring_n[1] = b->n;
     orgx = a->n ? a->v[0].x : (b->n ? b->v[0].x : 0); orgy = a->n ? a->v[0].y : (b->n ? b->v[0].y : 0);      // (before any coordinate is stored)
     ord = ALLF; hsel = ALLF; n_ael = 0; freemask = (1 << K) - 1;
     n_lm = 0; cur_lm = 0; n_il = 0; status = ST_OK; n_joins = 0; n_gj = 0; n_xtra = 0;
@@ -1072,19 +1095,27 @@ struct BeamCore {
     cur_lm = 0;
     next_lm_y = lm_y(0);
     int botY = next_lm_y, topY = 0;
+    scan_y = botY;
+    BEAM_PH(BEAM_PH_SETUP);
     int guard = 0;
     bool ok = true;
     for (;;) {
       insert_local_minima_into_ael(botY);              // (in front of the loop and at its end in Clipper: ONE call site here, same sequence)
+      BEAM_PH(BEAM_PH_LM);
       if (status & (ST_OVERFLOW_AEL | ST_OVERFLOW_REC | ST_OVERFLOW_IL | ST_ITER)) { ok = false; break; }
       const bool popped = pop_scanbeam(botY, topY);
+      BEAM_PH(BEAM_PH_POP);
       if (!popped) break;
       if (++guard > 4 * MAXV + 8) { status |= ST_ITER; break; }
       BEAM_CNT(beams, 1); BEAM_CNT(ael_sum, n_ael);
       process_horizontals();
+      BEAM_PH(BEAM_PH_HORZ);
       n_gj = 0;                                                             // ClearGhostJoins :1575
-      if (!process_intersections(topY)) { ok = false; break; }
+      const bool isect_ok = process_intersections(topY);
+      BEAM_PH(BEAM_PH_ISECT);
+      if (!isect_ok) { ok = false; break; }
       process_edges_at_top_of_scanbeam(topY);
+      BEAM_PH(BEAM_PH_TOP_UPDATE);
       if (status & ST_FAIL) { ok = false; break; }
       botY = topY;
     }

@@ -61,6 +61,11 @@
 #define SD_BLK SD_HD
 #endif
 
+#if defined(BEAM_VERIFY_CURX) && !defined(__HIP_DEVICE_COMPILE__)
+// counting build (host): {comparisons, differences} of the stored Curr.X against TopX recomputed at the top of a scan-beam
+inline long* sd_curx_checks() { static long c[2] = {0, 0}; return c; }
+#endif
+
 namespace sdclip {
 
 typedef long long i64;
@@ -990,7 +995,11 @@ struct SweepCore {
           if (outidx[e] >= 0) add_out_pt(e, botx[e], boty[e]);
           add_edge_to_sel(e);
         } else {
-          curx[e] = (int)top_x(e, topY);
+          // Curr.X = TopX(e, topY) (:3034): build_intersect_list stored exactly that in curx[e] for this topY, for every edge of the AEL, and
+          // nothing since has written curx or an edge's bot / top.  BEAM_VERIFY_CURX: the host build that counts differences.
+#if defined(BEAM_VERIFY_CURX) && !defined(__HIP_DEVICE_COMPILE__)
+          { const int stored = curx[e]; curx[e] = (int)top_x(e, topY); sd_curx_checks()[0] += 1; sd_curx_checks()[1] += (stored != (int)curx[e]); }
+#endif
           cury[e] = topY;
         }
         e = anext[e];

@@ -1,28 +1,17 @@
 """How long does ONE Clipper-exact sweep take on the device, and how does a launch scale with the number of pairs?  The pair-level probe
 (sd_clip_pairs_device: AddPath of both polygons + the bound-slot sweep per lane, tier 1) on n = 1 ... 2^17 pairs of bench-like star polygons
-(32 rays, radius ~ 14, overlap near the NMS threshold).  usage: python tools/time_clip_latency.py"""
+(32 rays, radius ~ 14, overlap near the NMS threshold).  usage: python tools/time_clip_latency.py
+(STARDIST_AMD_PROBE_LIB=NAME times a variant library of tools/build_variant.py instead of the product's)"""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _probe_lib  # noqa: F401  (first: selects the library)
 import numpy as np
 import torch
 from stardist_amd.lib import _native as N
+from _clip_pairs import NMAX, R, make_pairs
 
-rng = np.random.default_rng(0)
-R = 32
-phi = 2 * np.pi * np.arange(R) / R
 dev = torch.device("cuda:0")
-NMAX = 1 << 17
-
-
-def polys(n, shift):
-    d = 14.0 * (1 + 0.15 * rng.standard_normal((n, R))).astype(np.float32)
-    c = rng.uniform(200, 210, (n, 2)).astype(np.float32) + shift
-    x = (c[:, 1:2] + d * np.cos(phi)).astype(np.int32); y = (c[:, 0:1] + d * np.sin(phi)).astype(np.int32)
-    return x, y
-
-
-xa, ya = polys(NMAX, 0.0); xb, yb = polys(NMAX, np.float32([9.0, 6.0]))
-T = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (xa, ya, xb, yb)]
+T = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in make_pairs()]
 out = torch.zeros(NMAX, dtype=torch.int64, device=dev); fl = torch.zeros(NMAX, dtype=torch.int32, device=dev)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 for n in (1, 1, 4, 16, 64, 256, 1024, 4096, 16384, 65536, 98304, NMAX):
@@ -33,3 +22,7 @@ for n in (1, 1, 4, 16, 64, 256, 1024, 4096, 16384, 65536, 98304, NMAX):
         e1.record(); e1.synchronize()
         best = min(best, e0.elapsed_time(e1))
     print("n = %6d pairs: %.3f ms  (%.1f ns/pair)" % (n, best, best * 1e6 / n), flush=True)
+torch.cuda.synchronize()
+o = out.cpu().numpy(); f = fl.cpu().numpy()
+import zlib
+print("twice-area crc %08x  flags crc %08x  (all %d pairs)" % (zlib.crc32(o.tobytes()), zlib.crc32(f.tobytes()), NMAX), flush=True)

@@ -36,4 +36,4 @@ for r in range(int(sys.argv[1]) if len(sys.argv) > 1 else 3):
     torch.cuda.synchronize(); dt = time.time() - t
     st = _native.last_stats["nms2d"]
     crc = zlib.crc32((keep.cpu().numpy() if hasattr(keep, "cpu") else np.asarray(keep)).astype(np.uint8).tobytes())
-    print(f"rep {r}: N={len(td)} -> {int(keep.sum())}  {dt*1e3:.1f} ms  pair {st[4]/1e6:.2f} ms ({st[0]} pairs, {st[5]} launches)  general {st[6]/1e6:.2f} ms ({st[1]})  build {st[7]/1e6:.2f} ms  rounds {st[2]}  skipped {st[11]}  keep crc {crc:08x}", flush=True)
+    print(f"rep {r}: N={len(td)} -> {int(keep.sum())}  {dt*1e3:.1f} ms  pair {st[4]/1e6:.2f} ms ({st[0]} pairs, {st[5]} launches)  general {st[6]/1e6:.2f} ms ({st[1]})  build {st[7]/1e6:.2f} ms  rounds {st[2]}  decided {st[9]}  deferred {st[10]}  skipped {st[11]}  keep crc {crc:08x}", flush=True)

@@ -520,9 +520,12 @@ class StarDistBase(object):
             self._head_mode = getattr(self.net, "head_mode", "dense")
         else:
             from .unet import conv_mode
-            # everything the captured kernels depend on besides the weights: shape, head form, convolution kernel family
+            # everything the captured kernels depend on besides the weights: shape, head form, convolution kernel family, and -- for the
+            # sparse head -- the knobs StarDistNet._lazy_ok reads (they decide whether the capture stores the feature tensor)
             from .unet import split16_enabled
-            key = (tuple(xc.shape), xc.dtype, bool(sparse_head), conv_mode(), bool(getattr(self.net, "fused_heads", True)), split16_enabled())
+            lazy = (bool(getattr(self.net, "lazy_features", True)), int(getattr(self.net, "lazy_features_min_bytes", 0)),
+                    os.environ.get("STARDIST_AMD_LAZY_FEATURES", "1") != "0") if sparse_head else None
+            key = (tuple(xc.shape), xc.dtype, bool(sparse_head), conv_mode(), bool(getattr(self.net, "fused_heads", True)), split16_enabled(), lazy)
             cache = self.__dict__.setdefault("_graphs", {})
             if key not in cache:
                 if len(cache) >= 8:                                  # bounded: tiles of a big image share few shapes
@@ -540,13 +543,15 @@ class StarDistBase(object):
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g):
                         static_out = self._net_eager(static_in, sparse_head)
-                    cache[key] = (g, static_in, static_out, getattr(self.net, "head_mode", "dense"))
+                    # (what the capture left on the net for the caller's dist_rows stays with the entry: the net's own attributes are
+                    # those of the LAST capture)
+                    cache[key] = (g, static_in, static_out, getattr(self.net, "head_mode", "dense"), bool(getattr(self.net, "_lazy_split16", False)))
                 except Exception as e:                               # capture unsupported for some solver: stay eager
                     import warnings
                     warnings.warn("HIP graph capture of the network failed (%r); running eagerly" % (e,))
                     self.use_hip_graph = False
                     return self._net_forward_once(x, sparse_head)
-            g, static_in, static_out, self._head_mode = cache[key]
+            g, static_in, static_out, self._head_mode, self.net._lazy_split16 = cache[key]
             static_in.copy_(xc)
             g.replay()
             ys = static_out
@@ -634,7 +639,9 @@ class StarDistBase(object):
         """base.py:1100-1110 derives this empirically from an impulse response; the analytic receptive field of
         the conv stack (upper bound of the empirical one) is used instead.  tests/test_cpu_reference_predict.py runs the reference's
         own _compute_receptive_field on the graph its own _build makes and holds this bound to it (never smaller; the comparison
-        found the stem convolutions of anisotropic grids missing from the bound on the axes a stem round does not pool)."""
+        found the stem convolutions of anisotropic grids missing from the bound on the axes a stem round does not pool).  The reference's
+        impulse sits on the first pixel of a pooling block; tests/test_cpu_predict_cases.py moves it through the block (shift networks) and
+        found the grid stem's pooling missing: an output pixel reads grid - 1 pixels further towards the end of the axis."""
         rf = self._receptive_field_radius()
         d = dict(zip(self.config.axes.replace("C", ""), rf))
         return tuple(d.get(a, 0) for a in query_axes)
@@ -654,6 +661,9 @@ class StarDistBase(object):
                 for _ in range(rounds):                           # pre-pooling stages
                     r += ncv * (k[d] // 2) * scale
                     if scale < g:
+                        # an output pixel stands for the whole pooled cell: it reads up to `scale` further towards the end of the axis (g - 1
+                        # in all; a U-Net level's pooling is counted with its up-sampling below, the stem's has none)
+                        r += scale
                         scale *= 2
                 for n in range(depth):
                     r += ncv * (k[d] // 2) * scale; scale *= pool[d]

@@ -124,8 +124,7 @@ def test_model_sparse_head_equals_dense_prediction(dim):
     # with the dense feature tensor (small inputs) and without it (round 6: the features layer keeps only the probability head's partial sums, the
     # features of the candidate pixels are evaluated afterwards by sd_conv3_f16x3_rows_device; the default from 4 GiB of features on)
     for lazy_min, n_tiles in ((4 << 30, None), (4 << 30, tiles), (0, None), (0, tiles)):
-        m.net.lazy_features_min_bytes = lazy_min
-        m.__dict__.pop("_graphs", None)
+        m.net.lazy_features_min_bytes = lazy_min          # (the graph cache is keyed by it: no capture of another setting is replayed)
         prob, dist = m.predict(img, n_tiles=n_tiles)[:2]
         ps, ds, pts = m.predict_sparse(img, prob_thresh=thr, n_tiles=n_tiles)
         assert m._head_mode == ("sparse_lazy" if lazy_min == 0 else "sparse")

@@ -685,6 +685,22 @@ int sd_label_centroid_sums_device(const int32_t* d_lbl, int Z, int Y, int X, int
 int sd_label_intensity_stats_device(const int32_t* d_lbl, int Z, int Y, int X, int max_label, const int32_t* d_boxes, const void* d_img,
                                     int dtype, int C, int64_t* d_isum2, double* d_fsum2, void* d_minmax, void* stream);
 
+/* ---- connected components (csrc/label_cc.hip, csrc/label_cc.h): what skimage.measure.label(img, background, connectivity) and, for a
+ * mask, scipy.ndimage.label(mask, generate_binary_structure(ndim, connectivity)) compute ----------------------------------------------
+ * d_img: (Z, Y, X) contiguous image (2D: Z = 1); dtype: 0 = uint8 (a bool mask travels as uint8), 1 = uint16, 3 = int32 (the codes above;
+ * 2, float32, is not taken).  Two pixels are joined when they are neighbours, their values are equal and that value is not `background`
+ * (a background that is no value of the dtype makes every pixel foreground).  Neighbours: the offsets (dz, dy, dx) in {-1, 0, 1}^3 with
+ * at most `connectivity` (1 .. 3) non-zero coordinates, i.e. 6, 18 or 26 of them; with Z = 1 this is the 2D rule for connectivity 1
+ * (4 neighbours) or 2 (8).  d_out (Z * Y * X int32, not d_img) serves as the parent array first and then holds the result: 0 for
+ * background, ids 1 .. n in raster (C) order of each component's first pixel; d_count receives n.  A tiled union-find whose parent of a
+ * pixel never exceeds the pixel's own linear index, so that every loop ends without an iteration cap, and whose roots are the
+ * components' smallest indices: integer arithmetic only, the result depends on the input alone, the same bits from call to call.
+ * d_img is not written.  Bad arguments set the error string and return -1 before anything is launched: a null pointer, a
+ * non-positive extent, connectivity outside 1 .. 3, another dtype, more than 2^31 - 1 pixels.  Nothing is copied to the host and the
+ * stream is not synchronised (the workspace, one int per pixel, grows on a first call of a larger size). */
+int sd_label_components_device(const void* d_img, int dtype, int Z, int Y, int X, int connectivity, long long background, int* d_out,
+                               int* d_count, void* stream);
+
 /* Star distances at given pixels only: d_points (n, 2) [(n, 3)] int64 pixel coordinates (y, x) [(z, y, x)], d_dist (n, n_rays) float32.
  * Row p is the row of sd_star_dist2d_device [sd_star_dist3d_device] (grid 1) at that pixel, bit for bit -- 0 for a background pixel --
  * with one difference in what is read: the labels are int32 and are compared by their low 16 bits, the cast to unsigned short that the

@@ -921,6 +921,128 @@ def measure_labels(lbl, img=None, *, device=None, as_tensors=False):
     return _measure_columns(_measure_unpack(packed, nd, C, sum_dtype, mm_dtype), nd, channel_axis)
 
 
+# ----------------------------------------------------------------------------- connected components: mask -> label image
+# element type codes of sd_label_components_device (a bool mask travels as uint8)
+_COMPONENTS_DTYPE_CODE = {"bool": 0, "uint8": 0, "uint16": 1, "int32": 3}
+
+
+def _backward_offsets(nd, connectivity):
+    """the neighbour offsets with at most `connectivity` non-zero coordinates that point backwards in raster order: every edge of the
+    pixel graph once"""
+    from itertools import product
+    return [o for o in product((-1, 0, 1), repeat=nd) if o < (0,) * nd and sum(1 for c in o if c) <= connectivity]
+
+
+def _label_components_host(img, connectivity, background):
+    """(int32 label image, n) of a 2D / 3D numpy array: one edge list per backward offset, scipy's connected_components on the pixel
+    graph, ids by first occurrence in raster order"""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    a = np.ascontiguousarray(img)
+    out = np.zeros(a.shape, np.int32)
+    if a.size == 0:
+        return out, 0
+    if a.size > 2 ** 31 - 1:
+        raise ValueError("label_components: more than 2^31 - 1 pixels")
+    fg = a != background
+    index = np.arange(a.size, dtype=np.int32).reshape(a.shape)
+    rows, cols = [], []
+    for off in _backward_offsets(a.ndim, connectivity):
+        here = tuple(slice(max(0, -d), n - max(0, d)) for d, n in zip(off, a.shape))
+        there = tuple(slice(max(0, d), n - max(0, -d)) for d, n in zip(off, a.shape))
+        keep = (a[here] == a[there]) & fg[here]
+        rows.append(index[here][keep])
+        cols.append(index[there][keep])
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    graph = coo_matrix((np.ones(len(rows), np.int8), (rows, cols)), shape=(a.size, a.size)).tocsr()
+    comp = connected_components(graph, directed=False, return_labels=True)[1]
+    where = np.flatnonzero(fg.reshape(-1))
+    if not len(where):
+        return out, 0
+    of_pixel = comp[where]
+    ids, first = np.unique(of_pixel, return_index=True)                     # first: position of a component's first pixel
+    new_id = np.zeros(int(comp.max()) + 1, np.int32)
+    new_id[ids[np.argsort(first, kind="stable")]] = np.arange(1, len(ids) + 1, dtype=np.int32)
+    out.reshape(-1)[where] = new_id[of_pixel]
+    return out, int(len(ids))
+
+
+def _label_components_device(img, connectivity, background, device):
+    """(int32 label tensor, int32 device scalar n) through sd_label_components_device; img a numpy array (uploaded to `device`) or a
+    tensor (moved there if it is elsewhere) of one of the dtypes of _COMPONENTS_DTYPE_CODE; nothing comes to the host"""
+    import ctypes
+    import torch
+    from .lib import _native as N
+    N.require_device()
+    if int(np.prod(img.shape, dtype=np.int64)) > 2 ** 31 - 1:
+        raise ValueError("label_components: more than 2^31 - 1 pixels")
+    if isinstance(img, np.ndarray):
+        a = np.ascontiguousarray(img)
+        t = torch.as_tensor(a.view(np.uint8) if a.dtype == np.bool_ else a, device=torch.device("cuda" if device is None else device))
+    else:
+        t = (img if device is None else img.to(torch.device(device))).contiguous()
+        t = t.view(torch.uint8) if t.dtype == torch.bool else t
+    out = torch.empty(t.shape, dtype=torch.int32, device=t.device)
+    count = torch.zeros(1, dtype=torch.int32, device=t.device)
+    if t.numel():
+        code = _COMPONENTS_DTYPE_CODE[str(t.dtype).replace("torch.", "")]
+        N.dcall(t, "sd_label_components_device", ctypes.c_void_p(t.data_ptr()), code, *_zyx(t.shape), int(connectivity), int(background),
+                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(count.data_ptr()))
+    return out, count[0]
+
+
+def label_components(img, connectivity=None, background=0, *, return_num=False, device=None):
+    """Label the connected components of a 2D / 3D image, as skimage.measure.label(img, background=background,
+    connectivity=connectivity) does: pixels equal to `background` (None: 0) get 0; two neighbouring pixels belong to one component only if
+    their values are equal; `connectivity` = 1 .. ndim is the largest number of coordinates in which neighbours may differ (None: ndim);
+    ids 1 .. n are given in raster (C) order of each component's first pixel.  For a boolean mask this is scipy.ndimage.label(mask,
+    generate_binary_structure(ndim, connectivity)).  The result is int32, the project's label dtype, on both routes (skimage returns
+    int64).  return_num=True: (labels, n) with n a Python int.
+
+    Routing, as fill_label_holes: numpy in without `device` -> the host code (the pixel graph built with numpy, scipy's
+    connected_components, ids by first occurrence).  A bool / uint8 / uint16 / int32 tensor on a HIP device in (or `device=` given) -> an
+    int32 tensor on that device out, equal to the host result (csrc/label_cc.hip: a tiled union-find whose roots are the components'
+    first pixels; the input is not written, the result depends on the input alone); nothing is read back and the stream is not
+    synchronised unless return_num=True.  numpy in with `device=` -> uploaded, labelled there, numpy out.  A tensor of another dtype, or
+    a background that is no integer, goes through the host code and comes back as a tensor.  An image that is not 2D / 3D, a
+    connectivity outside 1 .. ndim or, on the device, more than 2^31 - 1 pixels raise ValueError before anything runs; an empty image
+    gives an empty result and n = 0."""
+    is_t = type(img).__module__.startswith("torch")
+    if not is_t:
+        img = np.asarray(img)
+    nd = len(img.shape)
+    if nd not in (2, 3):
+        raise ValueError("label_components: the image must be 2D or 3D, got %d dimensions" % nd)
+    if connectivity is None:
+        connectivity = nd
+    if isinstance(connectivity, (bool, np.bool_)) or not isinstance(connectivity, (int, np.integer)) or not 1 <= connectivity <= nd:
+        raise ValueError("Connectivity for %dD images must be in [1, ..., %d]. Got %r." % (nd, nd, connectivity))
+    connectivity = int(connectivity)
+    background = 0 if background is None else background
+    name = str(img.dtype).replace("torch.", "")
+    whole = isinstance(background, (int, np.integer, bool, np.bool_)) or (isinstance(background, (float, np.floating))
+                                                                           and float(background).is_integer())
+    on_device = device is not None or (is_t and img.is_cuda)
+    if on_device and name in _COMPONENTS_DTYPE_CODE and whole and abs(int(background)) < 2 ** 63:
+        out, count = _label_components_device(img, connectivity, int(background), device)
+        if not is_t:
+            out = to_host(out)                                              # synchronises: count is there too
+        return (out, int(count)) if return_num else out
+    if is_t:
+        import torch
+        n_box = []
+
+        def host(a):
+            lab, n = _label_components_host(a, connectivity, background)
+            n_box.append(n)
+            return lab
+        out = _via_host(host, img)
+        out = out if device is None else out.to(torch.device(device))
+        return (out, n_box[0]) if return_num else out
+    out, n = _label_components_host(img, connectivity, background)
+    return (out, n) if return_num else out
+
+
 def mask_to_categorical(y, n_classes, classes, return_cls_dict=False):
     """The multi-channel class map of the integer label array y (stardist/utils.py:318-380): float32 of shape y.shape + (n_classes + 1,),
     the first channel the background.  classes: a dict label id -> class id (0 = background class, 1 ... n_classes = that object class,

@@ -701,6 +701,31 @@ int sd_label_intensity_stats_device(const int32_t* d_lbl, int Z, int Y, int X, i
 int sd_label_components_device(const void* d_img, int dtype, int Z, int Y, int X, int connectivity, long long background, int* d_out,
                                int* d_count, void* stream);
 
+/* ---- nearest-feature transform (csrc/edt_feature.hip, csrc/edt_feature.h): scipy.ndimage.distance_transform_edt with indices, exactly -
+ * d_img: (Z, Y, X) contiguous image (2D: Z = 1, the z axis then takes no part); dtype: 0 = uint8, 1 = uint16, 3 = int32, as above.  The
+ * features are the pixels != 0, or with feature_is_zero = 1 the pixels == 0 (distance_transform_edt's orientation).  For a pixel p and
+ * a feature q, D(p, q) = ((sz dz)^2 + (sy dy)^2) + (sx dx)^2 in float64, every operation rounded on its own, each term t = s * d; t * t
+ * -- scipy's floats.  nearest(p) is the feature of smallest D; among equal D the smallest x wins, then the smallest y, then the
+ * smallest z (scipy's choice); a feature is its own nearest feature.  d_index[p] (int32, may be null) = the linear index of nearest(p),
+ * d_dist[p] (float64, may be null) = sqrt(D(p, nearest(p))).  max_distance < 0 or inf: no bound; otherwise a pixel with
+ * dist > max_distance, like every pixel of an image without features, gets index -1 and distance +inf, and no scan goes farther than
+ * the bound.  A separable pass per axis in scipy's order, outward scans that stop when the axis term alone exceeds the best value:
+ * no atomics, the result depends on the input alone, the same bits from call to call; the time follows the largest distance in the
+ * result (or the bound).  d_img is not written.  Bad arguments set the error string and return -1 before anything is launched: a null
+ * image, a non-positive extent, more than 2^31 - 1 pixels, a spacing that is not positive and finite, a NaN max_distance,
+ * feature_is_zero outside 0 / 1, another dtype.  Nothing is copied to the host and the stream is not synchronised (the workspace, 12 B
+ * per pixel, 24 B for a volume, grows on a first call of a larger size). */
+int sd_nearest_feature_device(const void* d_img, int dtype, int Z, int Y, int X, int feature_is_zero, double sz, double sy, double sx,
+                              double max_distance, int32_t* d_index, double* d_dist, void* stream);
+
+/* skimage.segmentation.expand_labels(lbl, distance, spacing) on the transform above: d_out[p] (Z * Y * X int32, not d_lbl) =
+ * d_lbl[nearest(p)] if sqrt(D) <= distance -- compared on the square root, as scikit-image does -- and 0 otherwise, the features being
+ * the pixels with d_lbl != 0 (negative labels too).  distance = 0 copies; distance = inf has no bound.  d_lbl is not written.  -1
+ * before any launch for a null pointer, d_out == d_lbl, a non-positive extent, more than 2^31 - 1 pixels, a spacing that is not
+ * positive and finite, a distance that is negative or NaN.  Nothing is copied to the host, the stream is not synchronised. */
+int sd_expand_labels_device(const int32_t* d_lbl, int Z, int Y, int X, double sz, double sy, double sx, double distance, int32_t* d_out,
+                            void* stream);
+
 /* Star distances at given pixels only: d_points (n, 2) [(n, 3)] int64 pixel coordinates (y, x) [(z, y, x)], d_dist (n, n_rays) float32.
  * Row p is the row of sd_star_dist2d_device [sd_star_dist3d_device] (grid 1) at that pixel, bit for bit -- 0 for a background pixel --
  * with one difference in what is read: the labels are int32 and are compared by their low 16 bits, the cast to unsigned short that the

@@ -1043,6 +1043,191 @@ def label_components(img, connectivity=None, background=0, *, return_num=False, 
     return (out, n) if return_num else out
 
 
+# ----------------------------------------------------------------------------- nearest-feature transform: expand_labels, distance_transform
+# (csrc/edt_feature.hip).  The host routes are scipy's distance_transform_edt; the device routes equal them, ties included.
+
+def _spacing_zyx(spacing, nd, who):
+    """one positive finite float per axis from a scalar or a sequence, as (sz, sy, sx) with sz = 1.0 for a 2D image, and the per-axis
+    tuple itself"""
+    s = np.asarray(1.0 if spacing is None else spacing, dtype=np.float64)
+    if s.ndim == 0:
+        s = np.full(nd, float(s))
+    if s.shape != (nd,):
+        raise ValueError("%s: the spacing must be a scalar or one value per axis (%d), got shape %r" % (who, nd, s.shape))
+    if not (np.isfinite(s).all() and (s > 0).all()):
+        raise ValueError("%s: the spacing must be positive and finite, got %r" % (who, s.tolist()))
+    per_axis = tuple(float(v) for v in s)
+    return ((1.0,) + per_axis if nd == 2 else per_axis), per_axis
+
+
+def _check_pixel_count(shape, who):
+    if int(np.prod(shape, dtype=np.int64)) > 2 ** 31 - 1:
+        raise ValueError("%s: more than 2^31 - 1 pixels" % who)
+
+
+def _expand_labels_host(lbl, distance, spacing):
+    """scikit-image's expand_labels: scipy's nearest labelled pixel of every background pixel, gathered where it is near enough"""
+    from scipy.ndimage import distance_transform_edt
+    out = np.zeros_like(lbl)
+    if not lbl.any():                                                       # scipy's indices are undefined without a feature
+        return out
+    dist, nearest = distance_transform_edt(lbl == 0, sampling=spacing, return_indices=True)
+    near = dist <= distance
+    out[near] = lbl[tuple(ax[near] for ax in nearest)]
+    return out
+
+
+def _expand_labels_device(lbl, distance, szyx, device):
+    """expand_labels through sd_expand_labels_device; numpy in (uploaded to `device`) -> numpy out, tensor in -> tensor out, of the
+    input's dtype and shape; the labels are non-negative; the input is never written"""
+    import ctypes
+    import torch
+    from .lib import _native as N
+    N.require_device()
+    as_np = isinstance(lbl, np.ndarray)
+    lab, _, ids = _device_labels(lbl, device)
+    out = torch.empty_like(lab)
+    if lab.numel():
+        N.dcall(lab, "sd_expand_labels_device", ctypes.c_void_p(lab.data_ptr()), *_zyx(lab.shape), *szyx, float(distance),
+                ctypes.c_void_p(out.data_ptr()))
+    if as_np:
+        res = to_host(out)
+        return ids[res] if ids is not None else res.astype(lbl.dtype, copy=False)
+    return ids[out.long()] if ids is not None else out.to(lbl.dtype)
+
+
+def expand_labels(lbl, distance=1, spacing=1, *, device=None):
+    """Grow every labelled object of a 2D / 3D label image by up to `distance` without growing into its neighbours, as
+    skimage.segmentation.expand_labels(lbl, distance, spacing) does: a background pixel takes the label of the nearest labelled pixel if
+    that pixel is at most `distance` away (Euclidean, in units of `spacing`: a scalar or one value per axis), and stays 0 otherwise.
+    A pixel equally near to several labels takes the one scipy's distance_transform_edt returns: the nearest pixel with the smallest
+    coordinate along the last axis, then along the axis before it.  distance <= 0 returns a copy.
+
+    Routing, as fill_label_holes and label_components: numpy in without `device` -> the host code (scipy's
+    distance_transform_edt(lbl == 0, sampling=spacing, return_indices=True) and the gather, as scikit-image composes them).  An integer
+    tensor on a HIP device in (or `device=` given) -> a tensor of the same dtype and shape on that device out, equal to the host result
+    (csrc/edt_feature.hip: one exact outward scan per pixel and axis, bounded by `distance`; the input is not written).  numpy in with
+    `device=` -> uploaded, expanded there, numpy out.  Ids beyond int32, or sparse huge ids, are compacted in ascending order for the
+    call and mapped back.  The device route takes non-negative labels: an image with a negative label (a feature like any other, as in
+    scikit-image) goes through the host code and comes back in the input's kind; so does a tensor that is no integer tensor.  An image
+    that is not 2D / 3D, a spacing that is not positive and finite or, on the device, more than 2^31 - 1 pixels raise ValueError before
+    anything runs; an empty image gives an empty result."""
+    is_t = type(lbl).__module__.startswith("torch")
+    if not is_t:
+        lbl = np.asarray(lbl)
+    nd = len(lbl.shape)
+    if nd not in (2, 3):
+        raise ValueError("expand_labels: the label image must be 2D or 3D, got %d dimensions" % nd)
+    szyx, per_axis = _spacing_zyx(spacing, nd, "expand_labels")
+    distance = float(distance)
+    if distance != distance:
+        raise ValueError("expand_labels: the distance is not a number")
+    size = int(np.prod(lbl.shape, dtype=np.int64))
+    if not distance > 0 or size == 0:
+        return lbl.clone() if is_t else lbl.copy()
+    on_device = device is not None or (is_t and lbl.is_cuda)
+    if is_t:
+        import torch
+        if on_device and str(lbl.dtype) in _DEVICE_LABEL_DTYPES and int(lbl.min()) >= 0:
+            _check_pixel_count(lbl.shape, "expand_labels")
+            return _expand_labels_device(lbl, distance, szyx, device)
+        out = _via_host(_expand_labels_host, lbl, distance, per_axis)
+        return out if device is None else out.to(torch.device(device))
+    if on_device and lbl.dtype.kind in "iu" and int(lbl.min()) >= 0:
+        _check_pixel_count(lbl.shape, "expand_labels")
+        return _expand_labels_device(lbl, distance, szyx, device)
+    return _expand_labels_host(lbl, distance, per_axis)
+
+
+def _distance_transform_host(img, per_axis, max_distance, return_distances, return_indices):
+    from scipy.ndimage import distance_transform_edt
+    zero = img == 0
+    if zero.any():
+        dist, idx = distance_transform_edt(img, sampling=per_axis, return_indices=True)
+        idx = idx.astype(np.int32)
+    else:
+        dist, idx = np.full(img.shape, np.inf), np.full((img.ndim,) + img.shape, -1, np.int32)
+    if max_distance is not None:
+        far = dist > max_distance
+        dist[far] = np.inf
+        idx[:, far] = -1
+    return dist if return_distances else None, idx if return_indices else None
+
+
+def _distance_transform_device(img, szyx, max_distance, return_distances, return_indices, device):
+    """(float64 distances or None, (ndim, ...) int32 indices or None) as device tensors, through sd_nearest_feature_device on the
+    uint8 mask img != 0 with the zero pixels as the features"""
+    import ctypes
+    import torch
+    from .lib import _native as N
+    N.require_device()
+    if isinstance(img, np.ndarray):
+        t = torch.as_tensor(np.ascontiguousarray(img != 0).view(np.uint8), device=torch.device("cuda" if device is None else device))
+    else:
+        t = (img if device is None else img.to(torch.device(device)))
+        t = (t != 0).to(torch.uint8).contiguous()
+    dist = torch.empty(t.shape, dtype=torch.float64, device=t.device) if return_distances else None
+    lin = torch.empty(t.shape, dtype=torch.int32, device=t.device) if return_indices else None
+    if t.numel():
+        N.dcall(t, "sd_nearest_feature_device", ctypes.c_void_p(t.data_ptr()), 0, *_zyx(t.shape), 1, *szyx,
+                -1.0 if max_distance is None else float(max_distance),
+                ctypes.c_void_p(lin.data_ptr() if return_indices else None), ctypes.c_void_p(dist.data_ptr() if return_distances else None))
+    idx = None
+    if return_indices:
+        none, rest, axes = lin < 0, lin.clamp(min=0), []
+        for n in reversed(t.shape):
+            axes.append(torch.where(none, lin, rest % n) if n else lin)
+            rest = torch.div(rest, max(n, 1), rounding_mode="floor")
+        idx = torch.stack(axes[::-1]) if t.numel() else torch.empty((t.dim(),) + tuple(t.shape), dtype=torch.int32, device=t.device)
+    return dist, idx
+
+
+def distance_transform(img, sampling=None, *, max_distance=None, return_distances=True, return_indices=False, device=None):
+    """scipy.ndimage.distance_transform_edt(img, sampling, return_distances, return_indices) for a 2D / 3D image: for every non-zero
+    pixel the exact Euclidean distance (float64) to the nearest zero pixel, in units of `sampling` (None: 1; a scalar or one value per
+    axis), and that pixel's coordinates as an (ndim, ...) int32 array; a zero pixel has distance 0 and its own coordinates.  Among
+    equally near zero pixels the indices are scipy's: the smallest coordinate along the last axis, then along the axis before it
+    (DESIGN.md section 3n).  Returns the distances, the indices, or (distances, indices), as scipy does.
+
+    Two departures from scipy.  (1) Where no zero pixel exists, or with max_distance given none lies within it, the distance is inf
+    and the indices are -1 (scipy leaves an image without a zero pixel undefined and has no bound).  (2) Time: on the device every pixel
+    scans outwards along each axis until the axis term alone exceeds its best distance, so an unbounded call costs time proportional
+    to the largest distance in the result -- small for images of nuclei, large for a lone zero pixel in a big image.  max_distance
+    bounds the scans.
+
+    Routing: numpy in without `device` -> scipy on the host, numpy out.  A tensor on a HIP device in (or `device=` given) ->
+    csrc/edt_feature.hip, equal to the host result; tensors on that device out for a tensor, numpy for numpy.  A host tensor without
+    `device` -> the host code, host tensors out.  An image that is not 2D / 3D, a sampling that is not positive and finite, a negative
+    or NaN max_distance, neither result asked for or, on the device, more than 2^31 - 1 pixels raise ValueError before anything
+    runs; an empty image gives empty results."""
+    is_t = type(img).__module__.startswith("torch")
+    if not is_t:
+        img = np.asarray(img)
+    nd = len(img.shape)
+    if nd not in (2, 3):
+        raise ValueError("distance_transform: the image must be 2D or 3D, got %d dimensions" % nd)
+    szyx, per_axis = _spacing_zyx(sampling, nd, "distance_transform")
+    if max_distance is not None:
+        max_distance = float(max_distance)
+        if not max_distance >= 0:
+            raise ValueError("distance_transform: max_distance must be >= 0 or None")
+        if max_distance == np.inf:
+            max_distance = None
+    if not (return_distances or return_indices):
+        raise ValueError("distance_transform: at least one of return_distances / return_indices must be True")
+    if device is not None or (is_t and img.is_cuda):
+        _check_pixel_count(img.shape, "distance_transform")
+        dist, idx = _distance_transform_device(img, szyx, max_distance, return_distances, return_indices, device)
+        if not is_t:
+            dist, idx = to_host_many([dist, idx])
+    else:
+        dist, idx = _distance_transform_host(img.numpy() if is_t else img, per_axis, max_distance, return_distances, return_indices)
+        if is_t:
+            import torch
+            dist, idx = (None if a is None else torch.from_numpy(a) for a in (dist, idx))
+    return (dist, idx) if return_distances and return_indices else (dist if return_distances else idx)
+
+
 def mask_to_categorical(y, n_classes, classes, return_cls_dict=False):
     """The multi-channel class map of the integer label array y (stardist/utils.py:318-380): float32 of shape y.shape + (n_classes + 1,),
     the first channel the background.  classes: a dict label id -> class id (0 = background class, 1 ... n_classes = that object class,

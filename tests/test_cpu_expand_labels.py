@@ -1,0 +1,347 @@
+"""CPU: stardist_amd.utils.expand_labels and distance_transform on host input.  The brute-force statement of the definition
+(tests/_expand_cases.py: every feature, the squared distance in its stated order, ties by the stated rule) against scipy's
+distance_transform_edt -- indices and distances -- and against the host route; the host route against scikit-image 0.18's
+expand_labels (tests/golden/expand_labels_reference.npz); the passes of the device code (csrc/edt_feature.h through
+tests/host/edt_feature_check.cpp) against the reference, and once more under the address and undefined-behaviour sanitizers as a
+stand-alone program.  All comparisons are exact."""
+import ctypes
+import os
+import re
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import _expand_cases as C
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "host", "edt_feature_check.cpp")
+_vp, _i, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+DTYPE_CODE = {"uint8": 0, "uint16": 1, "int32": 3}
+
+
+def expand(*a, **kw):
+    from stardist_amd.utils import expand_labels
+    return expand_labels(*a, **kw)
+
+
+def transform(*a, **kw):
+    from stardist_amd.utils import distance_transform
+    return distance_transform(*a, **kw)
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def zyx(shape):
+    return ((1,) + tuple(shape)) if len(shape) == 2 else tuple(shape)
+
+
+def szyx(spacing):
+    return ((1.0,) + tuple(spacing)) if len(spacing) == 2 else tuple(spacing)
+
+
+as_int32 = C.as_int32
+
+
+@pytest.fixture(scope="module")
+def lib(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("edt_feature") / "libedt_feature.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", SRC, "-o", so], check=True)
+    l = ctypes.CDLL(so)
+    l.edtf_threads.restype = _i
+    l.edtf_nearest.restype = l.edtf_expand.restype = _i
+    l.edtf_nearest.argtypes = [_vp, _i, _i, _i, _i, _i, _d, _d, _d, _d, _vp, _vp]
+    l.edtf_expand.argtypes = [_vp, _i, _i, _i, _d, _d, _d, _d, _vp]
+    return l
+
+
+def harness_nearest(lib, a, spacing, max_distance=-1.0, feature_is_zero=0, want_index=True, want_dist=True):
+    a = np.ascontiguousarray(a)
+    index, dist = np.full(a.shape, -7, np.int32), np.full(a.shape, -7.0)
+    rc = lib.edtf_nearest(a.ctypes.data, DTYPE_CODE[a.dtype.name], *zyx(a.shape), feature_is_zero, *szyx(spacing), max_distance,
+                          index.ctypes.data if want_index else None, dist.ctypes.data if want_dist else None)
+    assert rc == 0
+    return index, dist
+
+
+def harness_expand(lib, a, spacing, distance):
+    a = np.ascontiguousarray(a)
+    out = np.full(a.shape, -7, np.int32)
+    assert lib.edtf_expand(a.ctypes.data, *zyx(a.shape), *szyx(spacing), distance, out.ctypes.data) == 0
+    return out
+
+
+def test_cases_are_what_they_say(lib):
+    assert lib.edtf_threads() == C.THREADS
+    for name in C.NAMES:
+        a = C.case(name)
+        assert a.flags["C_CONTIGUOUS"] and a.size <= 400000 and a.ndim in (2, 3) and a.dtype.name in ("uint8", "uint16", "int32", "int64"), name
+        assert (name in C.SMALL) == (a.size <= C.BRUTE_LIMIT)
+    assert {C.case(n).ndim for n in C.BIG} == {2, 3} and all(C.case(n).size > 40000 for n in C.BIG)
+    for shape in (C.IMAGE, C.VOLUME, C.case("discs_big").shape, C.case("balls_big").shape):
+        assert shape[-1] % 64 and np.prod(shape) > 2 * C.THREADS and np.prod(shape[1:]) % C.THREADS       # partial last workgroup, several
+    assert {C.case(n).dtype.name for n in C.NAMES} == {"uint8", "uint16", "int32", "int64"}
+    assert C.case("high_labels").max() == 2 ** 31 - 1 and C.case("discs_i64").max() > 2 ** 40 and C.case("discs_u16").max() > 2 ** 15
+    for name in C.NO_FEATURE:
+        assert not C.case(name).any()
+    assert C.case("all_labelled").all() and C.case("all_labelled3d").all() and len(np.unique(C.case("all_labelled"))) == 5
+    assert C.case("one_row").shape[0] == 1 and C.case("one_column").shape[1] == 1 and C.case("plane_as_volume").shape[0] == 1
+    assert C.case("single_pixel").shape == (1, 1) and C.case("single_pixel")[0, 0] != 0
+    for name in ("corner", "far_corner", "corner3d", "far_corner3d"):
+        a = C.case(name)
+        (at,) = np.argwhere(a)
+        assert all(c in (0, n - 1) for c, n in zip(at, a.shape)), name
+    for name in ("points", "points3d", "lattice", "lattice3d", "high_labels", "one_row"):      # single pixels, all labels different
+        a = C.case(name)
+        assert len(np.unique(a[a != 0])) == (a != 0).sum() > 5, name
+    for name in C.DISCS:                                                    # touching / overlapping: different labels side by side
+        a = C.case(name)
+        side = (a[..., 1:] != a[..., :-1]) & (a[..., 1:] != 0) & (a[..., :-1] != 0)
+        assert side.sum() > 10 and len(np.unique(a)) > 6, name
+    for name in C.NAMES:
+        d = C.distances(name)
+        assert d[:3] == (0.0, 1.0, 1.5) and d[3] == np.sqrt(2.0) and d[4] < d[3] and np.nextafter(d[4], 2.0) == d[3] and d[5:7] == (3.0, 6.5)
+        assert d[7] > 2.0 * np.sqrt(sum(n * n for n in C.case(name).shape))               # beyond the diagonal at the largest spacing
+
+
+def test_ties_between_different_labels_exist_and_are_a_minority():
+    row = np.array([[3, 0, 0, 0, 4, 0, 0, 0, 4]], np.int32)                 # the helper itself: the midpoint of 3 and 4, not that of 4 and 4
+    assert np.array_equal(np.argwhere(C.ambiguous(row, (1.0, 1.0))), [[0, 2]])
+    for name in C.TIED:
+        for spacing in C.spacings(name)[:2]:                                # unit and dyadic spacing: exact integer and dyadic ties
+            if name in C.SMALL:
+                assert C.ambiguous_case(name, spacing).sum() >= 5, (name, spacing)
+    lat = C.ambiguous_case("lattice", (1.0, 1.0))
+    assert lat[1, 3] and lat[3, 1] and lat[3, 3] and not lat[1, 1] and not lat[1, 2]        # midpoints of pitch 4; features at 1, 5, ...
+    for name in C.RANDOMISED:
+        if name not in C.SMALL:
+            continue
+        for spacing in C.spacings(name):
+            a = C.case(name)
+            _, dist = C.reference(name, spacing)
+            grown = (a == 0) & (dist <= 6.5)
+            share = (C.ambiguous_case(name, spacing) & grown).sum() / max(grown.sum(), 1)
+            assert grown.sum() > 100 and share < 0.5, (name, spacing, share)
+            if name in C.DISCS:
+                assert share <= 0.10, (name, spacing, share)
+
+
+@pytest.mark.parametrize("name", C.SMALL)
+def test_brute_force_equals_scipy(name):
+    a = C.case(name)
+    for spacing in C.spacings(name):
+        index, dist = C.reference(name, spacing)
+        s_index, s_dist = C.scipy_reference(a, spacing)
+        assert same_bits(index, s_index) and same_bits(dist, s_dist), (name, spacing)
+    if a.any() and not a.all():                                             # the other orientation: the background as the features
+        index, dist = C.brute(a, C.spacings(name)[2], feature_is_zero=True)
+        s_index, s_dist = C.scipy_reference(a, C.spacings(name)[2], feature_is_zero=True)
+        assert same_bits(index, s_index) and same_bits(dist, s_dist), name
+
+
+@pytest.mark.parametrize("name", C.NAMES)
+def test_host_route_equals_reference(name):
+    a = C.case(name)
+    for spacing in C.spacings(name):
+        index, dist = C.reference(name, spacing)
+        for distance in C.distances(name):
+            got = expand(a, distance, spacing)
+            assert same_bits(got, C.expanded(a, index, dist, distance)), (name, spacing, distance)
+            assert got is not a and np.array_equal(got != 0, (dist <= distance) if distance > 0 else a != 0)
+    assert same_bits(expand(a), expand(a, 1, 1)) and same_bits(expand(a, 3, 1), expand(a, 3.0, (1.0,) * a.ndim))
+    assert same_bits(expand(a, 3, 2), expand(a, 3, (2,) * a.ndim)) and same_bits(expand(a, -1), a)
+
+
+def test_boundary_is_less_or_equal():
+    a = np.zeros((5, 5), np.int32)
+    a[2, 2] = 9
+    at, below = expand(a, C.SQRT2), expand(a, float(np.nextafter(C.SQRT2, 0)))
+    assert at.sum() == 9 * 9 and below.sum() == 9 * 5 and at[1, 1] == 9 and below[1, 1] == 0
+    assert expand(a, 1.3, (1.3, 0.7))[1, 2] == 9 and expand(a, float(np.nextafter(1.3, 0)), (1.3, 0.7))[1, 2] == 0
+
+
+def test_host_route_equals_scikit_image_golden():
+    g = np.load(os.path.join(ROOT, "tests", "golden", "expand_labels_reference.npz"))
+    names = sorted(set(k.split("/")[0] for k in g.files))
+    assert len(names) >= 10 and {C.case(n).ndim for n in names} == {2, 3} and "lattice" in names and "discs_big" in names
+    for name in names:
+        a = C.case(name)
+        assert same_bits(a, g[name + "/lbl"]), name
+        for k, distance in enumerate(C.distances(name)):
+            assert float(g["%s/d%d/distance" % (name, k)]) == distance
+            assert same_bits(expand(a, distance), g["%s/d%d/out" % (name, k)]), (name, distance)
+
+
+@pytest.mark.parametrize("name", [n for n in C.NAMES])
+def test_harness_equals_reference(lib, name):
+    a = as_int32(C.case(name))
+    narrow = C.case(name) if C.case(name).dtype.name in DTYPE_CODE else a
+    for spacing in C.spacings(name):
+        index, dist = C.reference(name, spacing)
+        got_index, got_dist = harness_nearest(lib, narrow, spacing)
+        assert same_bits(got_index, index) and same_bits(got_dist, dist), (name, spacing)
+        for distance in C.distances(name):
+            assert same_bits(harness_expand(lib, a, spacing, distance), C.expanded(a, index, dist, distance)), (name, spacing, distance)
+            b_index, b_dist = harness_nearest(lib, narrow, spacing, distance)
+            w_index, w_dist = C.bounded(index, dist, distance)
+            assert same_bits(b_index, w_index) and same_bits(b_dist, w_dist), (name, spacing, distance)
+    spacing = C.spacings(name)[2]
+    index, dist = C.reference(name, spacing)
+    only_index, untouched = harness_nearest(lib, narrow, spacing, want_dist=False)
+    assert same_bits(only_index, index) and (untouched == -7.0).all()
+    untouched, only_dist = harness_nearest(lib, narrow, spacing, want_index=False)
+    assert same_bits(only_dist, dist) and (untouched == -7).all()
+    if name in C.SMALL:
+        z_index, z_dist = harness_nearest(lib, narrow, spacing, feature_is_zero=1)
+        w_index, w_dist = C.brute(C.case(name), spacing, feature_is_zero=True)
+        assert same_bits(z_index, w_index) and same_bits(z_dist, w_dist)
+
+
+def test_harness_argument_checks(lib):
+    a, out, dist = np.ones((4, 4), np.int32), np.zeros((4, 4), np.int32), np.zeros((4, 4))
+    near = lambda *args: lib.edtf_nearest(*args, out.ctypes.data, dist.ctypes.data)
+    assert near(a.ctypes.data, 3, 1, 4, 4, 0, 1.0, 1.0, 1.0, -1.0) == 0 and near(a.ctypes.data, 3, 1, 4, 4, 1, 1.0, 1.0, 1.0, np.inf) == 0
+    for bad in ((None, 3, 1, 4, 4, 0, 1.0, 1.0, 1.0, -1.0), (a.ctypes.data, 2, 1, 4, 4, 0, 1.0, 1.0, 1.0, -1.0),
+                (a.ctypes.data, 3, 0, 4, 4, 0, 1.0, 1.0, 1.0, -1.0), (a.ctypes.data, 3, 1, 4, 4, 2, 1.0, 1.0, 1.0, -1.0),
+                (a.ctypes.data, 3, 1, 4, 4, 0, 1.0, 0.0, 1.0, -1.0), (a.ctypes.data, 3, 1, 4, 4, 0, 1.0, 1.0, np.nan, -1.0),
+                (a.ctypes.data, 3, 1, 4, 4, 0, np.inf, 1.0, 1.0, -1.0), (a.ctypes.data, 3, 1, 4, 4, 0, 1.0, 1.0, 1.0, np.nan),
+                (a.ctypes.data, 3, 2, 2 ** 15, 2 ** 15, 0, 1.0, 1.0, 1.0, -1.0)):
+        assert near(*bad) == -1, bad
+    grow = lambda *args: lib.edtf_expand(*args)
+    assert grow(a.ctypes.data, 1, 4, 4, 1.0, 1.0, 1.0, 0.0, out.ctypes.data) == 0
+    for bad in ((None, 1, 4, 4, 1.0, 1.0, 1.0, 1.0, out.ctypes.data), (a.ctypes.data, 1, 4, 4, 1.0, 1.0, 1.0, 1.0, None),
+                (a.ctypes.data, 1, 4, 4, 1.0, 1.0, 1.0, 1.0, a.ctypes.data), (a.ctypes.data, 1, 4, 4, 1.0, 1.0, 1.0, -1.0, out.ctypes.data),
+                (a.ctypes.data, 1, 4, 4, 1.0, 1.0, 1.0, np.nan, out.ctypes.data), (a.ctypes.data, 1, 4, -4, 1.0, 1.0, 1.0, 1.0, out.ctypes.data),
+                (a.ctypes.data, 1, 4, 4, 1.0, -1.0, 1.0, 1.0, out.ctypes.data)):
+        assert grow(*bad) == -1, bad
+
+
+def test_stand_alone_sanitizer_build_passes_every_case(tmp_path):
+    exe, cases = str(tmp_path / "edt_feature_check"), str(tmp_path / "cases.bin")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-DEDT_FEATURE_CHECK_MAIN", SRC, "-o", exe], check=True)
+    records = 0
+    with open(cases, "wb") as f:
+        for name in C.NAMES:
+            a = as_int32(C.case(name))
+            narrow = C.case(name) if C.case(name).dtype.name in DTYPE_CODE else a
+            for spacing in C.spacings(name):
+                index, dist = C.reference(name, spacing)
+                for distance in C.distances(name)[1::2] if name in C.BIG else C.distances(name):
+                    f.write(struct.pack("<6i4d", 1, 3, *zyx(a.shape), 0, *szyx(spacing), distance))
+                    f.write(a.tobytes() + np.ascontiguousarray(C.expanded(a, index, dist, distance), "<i4").tobytes())
+                    records += 1
+                for bound in (-1.0, 3.0):
+                    w_index, w_dist = (index, dist) if bound < 0 else C.bounded(index, dist, bound)
+                    f.write(struct.pack("<6i4d", 0, DTYPE_CODE[narrow.dtype.name], *zyx(a.shape), 0, *szyx(spacing), bound))
+                    f.write(narrow.tobytes() + np.ascontiguousarray(w_index, "<i4").tobytes() + np.ascontiguousarray(w_dist, "<f8").tobytes())
+                    records += 1
+    r = subprocess.run([exe, cases], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "%d records, 0 bad" % records in r.stdout
+
+
+@pytest.mark.parametrize("name", ("discs", "lattice", "balls", "lattice3d", "no_feature", "all_labelled", "one_column", "discs_big"))
+def test_distance_transform_host_route_equals_scipy(name):
+    from scipy.ndimage import distance_transform_edt
+    a = C.case(name)
+    for img in (a, a == 0):                                                 # distances inside the objects; distances to the objects
+        for spacing in C.spacings(name):
+            if not (img == 0).any():
+                dist, idx = transform(img, spacing, return_indices=True)
+                assert np.isinf(dist).all() and (idx == -1).all() and idx.shape == (a.ndim,) + a.shape and idx.dtype == np.int32
+                continue
+            want, want_idx = distance_transform_edt(img, sampling=spacing, return_indices=True)
+            dist, idx = transform(img, spacing, return_indices=True)
+            assert same_bits(dist, want) and same_bits(idx, want_idx), (name, spacing)
+            assert same_bits(transform(img, spacing), want) and same_bits(transform(img, spacing, return_distances=False, return_indices=True), idx)
+            for bound in (0.0, 1.0, C.SQRT2, 3.0, 1e9, np.inf):
+                far = want > bound
+                dist, idx = transform(img, spacing, max_distance=bound, return_indices=True)
+                assert same_bits(dist, np.where(far, np.inf, want)) and same_bits(idx, np.where(far[None], np.int32(-1), want_idx)), (name, bound)
+    assert same_bits(transform(a), distance_transform_edt(a)) or not (a == 0).any()
+    assert same_bits(transform(a, 2.0), transform(a, (2.0,) * a.ndim))
+
+
+def test_arguments_and_routing(monkeypatch):
+    import torch
+    from stardist_amd import utils
+    monkeypatch.setattr(utils, "_expand_labels_device", lambda *a, **k: pytest.fail("device path taken"))
+    monkeypatch.setattr(utils, "_distance_transform_device", lambda *a, **k: pytest.fail("device path taken"))
+    a = C.case("discs")
+    want = expand(a, 3, (2.0, 0.5))
+    assert np.array_equal(expand(a.tolist(), 3, (2.0, 0.5)), want)
+    for dt in ("uint8", "uint16", "int32", "int64", "float32"):
+        got = expand(a.astype(dt), 3, (2.0, 0.5))
+        assert got.dtype == np.dtype(dt) and np.array_equal(got, want)
+    t = expand(torch.from_numpy(a.copy()), 3, (2.0, 0.5))                   # a host tensor: the host code, a host tensor out
+    assert isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device.type == "cpu" and np.array_equal(t.numpy(), want)
+    neg = np.where(a == 2, -2, a)                                           # a negative label is a feature like any other
+    grown = expand(neg, 3)
+    assert np.array_equal(grown == -2, expand(a, 3) == 2) and (grown == -2).sum() > (a == 2).sum()
+    assert np.array_equal(expand(neg, 3, device="cuda"), grown)             # ... and takes the host code on the device route too
+    for name, shape in zip(("a", "b", "c", "d", "e"), C.EMPTY_SHAPES):
+        e = expand(np.zeros(shape, np.uint16), 2)
+        assert e.shape == shape and e.dtype == np.uint16
+        d, i = transform(np.zeros(shape, np.uint8), return_indices=True)
+        assert d.shape == shape and d.dtype == np.float64 and i.shape == (len(shape),) + shape and i.dtype == np.int32
+    for dev in (None, "cuda"):                                              # the same errors, before anything runs, on both routes
+        for fn in (expand, lambda x, **k: transform(x, **k)):
+            with pytest.raises(ValueError, match="2D or 3D"):
+                fn(np.zeros(7, np.uint8), device=dev)
+            with pytest.raises(ValueError, match="2D or 3D"):
+                fn(np.zeros((2, 3, 4, 5), np.uint8), device=dev)
+        for bad in (0, -1.0, (1.0, 0.0), (1.0, np.nan), (1.0, np.inf), (1.0, 2.0, 3.0), ((1.0, 2.0),)):
+            with pytest.raises(ValueError, match="spacing"):
+                expand(a, 2, bad, device=dev)
+            with pytest.raises(ValueError, match="spacing"):
+                transform(a, bad, device=dev)
+        with pytest.raises(ValueError, match="not a number"):
+            expand(a, np.nan, device=dev)
+        for bad in (-1.0, np.nan):
+            with pytest.raises(ValueError, match="max_distance"):
+                transform(a, max_distance=bad, device=dev)
+        with pytest.raises(ValueError, match="at least one"):
+            transform(a, return_distances=False, device=dev)
+    d = transform(torch.from_numpy(a.copy()), (1.3, 0.7))                   # a host tensor: the host code, host tensors out
+    assert isinstance(d, torch.Tensor) and d.dtype == torch.float64 and same_bits(d.numpy(), transform(a, (1.3, 0.7)))
+    import stardist_amd
+    assert not hasattr(stardist_amd, "expand_labels")                       # the top-level names mirror the reference's exports
+
+
+def test_device_route_is_taken_for_integer_labels(monkeypatch):
+    from stardist_amd import utils
+    seen = []
+
+    def fake(lbl, distance, szyx, device):
+        seen.append((str(lbl.dtype), distance, szyx, device))
+        raise RuntimeError("stop")
+    monkeypatch.setattr(utils, "_expand_labels_device", fake)
+    for dt in ("uint8", "uint16", "int32", "int64"):
+        with pytest.raises(RuntimeError, match="stop"):
+            expand(np.ones((3, 4), dt), 2, (2, 0.5), device="cuda")
+    assert seen == [(dt, 2.0, (1.0, 2.0, 0.5), "cuda") for dt in ("uint8", "uint16", "int32", "int64")]
+    with pytest.raises(RuntimeError, match="stop"):
+        expand(np.ones((2, 3, 4), np.int32), 1, device="cuda")
+    assert seen[-1] == ("int32", 1.0, (1.0, 1.0, 1.0), "cuda")
+    assert expand(np.ones((3, 4), np.float32), 2, device="cuda").dtype == np.float32           # the host code, numpy out
+    assert same_bits(expand(np.ones((3, 4), np.int32), 0, device="cuda"), np.ones((3, 4), np.int32))      # a copy: nothing to run
+    assert len(seen) == 5
+
+
+def test_header_and_library_agree_on_the_new_symbols():
+    from stardist_amd.lib import _native as N
+    txt = open(os.path.join(ROOT, "include", "stardist_hip.h")).read()
+    for name in ("sd_nearest_feature_device", "sd_expand_labels_device"):
+        (params,) = re.findall(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, txt)
+        res, args = N.SIGNATURES[name]
+        assert res is ctypes.c_int and len(args) == len(params.split(",")), name
+        for arg, param in zip(args, params.split(",")):
+            want = ctypes.c_double if param.strip().startswith("double ") else (ctypes.c_int if param.strip().startswith("int ") else _vp)
+            assert arg is want, (name, param)
+        fn = getattr(N.lib(), name)                                         # exported by the built library
+        assert fn.restype is ctypes.c_int and list(fn.argtypes) == list(args)

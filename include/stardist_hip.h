@@ -726,6 +726,19 @@ int sd_nearest_feature_device(const void* d_img, int dtype, int Z, int Y, int X,
 int sd_expand_labels_device(const int32_t* d_lbl, int Z, int Y, int X, double sz, double sy, double sx, double distance, int32_t* d_out,
                             void* stream);
 
+/* The augmentation chain of a training batch (stardist_amd.augment.Compose.apply_device; the rules are csrc/augment.h's) in ONE launch:
+ * d_x (B, *shape) float32 and d_y (B, *shape) int32, nd = 2 or 3 extents in h_shape, give d_out_x and d_out_y of the same shapes
+ * (not the inputs): per sample FlipRot90 (always, as an index map), then Warp (flags bit 0; bit 1: mode 'reflect', else 'constant'),
+ * then on the image IntensityScaleShift (bit 2) and AdditiveNoise (bit 3).  The table holds one 168-byte row per sample (struct
+ * augment::Sample): h_table on the host, read here to check that every index map stays inside its patch, d_table the same bytes on
+ * the device, uploaded by the caller in one copy.  d_disp: (B, n_disp, *shape) float32 displacements added to the warp coordinates of
+ * the axes a row names, or NULL with n_disp = 0.  Equal to the host route (numpy, scipy.ndimage.map_coordinates of order 1 / 0) bit
+ * for bit, NaN for NaN; no atomics, the same bits from call to call.  -1 before the launch for a null pointer, an output that is an
+ * input, nd outside 2 / 3, B outside 1 .. 65535, an extent < 1, more than 2^31 - 1 pixels per sample, unknown flags, a displacement
+ * field without a Warp, a row whose map leaves the patch.  Nothing is copied to the host, the stream is not synchronised. */
+int sd_augment_batch_device(const float* d_x, const int32_t* d_y, int B, int nd, const int* h_shape, int flags, const void* h_table,
+                            const void* d_table, const float* d_disp, int n_disp, float* d_out_x, int32_t* d_out_y, void* stream);
+
 /* Star distances at given pixels only: d_points (n, 2) [(n, 3)] int64 pixel coordinates (y, x) [(z, y, x)], d_dist (n, n_rays) float32.
  * Row p is the row of sd_star_dist2d_device [sd_star_dist3d_device] (grid 1) at that pixel, bit for bit -- 0 for a background pixel --
  * with one difference in what is read: the labels are int32 and are compared by their low 16 bits, the cast to unsigned short that the

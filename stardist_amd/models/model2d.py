@@ -138,7 +138,9 @@ class StarDist2D(StarDistBase):
         validation_data may then be (X_val, Y_val, classes_val), a pair means 'auto'.  With n_classes > 1, 'auto' is out of scope
         (NotImplementedError; the reference raises ValueError).  A label that its image's dict does not hold raises the reference's
         ValueError, for the training data at the end of the epoch that met it.  A single-class model ignores anything but 'auto' / None
-        with the reference's warning.  workers: accepted for the reference's signature, the host part of the data pipeline runs in the
+        with the reference's warning.  augmenter: None, a callable (x, y) -> (x, y) that runs on the host once per sample, or a
+        stardist_amd.augment.Compose (flips, warps, intensity, noise), which augments each batch on the device with the same result.
+        workers: accepted for the reference's signature, the host part of the data pipeline runs in the
         calling thread.
         Returns a History (training.History: a dict of per-epoch lists, also reachable as .history, with .epoch and .params) with the
         keys of the reference's Keras history: loss, prob_loss, dist_loss, prob_kld, dist_relevant_mae, dist_relevant_mse,

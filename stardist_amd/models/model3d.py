@@ -142,7 +142,9 @@ class StarDist3D(StarDistBase):
         X: input volumes (3D, no channel axis), Y: label volumes (negative values switch the losses off there), validation_data:
         (X_val, Y_val).  With a model folder, weights_best.npz / weights_last.npz are written there and the best weights are loaded at
         the end.  classes and a third entry of validation_data: as in StarDist2D.train (a model with n_classes; a single-class model
-        ignores anything but 'auto' / None with the reference's warning); workers: accepted for the reference's signature, the host
+        ignores anything but 'auto' / None with the reference's warning).  augmenter: None, a callable (x, y) -> (x, y) that runs on the host once per sample, or a
+        stardist_amd.augment.Compose (flips, warps, intensity, noise), which augments each batch on the device with the same result.
+        workers: accepted for the reference's signature, the host
         part of the data pipeline runs in the calling thread.
         Returns a History (training.History: a dict of per-epoch lists, also reachable as .history, with .epoch and .params) with the
         keys of the reference's Keras history: loss, prob_loss, dist_loss, prob_kld, dist_relevant_mae, dist_relevant_mse,

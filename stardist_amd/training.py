@@ -5,7 +5,9 @@ volumes (B, D, H, W, C): an image is the D = 1, kz = 1 case of the same native c
 
   patches      sample_patches / get_valid_inds (stardist/sample_patches.py), StarDistDataBase.get_valid_inds (base.py:129-224) and
                csbdeep's RollingSequence.batch / utils.choice, restated with the same np.random draws in the same order: np.random.seed(s)
-               gives the reference's patches.  The augmenter runs on the host, as there.
+               gives the reference's patches.  A plain augmenter callable runs on the host, as there; a stardist_amd.augment.Compose
+               runs on the device when the batch goes there: the host draws its parameters where it would have called it (the same
+               np.random stream), the raw patches go up, one launch augments the batch and the targets start from the device labels.
   targets      one upload of the batch's label patches; prob (edt_prob of the grid-subsampled labels) and dist (star_dist with the grid) on
                the device by sd_edt_prob_device / sd_star_dist2d_device: equal to stardist_targets() bit for bit.
   forward      the exact-f32 kernels of inference (sd_conv3_ndhwc_device per sample; sd_maxpool_ndhwc_device, for images with the batch
@@ -178,13 +180,35 @@ class TrainData2D(object):
             return self.get_valid_inds(k, foreground_prob=0)
         return inds
 
-    def sample(self, i):
-        """(X, Y): the batch's image and label patches (tuples of 2D arrays) after the augmenter"""
+    def sample(self, i, draw_only=False):
+        """(X, Y): the batch's image and label patches (tuples of 2D arrays) after the augmenter.  draw_only (an augmenter with draw()):
+        (X, Y, params) with the raw patches and, drawn where the augmenter would have been called, each sample's parameters"""
         idx = self.batch(i)
         arrays = [sample_patches((self.Y[k], self.X[k]), patch_size=self.patch_size, n_samples=1, valid_inds=self.get_valid_inds(k)) for k in idx]
         X, Y = list(zip(*[(x[0], y[0]) for y, x in arrays]))
+        if draw_only:
+            return X, Y, [self.augmenter.draw(_x.shape) for _x in X]
         X, Y = tuple(zip(*tuple(self.augmenter(_x, _y) for _x, _y in zip(X, Y))))
         return X, Y
+
+    def augments_on(self, device):
+        """whether batches for `device` take the device route: an augmenter with draw() and apply_device(), and a HIP device"""
+        return hasattr(self.augmenter, "draw") and hasattr(self.augmenter, "apply_device") and torch.device(device).type == "cuda"
+
+    def patches(self, i, device):
+        """(x, labels) of batch i: x float32 (B, *patch) on `device`; labels the augmented label patches, as a tuple of host arrays
+        (the augmenter ran on the host) or, on the device route, as one int32 tensor (B, *patch) on the device"""
+        if not self.augments_on(device):
+            X, Y = self.sample(i)
+            return torch.from_numpy(np.ascontiguousarray(np.stack(X), np.float32)).to(device, non_blocking=False), Y
+        X, Y, params = self.sample(i, draw_only=True)
+        lab = np.stack(Y)
+        if lab.dtype.kind not in "iub" or lab.dtype.itemsize > 4 or lab.dtype == np.uint32:
+            if lab.size and (int(lab.max()) >= 2 ** 31 or int(lab.min()) < -2 ** 31):
+                raise ValueError("label ids must fit int32")
+        x = torch.from_numpy(np.ascontiguousarray(np.stack(X), np.float32)).to(device, non_blocking=False)
+        y = torch.from_numpy(np.ascontiguousarray(lab, np.int32)).to(device)
+        return self.augmenter.apply_device(x, y, params)
 
     def batch_classes(self, i):
         """what the targets functions take as `classes` for batch i: (the class tables, the batch's image indices), or None for a
@@ -194,9 +218,8 @@ class TrainData2D(object):
     def batch_device(self, i, device):
         """x (B, H, W, 1), prob_true (B, h, w), dist_true_mask (B, h, w, n_rays + 1): float32 device tensors; with n_classes also
         prob_class_true (B, h, w, n_classes + 1)"""
-        X, Y = self.sample(i)
-        x = torch.from_numpy(np.ascontiguousarray(np.stack(X)[..., None], np.float32)).to(device, non_blocking=False)
-        return (x,) + targets_device(Y, self.n_rays, self.grid, device, self.batch_classes(i))
+        x, Y = self.patches(i, device)
+        return (x[..., None],) + targets_device(Y, self.n_rays, self.grid, device, self.batch_classes(i))
 
 
 def _upload_labels(Y, grid, device):
@@ -221,26 +244,48 @@ def _finish_targets(prob, dist, neg):
     """the end of both: (prob_true, dist_true_mask) from the device tensors prob and dist, prob_true = -1 where the label is negative"""
     dtm = torch.cat([dist, prob[..., None]], dim=-1).contiguous()
     if neg is not None:
-        prob[torch.from_numpy(np.stack(neg)).to(prob.device)] = -1
+        prob[neg if torch.is_tensor(neg) else torch.from_numpy(np.stack(neg)).to(prob.device)] = -1
     return prob, dtm
 
 
+def _device_labels(d_raw, grid, on_grid):
+    """_upload_labels for label patches that are on the device already (int32 (B, *patch), after a device augmenter): (ranges, neg,
+    d_lab, d_u16) with the same clip (every sample, if any label ON THE GRID is negative), neg the mask of negative labels on the grid
+    as a device tensor (None if there are none) and ranges the (min, max) per sample of what the host route looks at -- the clipped
+    labels on the grid (on_grid, 2D) or of the whole patch (3D) -- from ONE read-back of 4 numbers per sample"""
+    B = int(d_raw.shape[0])
+    sub = d_raw[(slice(None),) + tuple(slice(None, None, int(g)) for g in grid)]
+    lo_s, hi_s = torch.aminmax(sub.reshape(B, -1), dim=1)
+    lo_f, hi_f = (lo_s, hi_s) if all(int(g) == 1 for g in grid) else torch.aminmax(d_raw.reshape(B, -1), dim=1)
+    st = torch.stack([lo_s, hi_s, lo_f, hi_f], dim=1).cpu().numpy()
+    lo, hi = (st[:, 0], st[:, 1]) if on_grid else (st[:, 2], st[:, 3])
+    neg, d_lab = None, d_raw.contiguous()
+    if (st[:, 0] < 0).any():
+        neg, d_lab = sub < 0, d_lab.clamp_min(0)
+        lo, hi = np.maximum(lo, 0), np.maximum(hi, 0)
+    return [(int(a), int(b)) for a, b in zip(lo, hi)], neg, d_lab, d_lab.to(torch.uint16).contiguous()
+
+
 def targets_device(Y, n_rays, grid, device, classes=None):
-    """the targets of StarDistData2D.__getitem__ (model2d.py:63-119, shape_completion=False) for the label images Y (one shape) from ONE
+    """the targets of StarDistData2D.__getitem__ (model2d.py:63-119, shape_completion=False) for the label images Y (one shape; host
+    arrays, or one int32 tensor (B, H, W) on the device, which is then not uploaded but asked for its ranges) from ONE
     upload: prob_true (B, h, w) (-1 where the label is negative) and dist_true_mask (B, h, w, n_rays + 1) on `device`; with classes =
     (ClassTables, the images' indices into them) also prob_class_true (B, h, w, n_classes + 1)"""
     from .utils import edt_prob
     gy, gx = int(grid[0]), int(grid[1])
-    lab, neg, d_lab, d_u16 = _upload_labels(Y, grid, device)
-    B, H, W = lab.shape
+    if torch.is_tensor(Y):
+        ranges, neg, d_lab, d_u16 = _device_labels(Y, grid, True)
+    else:
+        lab, neg, d_lab, d_u16 = _upload_labels(Y, grid, device)
+        ranges = [(int(sub.min()), int(sub.max())) if sub.size else (0, 0) for sub in (lab[b, ::gy, ::gx] for b in range(len(lab)))]
+    B, H, W = (int(n) for n in d_lab.shape)
     d_sub = d_lab[:, ::gy, ::gx].contiguous()
     h, w = int(d_sub.shape[1]), int(d_sub.shape[2])
     prob = torch.empty((B, h, w), dtype=torch.float32, device=device)
     dist = torch.empty((B, h, w, n_rays), dtype=torch.float32, device=device)
     for b in range(B):
-        sub = lab[b, ::gy, ::gx]
-        lo, hi = (int(sub.min()), int(sub.max())) if sub.size else (0, 0)
-        if (lo == hi and lo > 0) or hi > 4 * sub.size + 1024:
+        lo, hi = ranges[b]
+        if (lo == hi and lo > 0) or hi > 4 * h * w + 1024:
             prob[b] = edt_prob(d_sub[b])           # the special cases of edt_prob (constant image, sparse huge ids)
         else:
             N.dcall(d_sub, "sd_edt_prob_device", _p(d_sub[b]), 1, h, w, 1.0, 1.0, 1.0, max(hi, 0), _p(prob[b]))
@@ -345,7 +390,7 @@ def class_targets_device(d_lab, neg, grid, tables, idx):
     C = tables.n_classes + 1
     d_neg = None
     if neg is not None:
-        d_neg = torch.from_numpy(np.ascontiguousarray(np.stack(neg))).to(device)
+        d_neg = neg.contiguous() if torch.is_tensor(neg) else torch.from_numpy(np.ascontiguousarray(np.stack(neg))).to(device)
         if tuple(d_neg.shape) != (B,) + (d, h, w)[3 - nd:]:
             raise ValueError("the patch size must be divisible by the grid")
     meta = np.ascontiguousarray(tables.meta[np.asarray(idx, np.int64)])

@@ -6,7 +6,7 @@ those of training.py on five-axis tensors.
   patches      TrainData3D: StarDistData3D's patch part on the 2D generator's restatement (training.TrainData2D: sample_patches,
                get_valid_inds, StarDistDataBase.get_valid_inds with foreground_prob, the max-filter and sample_ind_cache, csbdeep's
                RollingSequence.batch / choice): the same np.random draws in the same order, so np.random.seed(s) gives the reference's
-               patches.  The augmenter runs on the host.
+               patches.  The augmenter runs on the host, or, a stardist_amd.augment.Compose, on the device (training.py).
   targets      one upload of the batch's label patches; prob = edt_prob(lbl, anisotropy) of the FULL patch, sub-sampled by the grid
                afterwards (model3d.py:86-88, unlike 2D), by sd_edt_prob_device; dist = star_dist3D with the grid on the labels read as
                uint16 (sd_star_dist3d_device): equal to stardist_targets(..., rays=, grid=, anisotropy=) bit for bit.
@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from .lib import _native as N
-from .training import (TrainData2D, _conv_layer, _convact, _finish_targets, _multiple_of_32, _p, _packed, _relu_or_linear,
+from .training import (TrainData2D, _conv_layer, _convact, _device_labels, _finish_targets, _multiple_of_32, _p, _packed, _relu_or_linear,
                        _upload_labels, check_scope, class_targets_device, heads_loss, run_training, unet_forward)
 
 
@@ -50,19 +50,23 @@ class TrainData3D(TrainData2D):
     def batch_device(self, i, device):
         """x (B, D, H, W, 1), prob_true (B, d, h, w), dist_true_mask (B, d, h, w, n_rays + 1): float32 device tensors; with n_classes
         also prob_class_true (B, d, h, w, n_classes + 1)"""
-        X, Y = self.sample(i)
-        x = torch.from_numpy(np.ascontiguousarray(np.stack(X)[..., None], np.float32)).to(device, non_blocking=False)
-        return (x,) + targets_device3d(Y, self.rays, self.grid, self.anisotropy, device, self.batch_classes(i))
+        x, Y = self.patches(i, device)
+        return (x[..., None],) + targets_device3d(Y, self.rays, self.grid, self.anisotropy, device, self.batch_classes(i))
 
 
 def targets_device3d(Y, rays, grid, anisotropy, device, classes=None):
-    """the targets of StarDistData3D.__getitem__ (model3d.py:66-127) for the label volumes Y (one shape) from ONE upload: prob_true
+    """the targets of StarDistData3D.__getitem__ (model3d.py:66-127) for the label volumes Y (one shape; host arrays, or one int32 device
+    tensor (B, Z, H, W) as in training.targets_device) from ONE upload: prob_true
     (B, d, h, w) (-1 where the sub-sampled label is negative) and dist_true_mask (B, d, h, w, n_rays + 1) on `device`; with classes =
     (training.ClassTables, the volumes' indices into them) also prob_class_true (B, d, h, w, n_classes + 1)"""
     from .utils import edt_prob
     gz, gy, gx = (int(g) for g in grid)
-    lab, neg, d_lab, d_u16 = _upload_labels(Y, grid, device)
-    B, Z, H, W = lab.shape
+    if torch.is_tensor(Y):
+        ranges, neg, d_lab, d_u16 = _device_labels(Y, grid, False)
+    else:
+        lab, neg, d_lab, d_u16 = _upload_labels(Y, grid, device)
+        ranges = [(int(v.min()), int(v.max())) if v.size else (0, 0) for v in lab]
+    B, Z, H, W = (int(n) for n in d_lab.shape)
     R = len(rays)
     rz, ry, rx = (torch.from_numpy(np.ascontiguousarray(v, np.float32)).to(device) for v in np.asarray(rays.vertices).T)
     samp = (1.0, 1.0, 1.0) if anisotropy is None else tuple(float(a) for a in anisotropy)
@@ -71,8 +75,8 @@ def targets_device3d(Y, rays, grid, anisotropy, device, classes=None):
     dist = torch.empty((B, d, h, w, R), dtype=torch.float32, device=device)
     full = torch.empty((Z, H, W), dtype=torch.float32, device=device)
     for b in range(B):
-        lo, hi = (int(lab[b].min()), int(lab[b].max())) if lab[b].size else (0, 0)
-        if (lo == hi and lo > 0) or hi > 4 * lab[b].size + 1024:
+        lo, hi = ranges[b]
+        if (lo == hi and lo > 0) or hi > 4 * Z * H * W + 1024:
             pf = edt_prob(d_lab[b], anisotropy=anisotropy)      # the special cases of edt_prob (constant volume, sparse huge ids)
         else:
             N.dcall(d_lab, "sd_edt_prob_device", _p(d_lab[b]), Z, H, W, samp[0], samp[1], samp[2], max(hi, 0), _p(full))

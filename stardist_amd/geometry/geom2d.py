@@ -1,8 +1,9 @@
 """Mirror of stardist/geometry/geom2d.py (hot-path functions) on top of the HIP natives."""
 import numpy as np
 
+from .. import _route as R
 from ..lib import _native as N
-from ..utils import _normalize_grid
+from ..utils import _normalize_grid, to_host
 
 
 _SC_CACHE = {}
@@ -186,13 +187,10 @@ def _region_centroids_device(lab, top):
     image that int32 offsets address satisfies this (fewer than 2**31 pixels, coordinates below 2**31 / count).  One scalar comes to the
     host, the number of objects (in torch.nonzero)."""
     import torch
-    nd = lab.dim()
-    sums = torch.empty((int(top) + 1, 4), dtype=torch.int64, device=lab.device)
-    Z, Y, X = ((1,) + tuple(lab.shape)) if nd == 2 else tuple(lab.shape)
-    N.dcall(lab, "sd_label_centroid_sums_device", N.tptr(lab), int(Z), int(Y), int(X), int(top), N.tptr(sums))
+    sums = R.label_tables(lab, int(top), sums=True)[1]
     labs = torch.nonzero(sums[:, 0]).reshape(-1)
     s = sums.index_select(0, labs)
-    return labs, torch.div(s[:, 4 - nd:], s[:, :1], rounding_mode="floor").contiguous()
+    return labs, torch.div(s[:, 4 - lab.dim():], s[:, :1], rounding_mode="floor").contiguous()
 
 
 def _star_representation_device(lbl, rays):
@@ -200,7 +198,7 @@ def _star_representation_device(lbl, rays):
     use them: the labels present (ascending), the pixel under each centroid (int64) and the row of star_dist(lbl, rays) (`rays` an int:
     2D) or of star_dist3D(lbl, rays) (a Rays_* object: 3D; clamped below at 1e-3, geom3d.py:214) at that pixel, float32, evaluated
     there only (sd_star_dist2d_points_device / sd_star_dist3d_points_device).  lbl: an integer tensor without negative values whose ids
-    need no compaction (stardist_amd.utils._ids_need_compaction); nothing but the number of objects and the kernels' status come to
+    need no compaction (stardist_amd._route._ids_need_compaction); nothing but the number of objects and the kernels' status come to
     the host."""
     import ctypes
     import torch
@@ -232,16 +230,14 @@ def _relabel_route(lbl, ndim, device, kwargs):
     negative, `ndim` axes: ValueError).  -> (route, image): 'host' = the host code on the numpy array `image`; 'via_host' = the host
     function on a copy of the tensor, the result back as a tensor; 'device' = `image` is the label tensor on the device (an uploaded
     numpy array comes back as numpy: the caller sees that from its own argument)."""
-    from ..utils import _DEVICE_LABEL_DTYPES, _ids_need_compaction
-    if not N.is_torch(lbl):
-        lbl = np.asarray(lbl)
+    lbl, is_t, on_device = R.classify(lbl, device)
+    if not is_t:
         _check_label_array(lbl, "lbl")
         if not lbl.ndim == ndim:
             raise ValueError("lbl image should be %d dimensional" % ndim)
-        if device is None or kwargs or (lbl.size and _ids_need_compaction(int(lbl.max()), lbl.size)):
+        if not on_device or kwargs or (lbl.size and R._ids_need_compaction(int(lbl.max()), lbl.size)):
             return "host", lbl
-        import torch
-        return "device", torch.as_tensor(np.ascontiguousarray(lbl.astype(np.int32)), device=torch.device(device))
+        return "device", R.to_device_tensor(lbl.astype(np.int32), device)
     import torch
     if lbl.is_floating_point() or lbl.is_complex() or lbl.dtype == torch.bool:
         raise ValueError("lbl must be an array of non-negative integers.")
@@ -250,31 +246,29 @@ def _relabel_route(lbl, ndim, device, kwargs):
         raise ValueError("lbl must be an array of non-negative integers.")
     if not lbl.dim() == ndim:
         raise ValueError("lbl image should be %d dimensional" % ndim)
-    on_device = lbl.is_cuda or device is not None
-    if kwargs or not on_device or str(lbl.dtype) not in _DEVICE_LABEL_DTYPES or _ids_need_compaction(hi, lbl.numel()):
+    if kwargs or not on_device or str(lbl.dtype) not in R._DEVICE_LABEL_DTYPES or R._ids_need_compaction(hi, lbl.numel()):
         return "via_host", lbl
-    return "device", (lbl if device is None else lbl.to(torch.device(device)))
+    return "device", R.to_device_tensor(lbl, device)
 
 
 def relabel_image_stardist(lbl, n_rays, *, device=None, **kwargs):
     """geom2d.py:200-211: relabel each label region in `lbl` with its star representation (star_dist at the truncated region
     centroid -> polygons_to_label).  Label ids of the result are 1..n in the order of the regions' ids, as in the reference.
 
-    numpy in without `device` -> the host code below.  An integer tensor on a HIP device in -> it stays there: centroids and the star
-    distances at the centroids only (`_star_representation_device`), then the tensor path of polygons_to_label; an int32 tensor on
-    that device out, equal to the host result.  numpy in with `device=` -> uploaded, relabelled there, numpy out.  With any **kwargs
-    (grid, mode), or ids that stardist_amd.utils._device_labels would compact (the compaction loses the low 16 bits the rays compare),
-    a tensor goes through the host function and comes back as a tensor; a numpy array takes the host code."""
+    Routing: DESIGN.md section 3p; the host code is the one below.  The device route takes integer images: centroids and the star
+    distances at the centroids only (`_star_representation_device`), then the tensor path of polygons_to_label; the result is int32
+    and equals the host result.  Its own (exception 8 there): with any **kwargs (grid, mode), or ids that
+    stardist_amd._route._device_labels would compact (the compaction loses the low 16 bits the rays compare), a tensor goes through
+    the host function and comes back as a tensor where it lives, whatever `device=` says; a numpy array takes the host code."""
     route, img = _relabel_route(lbl, 2, device, kwargs)
     if route == "via_host":
-        from ..utils import _via_host
-        return _via_host(relabel_image_stardist, img, n_rays, **kwargs)
+        return R.via_host(relabel_image_stardist, img, n_rays, **kwargs)
     if route == "device":
         import torch
         _, points, dist = _star_representation_device(img, int(n_rays))
         shape = tuple(int(v) for v in img.shape)
         out = polygons_to_label(dist, points, shape=shape) if len(points) else torch.zeros(shape, dtype=torch.int32, device=img.device)
-        return out if N.is_torch(lbl) else out.cpu().numpy()
+        return out if N.is_torch(lbl) else to_host(out)
     lbl = img
     dist = star_dist(lbl, n_rays, **kwargs)
     points = _region_centroids(lbl)[1].astype(int)

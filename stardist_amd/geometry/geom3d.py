@@ -1,8 +1,9 @@
 """Mirror of stardist/geometry/geom3d.py (hot-path functions) on top of the HIP natives."""
 import numpy as np
 
+from .. import _route as R
 from ..lib import _native as N
-from ..utils import _normalize_grid
+from ..utils import _normalize_grid, to_host
 
 
 def star_dist3D(lbl, rays, grid=(1, 1, 1), mode="hip"):
@@ -115,20 +116,19 @@ def relabel_image_stardist3D(lbl, rays, verbose=False, *, device=None, **kwargs)
     """geom3d.py:201-217: relabel each label region in `lbl` with its star representation (star_dist3D at the truncated region
     centroid, clamped below at 1e-3 -> polyhedron_to_label with the regions' own label ids).
 
-    numpy in without `device` -> the host code below.  An integer tensor on a HIP device in -> it stays there (geom2d.
-    _star_representation_device, then the tensor path of polyhedron_to_label with labels = the regions' ids); an int32 tensor on that
-    device out.  numpy in with `device=` -> uploaded, relabelled there, numpy out.  With any **kwargs (grid, mode) or ids that would be
-    compacted, a tensor goes through the host function and comes back as a tensor.  An image without objects gives what
-    polyhedron_to_label gives for no points (a uint16 numpy array of zeros, and its warning under `verbose`) on either path."""
+    Routing: DESIGN.md section 3p, as relabel_image_stardist; the device route is geom2d._star_representation_device, then the tensor
+    path of polyhedron_to_label with labels = the regions' ids, an int32 tensor out.  Its own (exceptions 8 and 9 there): with any
+    **kwargs (grid, mode) or ids that would be compacted, a tensor goes through the host function and comes back as a tensor where it
+    lives; an image without objects gives what polyhedron_to_label gives for no points (a uint16 numpy array of zeros, and its warning
+    under `verbose`) on either path, also for a tensor."""
     from .geom2d import _region_centroids, _relabel_route, _star_representation_device
     route, img = _relabel_route(lbl, 3, device, kwargs)
     if route == "via_host":
-        from ..utils import _via_host
-        return _via_host(relabel_image_stardist3D, img, rays, verbose, **kwargs)
+        return R.via_host(relabel_image_stardist3D, img, rays, verbose, **kwargs)
     if route == "device":
         labs, points, dist = _star_representation_device(img, rays)
         out = polyhedron_to_label(dist, points, rays, shape=tuple(int(v) for v in img.shape), labels=labs, verbose=verbose)
-        return out if N.is_torch(lbl) or not N.is_torch(out) else out.cpu().numpy()
+        return out if N.is_torch(lbl) or not N.is_torch(out) else to_host(out)
     lbl = img
     dist_all = star_dist3D(lbl, rays, **kwargs)
     labs, cen = _region_centroids(lbl)

@@ -1,0 +1,590 @@
+"""Functions of label images with a host route (numpy + scipy, like the reference's) and a device route (hand-written HIP):
+fill_label_holes, calculate_extents, measure_labels, label_components, expand_labels, distance_transform.  stardist_amd.utils re-exports
+the public names.  Which route a call takes and what comes back is one rule, DESIGN.md section 3p, and its code is stardist_amd._route;
+a `_X_device` half here allocates its outputs and calls its kernels."""
+import numpy as np
+
+from . import _route as R
+from ._route import _DEVICE_DTYPE_CODE, _DEVICE_LABEL_DTYPES, _ids_need_compaction
+from .lib import _native as N
+
+
+def _object_boxes(lbl_img):
+    """[(label id, bounding-box slices)] of the labels present, ascending (scipy.ndimage.find_objects: entry i - 1 belongs to label i)"""
+    from scipy.ndimage import find_objects
+    return [(i, sl) for i, sl in enumerate(find_objects(lbl_img), 1) if sl is not None]
+
+
+# ----------------------------------------------------------------------------- fill_label_holes, calculate_extents
+# (stardist/__init__.py:13 exports them; csrc/fill_holes.hip)
+
+def _fill_label_holes_device(lbl_img, device=None):
+    """fill_label_holes through sd_fill_label_holes_device; numpy in (uploaded to `device`) -> numpy out, tensor in -> tensor out, of the
+    input's dtype and shape; the input is never written"""
+    import torch
+    N.require_device()
+    if lbl_img.ndim not in (2, 3):
+        raise ValueError("fill_label_holes: a label image on the device must be 2D or 3D")
+    lab, top, ids = R._device_labels(lbl_img, device)
+    out = torch.empty_like(lab)
+    if lab.numel():
+        Z, Y, X = R.zyx(lab.shape)
+        if lab.dim() == 3 and Z == 1:
+            # one plane given as a volume: along z every pixel lies on the box's outer layer, so nothing is a hole (the host function
+            # says the same); the library takes Z = 1 for a 2D image, so the plane goes in as the volume (Y, 1, X) -- the same memory
+            Z, Y = Y, 1
+        N.dcall(lab, "sd_fill_label_holes_device", R.ptr(lab), Z, Y, X, top, R.ptr(out))
+    res = R.like_input(out, lbl_img, ids)
+    return res if isinstance(lbl_img, np.ndarray) else res.to(lbl_img.device)         # section 3p, exception 1
+
+
+def _label_boxes_device(t):
+    """(n present, ndim) int64 numpy array of the bounding-box sizes of the labels of a 2D / 3D device tensor, by ascending label
+    (sd_label_boxes_device; only the box table comes to the host)"""
+    import torch
+    from .utils import to_host
+    N.require_device()
+    nd = t.dim()
+    if t.numel() == 0:
+        return np.zeros((0, nd), np.int64)
+    if str(t.dtype) not in _DEVICE_LABEL_DTYPES:
+        t = t.to(torch.int64)
+    lab, top, _ = R._device_labels(t)
+    b = to_host(R.label_tables(lab, top, boxes=True)[0]).astype(np.int64)
+    b = b[b[:, 5] > b[:, 2]]
+    return (b[:, 3:] - b[:, :3])[:, 3 - nd:]
+
+
+def fill_label_holes(lbl_img, *, device=None, **kwargs):
+    """Fill the holes of every labelled object (stardist/utils.py:137-153): per object, `binary_fill_holes` of its mask on its bounding
+    box grown by one pixel on every side that is not an image border -- a cavity that reaches the image border stays open, as there.
+    **kwargs go to scipy.ndimage.binary_fill_holes.
+
+    Routing: DESIGN.md section 3p; the device route takes 2D / 3D integer images and equals the host result (csrc/fill_holes.hip:
+    bounding boxes in one pass, then per object two bit planes and a flood from the box's outer layer; the input is not written).  Its
+    own: the kernels implement the default structure, so with any **kwargs a tensor goes through the host function and comes back as a
+    tensor, and a numpy array takes the host code; a tensor's result lives where the tensor lives, whatever `device=` says (exceptions
+    1 and 2 there).  Ids beyond int32, or sparse huge ids, are compacted in ascending order for the call and mapped back."""
+    if R.is_torch(lbl_img):
+        on_device = lbl_img.is_cuda or device is not None
+        if kwargs or not on_device or str(lbl_img.dtype) not in _DEVICE_LABEL_DTYPES:
+            return R.via_host(fill_label_holes, lbl_img, **kwargs)
+        return _fill_label_holes_device(lbl_img, device)
+    lbl_img = np.asarray(lbl_img)
+    if device is not None and not kwargs and lbl_img.dtype.kind in "iu":
+        return _fill_label_holes_device(lbl_img, device)
+    from scipy.ndimage import binary_fill_holes
+    out = np.zeros_like(lbl_img)
+    for lab, box in _object_boxes(lbl_img):
+        room = [(s.start > 0, s.stop < n) for s, n in zip(box, lbl_img.shape)]
+        grown = tuple(slice(s.start - int(lo), s.stop + int(hi)) for s, (lo, hi) in zip(box, room))
+        inner = tuple(slice(int(lo), -1 if hi else None) for lo, hi in room)
+        filled = binary_fill_holes(lbl_img[grown] == lab, **kwargs)[inner]
+        out[box][filled] = lab
+    return out
+
+
+def calculate_extents(lbl, func=np.median):
+    """Aggregate (median by default) of the objects' bounding-box sizes per axis, for one 2D / 3D label image, or over a sequence / 4D
+    stack of them (stardist/utils.py:180-193).  Label images that are tensors on a HIP device stay there: one sd_label_boxes_device call
+    per image, the box table comes to the host and `func` runs over the extents as for host input.  There is no `device=` (DESIGN.md
+    section 3p, exception 3)."""
+    from collections.abc import Iterable
+    if R.is_device_tensor(lbl):
+        if lbl.dim() == 4:
+            return func(np.stack([calculate_extents(one, func) for one in lbl], axis=0), axis=0)
+        if lbl.dim() not in (2, 3):
+            raise ValueError("label image should be 2- or 3-dimensional (or pass a list of these)")
+        extents = _label_boxes_device(lbl)
+        return func(extents, axis=0) if len(extents) else np.zeros(lbl.dim())
+    if (isinstance(lbl, np.ndarray) and lbl.ndim == 4) or (not isinstance(lbl, np.ndarray) and isinstance(lbl, Iterable)):
+        return func(np.stack([calculate_extents(one, func) for one in lbl], axis=0), axis=0)
+    n = lbl.ndim
+    if n not in (2, 3):
+        raise ValueError("label image should be 2- or 3-dimensional (or pass a list of these)")
+    boxes = _object_boxes(lbl)
+    if not boxes:
+        return np.zeros(n)
+    return func(np.array([[s.stop - s.start for s in box] for _, box in boxes]), axis=0)
+
+
+# ----------------------------------------------------------------------------- measure_labels: the per-object table
+# Both routes produce the same "raw" columns -- label (n,), area (n,), bbox (n, 2 nd), csum (n, nd) coordinate sums, all int64, and with
+# an image sum, sum2 (n, C) int64 / float64 and min, max (n, C) int64 / the image's float type -- as numpy arrays or as tensors;
+# _measure_columns derives the table from them, the one place where centroid, mean and std are computed.
+_MEASURE_RAW = ("label", "area", "bbox", "csum", "sum", "sum2", "min", "max")
+
+
+def _measure_shapes(lbl_shape, img_shape):
+    """(number of channels or None without an image, whether the image has a channel axis); raises the ValueErrors of measure_labels"""
+    nd = len(lbl_shape)
+    if nd not in (2, 3):
+        raise ValueError("measure_labels: the label image must be 2D or 3D, got %d axes" % nd)
+    if img_shape is None:
+        return None, False
+    if tuple(img_shape) == tuple(lbl_shape):
+        return 1, False
+    if len(img_shape) == nd + 1 and tuple(img_shape[:-1]) == tuple(lbl_shape) and img_shape[-1] >= 1:
+        return int(img_shape[-1]), True
+    raise ValueError("measure_labels: the image's shape %s is neither the label image's %s nor that plus a channel axis"
+                     % (tuple(img_shape), tuple(lbl_shape)))
+
+
+def _measure_pack(raw):
+    """the raw columns side by side as one (n, K) int64 array / tensor (floats as the bits of their float64 value): one copy moves it"""
+    wide = [raw[key] if raw[key].ndim == 2 else raw[key].reshape(raw[key].shape[0], 1) for key in _MEASURE_RAW if key in raw]
+    if R.is_torch(raw["label"]):
+        import torch
+        return torch.cat([a.to(torch.float64).contiguous().view(torch.int64) if a.dtype.is_floating_point else a.to(torch.int64)
+                          for a in wide], dim=1).contiguous()
+    return np.ascontiguousarray(np.concatenate([np.ascontiguousarray(a, np.float64).view(np.int64) if a.dtype.kind == "f"
+                                                else a.astype(np.int64) for a in wide], axis=1))
+
+
+def _measure_unpack(packed, nd, C, sum_dtype, mm_dtype):
+    """the raw columns of _measure_pack's array; sum_dtype / mm_dtype: the names of the dtypes of sum, sum2 and of min, max"""
+    is_t = R.is_torch(packed)
+    widths = [("label", 1, "int64"), ("area", 1, "int64"), ("bbox", 2 * nd, "int64"), ("csum", nd, "int64")]
+    if C is not None:
+        widths += [("sum", C, sum_dtype), ("sum2", C, sum_dtype), ("min", C, mm_dtype), ("max", C, mm_dtype)]
+    raw, at = {}, 0
+    for key, w, dt in widths:
+        a = packed[:, at:at + w]
+        at += w
+        if is_t:
+            import torch
+            a = a.contiguous()
+            a = a.view(torch.float64).to(getattr(torch, dt)) if dt.startswith("float") else a
+        else:
+            a = np.ascontiguousarray(a)
+            a = a.view(np.float64).astype(dt) if dt.startswith("float") else a
+        raw[key] = a.reshape(-1) if key in ("label", "area") else a
+    return raw
+
+
+def _measure_columns(raw, nd, channel_axis):
+    """the table of measure_labels from the raw columns (numpy arrays or tensors): centroid = float64(coordinate sum) / count, mean =
+    float64(sum) / count, var = max(0, float64(sum2) / count - mean^2), std = sqrt(var), every operation rounded on its own"""
+    if R.is_torch(raw["label"]):
+        import torch
+        f64, sqrt, col = (lambda a: a.to(torch.float64)), torch.sqrt, (lambda a: a.contiguous())
+    else:
+        f64, sqrt, col = (lambda a: a.astype(np.float64)), np.sqrt, np.ascontiguousarray
+    out = {"label": raw["label"], "area": raw["area"]}
+    for k in range(2 * nd):
+        out["bbox-%d" % k] = col(raw["bbox"][:, k])
+    count = f64(raw["area"])
+    for k in range(nd):
+        out["centroid-%d" % k] = f64(raw["csum"][:, k]) / count
+    if "sum" in raw:
+        with np.errstate(all="ignore"):
+            cnt = count[:, None]
+            mean = f64(raw["sum"]) / cnt
+            var = (f64(raw["sum2"]) / cnt - mean * mean).clip(min=0)
+            std = sqrt(var)
+        named = (("sum_intensity", raw["sum"]), ("mean_intensity", mean), ("min_intensity", raw["min"]), ("max_intensity", raw["max"]),
+                 ("std_intensity", std))
+        for name, a in named:
+            for c in range(a.shape[1]):
+                out[("%s-%d" % (name, c)) if channel_axis else name] = col(a[:, c])
+    return out
+
+
+def _measure_raw_host(lbl, img):
+    """the raw columns by numpy over scipy.ndimage.find_objects boxes; img: None or an array of lbl.shape (+ (C,))"""
+    if lbl.dtype.kind == "b":
+        lbl = lbl.astype(np.uint8)
+    if lbl.dtype.kind not in "iu":
+        raise ValueError("measure_labels: the label image must have an integer type, got %s" % lbl.dtype)
+    nd = lbl.ndim
+    top = int(lbl.max()) if lbl.size else 0
+    ids = None
+    if _ids_need_compaction(top, lbl.size):
+        pos = lbl > 0
+        ids, inv = np.unique(lbl[pos], return_inverse=True)
+        lab = np.zeros(lbl.shape, np.int32)
+        lab[pos] = inv.reshape(-1) + 1
+    else:
+        lab = np.maximum(lbl, 0) if lbl.dtype.kind != "u" else lbl
+    boxes = _object_boxes(lab) if lab.size else []
+    n = len(boxes)
+    raw = {"label": np.array([k for k, _ in boxes], np.int64).reshape(n), "area": np.zeros(n, np.int64),
+           "bbox": np.zeros((n, 2 * nd), np.int64), "csum": np.zeros((n, nd), np.int64)}
+    if ids is not None:
+        raw["label"] = ids.astype(np.int64)[raw["label"] - 1]
+    if img is not None:
+        C = 1 if img.ndim == nd else img.shape[-1]
+        exact = img.dtype.kind in "iub"
+        raw["sum"] = np.zeros((n, C), np.int64 if exact else np.float64)
+        raw["sum2"] = np.zeros((n, C), np.int64 if exact else np.float64)
+        raw["min"] = np.zeros((n, C), np.int64 if exact else img.dtype)
+        raw["max"] = np.zeros((n, C), np.int64 if exact else img.dtype)
+    with np.errstate(all="ignore"):
+        for k, (l, box) in enumerate(boxes):
+            mask = lab[box] == l
+            where = np.nonzero(mask)
+            area = len(where[0])
+            raw["area"][k] = area
+            raw["bbox"][k] = [s.start for s in box] + [s.stop for s in box]
+            raw["csum"][k] = [int(w.sum(dtype=np.int64)) + area * s.start for w, s in zip(where, box)]
+            if img is not None:
+                v = img[box][mask].reshape(area, C)
+                wide = v.astype(np.int64 if exact else np.float64)
+                raw["sum"][k] = wide.sum(axis=0)
+                raw["sum2"][k] = (wide * wide).sum(axis=0)
+                raw["min"][k] = v.min(axis=0)
+                raw["max"][k] = v.max(axis=0)
+    return raw
+
+
+def _measure_raw_device(lbl, img, C, device):
+    """the raw columns as tensors on the device: sd_label_boxes_device, sd_label_centroid_sums_device and, with an image,
+    sd_label_intensity_stats_device, then the rows of the labels present (one scalar, their number, comes to the host)"""
+    import torch
+    N.require_device()
+    lab, top, ids = R._device_labels(lbl, device)
+    dev, nd = lab.device, lab.dim()
+    code = None
+    if img is not None:
+        img = R.to_device_tensor(img, dev)                                  # an image that is elsewhere is moved to the labels' device
+        code = _DEVICE_DTYPE_CODE[str(img.dtype)]
+    sum_t, mm_t = (torch.float64, torch.float32) if code == 2 else (torch.int64, torch.int32)
+    if lab.numel() == 0 or top <= 0:
+        raw = {"label": torch.zeros(0, dtype=torch.int64, device=dev), "area": torch.zeros(0, dtype=torch.int64, device=dev),
+               "bbox": torch.zeros((0, 2 * nd), dtype=torch.int64, device=dev), "csum": torch.zeros((0, nd), dtype=torch.int64, device=dev)}
+        if img is not None:
+            raw.update(sum=torch.zeros((0, C), dtype=sum_t, device=dev), sum2=torch.zeros((0, C), dtype=sum_t, device=dev),
+                       min=torch.zeros((0, C), dtype=torch.float32 if code == 2 else torch.int64, device=dev),
+                       max=torch.zeros((0, C), dtype=torch.float32 if code == 2 else torch.int64, device=dev))
+        return raw
+    boxes, sums = R.label_tables(lab, top, boxes=True, sums=True)
+    if img is not None:
+        acc = torch.empty((top + 1, C, 2), dtype=sum_t, device=dev)
+        mm = torch.empty((top + 1, C, 2), dtype=mm_t, device=dev)
+        N.dcall(lab, "sd_label_intensity_stats_device", R.ptr(lab), *R.zyx(lab.shape), top, R.ptr(boxes), R.ptr(img), code, C,
+                R.ptr(acc) if code != 2 else None, R.ptr(acc) if code == 2 else None, R.ptr(mm))
+    present = torch.nonzero(sums[:, 0]).reshape(-1)
+    s = sums.index_select(0, present)
+    b = boxes.index_select(0, present).to(torch.int64)
+    raw = {"label": R.original_labels(present, ids), "area": s[:, 0].contiguous(), "bbox": b if nd == 3 else b[:, [1, 2, 4, 5]], "csum": s[:, 4 - nd:]}
+    if img is not None:
+        a, m = acc.index_select(0, present), mm.index_select(0, present)
+        raw.update(sum=a[:, :, 0], sum2=a[:, :, 1], min=m[:, :, 0] if code == 2 else m[:, :, 0].to(torch.int64),
+                   max=m[:, :, 1] if code == 2 else m[:, :, 1].to(torch.int64))
+    return raw
+
+
+def measure_labels(lbl, img=None, *, device=None, as_tensors=False):
+    """Per-object table of a 2D / 3D integer label image (values <= 0 are background) and, optionally, of the image `img` that was
+    segmented: shape lbl.shape or lbl.shape + (C,) (channels last).  Returns a dict of 1-D columns, one row per label present,
+    ascending by label, named as scikit-image 0.18's regionprops_table names them:
+
+        label                  int64    the label's id
+        area                   int64    pixel count
+        bbox-0 .. bbox-(2nd-1) int64    starts, then exclusive stops (scipy.ndimage.find_objects)
+        centroid-0 .. -(nd-1)  float64  float64(coordinate sum) / count
+      with img (with a channel axis every name gets -0 .. -(C-1)):
+        sum_intensity          int64 (integer images) / float64
+        mean_intensity         float64  float64(sum) / count
+        min_intensity, max_intensity    int64 / the image's float type
+        std_intensity          float64  population standard deviation: sqrt(max(0, float64(sum of squares) / count - mean^2))
+
+    Arithmetic: integer images are summed (values and squares) in int64, exactly, also beyond 2^53; float images in float64, where
+    every square of a float32 is exact.  The derived columns are computed in one place for both routes, every operation rounded on
+    its own.  A NaN pixel makes sum, mean, min, max and std of its object and channel NaN, as numpy does; +-inf follow IEEE.  Without
+    objects every column is an empty array of its dtype.
+
+    Routing: DESIGN.md section 3p, by the label image; an image that is elsewhere is moved to the labels' device.  The device route
+    takes integer labels and uint8 / uint16 / float32 images (csrc/measure.hip and the box and centroid-sum kernels; the inputs are not
+    written): its float64 sums are added in a fixed order without floating-point atomics, so they depend on (shape, lbl, img) alone --
+    the same bits from call to call and from process to process -- and differ from the host's only by the order of the additions.  Any
+    other dtype goes through the host code.  Ids beyond int32, or sparse huge ids, are compacted in ascending order for the call;
+    `label` reports the originals.  Its own (exception 4 there): the columns are numpy arrays whatever the input's kind, which the
+    device route reads back in one copy of the table; as_tensors=True makes them tensors, on the device for the device route (besides
+    what reading the largest label needs, one scalar comes to the host, the number of rows), else where the labels are or on `device`.
+    A label image that is not 2D / 3D or an image of another shape raises ValueError before anything runs."""
+    lbl, lbl_t, on_device = R.classify(lbl, device)
+    img_t = img is not None and R.is_torch(img)
+    if img is not None and not img_t:
+        img = np.asarray(img)
+    nd = len(lbl.shape)
+    C, channel_axis = _measure_shapes(tuple(lbl.shape), None if img is None else tuple(img.shape))
+    lbl_ok = (str(lbl.dtype) in _DEVICE_LABEL_DTYPES) if lbl_t else (lbl.dtype.kind in "iu")
+    img_ok = img is None or (str(img.dtype) if img_t else "torch." + img.dtype.name) in _DEVICE_DTYPE_CODE
+    if on_device and lbl_ok and img_ok:
+        raw = _measure_raw_device(lbl, img, C, device)
+        if as_tensors:
+            return _measure_columns(raw, nd, channel_axis)
+        from .utils import to_host
+        sum_dtype, mm_dtype = (str(raw["sum"].dtype)[6:], str(raw["min"].dtype)[6:]) if img is not None else (None, None)
+        return _measure_columns(_measure_unpack(to_host(_measure_pack(raw)), nd, C, sum_dtype, mm_dtype), nd, channel_axis)
+    if not as_tensors:
+        return _measure_columns(_measure_raw_host(lbl.cpu().numpy() if lbl_t else lbl, img.cpu().numpy() if img_t else img), nd, channel_axis)
+    # the host table as tensors where the labels are (or on `device`): the packed raw columns make the trip
+    import torch
+    host_packed = lambda l, i=None: _measure_pack(_measure_raw_host(l, i))
+    rest = () if img is None else (img,)
+    if lbl_t:
+        packed = R.via_host(host_packed, lbl, *rest, to=device)
+    else:
+        packed = torch.as_tensor(host_packed(lbl, *[i.cpu().numpy() if img_t else i for i in rest]),
+                                 device=torch.device("cpu" if device is None else device))
+    sum_dtype = mm_dtype = None
+    if img is not None:
+        name = str(img.dtype)[6:] if img_t else img.dtype.name
+        floating = name.startswith("float") or name.startswith("bfloat")
+        sum_dtype, mm_dtype = ("float64", name) if floating else ("int64", "int64")
+    return _measure_columns(_measure_unpack(packed, nd, C, sum_dtype, mm_dtype), nd, channel_axis)
+
+
+# ----------------------------------------------------------------------------- connected components: mask -> label image
+# element type codes of sd_label_components_device (a bool mask travels as uint8)
+_COMPONENTS_DTYPE_CODE = {"bool": 0, "uint8": 0, "uint16": 1, "int32": 3}
+
+
+def _backward_offsets(nd, connectivity):
+    """the neighbour offsets with at most `connectivity` non-zero coordinates that point backwards in raster order: every edge of the
+    pixel graph once"""
+    from itertools import product
+    return [o for o in product((-1, 0, 1), repeat=nd) if o < (0,) * nd and sum(1 for c in o if c) <= connectivity]
+
+
+def _label_components_host(img, connectivity, background):
+    """(int32 label image, n) of a 2D / 3D numpy array: one edge list per backward offset, scipy's connected_components on the pixel
+    graph, ids by first occurrence in raster order"""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    a = np.ascontiguousarray(img)
+    out = np.zeros(a.shape, np.int32)
+    if a.size == 0:
+        return out, 0
+    R.check_pixel_count(a.shape, "label_components")
+    fg = a != background
+    index = np.arange(a.size, dtype=np.int32).reshape(a.shape)
+    rows, cols = [], []
+    for off in _backward_offsets(a.ndim, connectivity):
+        here = tuple(slice(max(0, -d), n - max(0, d)) for d, n in zip(off, a.shape))
+        there = tuple(slice(max(0, d), n - max(0, -d)) for d, n in zip(off, a.shape))
+        keep = (a[here] == a[there]) & fg[here]
+        rows.append(index[here][keep])
+        cols.append(index[there][keep])
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    graph = coo_matrix((np.ones(len(rows), np.int8), (rows, cols)), shape=(a.size, a.size)).tocsr()
+    comp = connected_components(graph, directed=False, return_labels=True)[1]
+    where = np.flatnonzero(fg.reshape(-1))
+    if not len(where):
+        return out, 0
+    of_pixel = comp[where]
+    ids, first = np.unique(of_pixel, return_index=True)                     # first: position of a component's first pixel
+    new_id = np.zeros(int(comp.max()) + 1, np.int32)
+    new_id[ids[np.argsort(first, kind="stable")]] = np.arange(1, len(ids) + 1, dtype=np.int32)
+    out.reshape(-1)[where] = new_id[of_pixel]
+    return out, int(len(ids))
+
+
+def _label_components_device(img, connectivity, background, device):
+    """(int32 label tensor, int32 device scalar n) through sd_label_components_device; img a numpy array (uploaded to `device`) or a
+    tensor (moved there if it is elsewhere) of one of the dtypes of _COMPONENTS_DTYPE_CODE; nothing comes to the host"""
+    import torch
+    N.require_device()
+    R.check_pixel_count(img.shape, "label_components")
+    t = R.to_device_tensor(img, device)
+    out = torch.empty(t.shape, dtype=torch.int32, device=t.device)
+    count = torch.zeros(1, dtype=torch.int32, device=t.device)
+    if t.numel():
+        code = _COMPONENTS_DTYPE_CODE[str(t.dtype).replace("torch.", "")]
+        N.dcall(t, "sd_label_components_device", R.ptr(t), code, *R.zyx(t.shape), int(connectivity), int(background), R.ptr(out),
+                R.ptr(count))
+    return out, count[0]
+
+
+def label_components(img, connectivity=None, background=0, *, return_num=False, device=None):
+    """Label the connected components of a 2D / 3D image, as skimage.measure.label(img, background=background,
+    connectivity=connectivity) does: pixels equal to `background` (None: 0) get 0; two neighbouring pixels belong to one component only if
+    their values are equal; `connectivity` = 1 .. ndim is the largest number of coordinates in which neighbours may differ (None: ndim);
+    ids 1 .. n are given in raster (C) order of each component's first pixel.  For a boolean mask this is scipy.ndimage.label(mask,
+    generate_binary_structure(ndim, connectivity)).  The result is int32, the project's label dtype, on both routes (skimage returns
+    int64).  return_num=True: (labels, n) with n a Python int.
+
+    Routing: DESIGN.md section 3p; the host code builds the pixel graph with numpy and runs scipy's connected_components, ids by first
+    occurrence.  The device route takes bool / uint8 / uint16 / int32 images and a background that is an integer, and equals the host
+    result (csrc/label_cc.hip: a tiled union-find whose roots are the components' first pixels; the input is not written, the result
+    depends on the input alone).  Its own (exception 5 there): for a tensor nothing is read back and the stream is not synchronised
+    unless return_num=True.  An image that is not 2D / 3D, a connectivity outside 1 .. ndim or, on the device, more than 2^31 - 1
+    pixels raise ValueError before anything runs; an empty image gives an empty result and n = 0."""
+    img, is_t, on_device = R.classify(img, device)
+    nd = len(img.shape)
+    if nd not in (2, 3):
+        raise ValueError("label_components: the image must be 2D or 3D, got %d dimensions" % nd)
+    if connectivity is None:
+        connectivity = nd
+    if isinstance(connectivity, (bool, np.bool_)) or not isinstance(connectivity, (int, np.integer)) or not 1 <= connectivity <= nd:
+        raise ValueError("Connectivity for %dD images must be in [1, ..., %d]. Got %r." % (nd, nd, connectivity))
+    connectivity = int(connectivity)
+    background = 0 if background is None else background
+    name = str(img.dtype).replace("torch.", "")
+    whole = isinstance(background, (int, np.integer, bool, np.bool_)) or (isinstance(background, (float, np.floating))
+                                                                           and float(background).is_integer())
+    if on_device and name in _COMPONENTS_DTYPE_CODE and whole and abs(int(background)) < 2 ** 63:
+        out, count = _label_components_device(img, connectivity, int(background), device)
+        if not is_t:
+            from .utils import to_host
+            out = to_host(out)                                              # synchronises: count is there too
+        return (out, int(count)) if return_num else out
+    if is_t:
+        n_box = []
+
+        def host(a):
+            lab, n = _label_components_host(a, connectivity, background)
+            n_box.append(n)
+            return lab
+        out = R.via_host(host, img, to=device)
+        return (out, n_box[0]) if return_num else out
+    out, n = _label_components_host(img, connectivity, background)
+    return (out, n) if return_num else out
+
+
+# ----------------------------------------------------------------------------- nearest-feature transform: expand_labels, distance_transform
+# (csrc/edt_feature.hip).  The host routes are scipy's distance_transform_edt; the device routes equal them, ties included.
+
+def _expand_labels_host(lbl, distance, spacing):
+    """scikit-image's expand_labels: scipy's nearest labelled pixel of every background pixel, gathered where it is near enough"""
+    from scipy.ndimage import distance_transform_edt
+    out = np.zeros_like(lbl)
+    if not lbl.any():                                                       # scipy's indices are undefined without a feature
+        return out
+    dist, nearest = distance_transform_edt(lbl == 0, sampling=spacing, return_indices=True)
+    near = dist <= distance
+    out[near] = lbl[tuple(ax[near] for ax in nearest)]
+    return out
+
+
+def _expand_labels_device(lbl, distance, szyx, device):
+    """expand_labels through sd_expand_labels_device; numpy in (uploaded to `device`) -> numpy out, tensor in -> tensor out, of the
+    input's dtype and shape; the labels are non-negative; the input is never written"""
+    import torch
+    N.require_device()
+    lab, _, ids = R._device_labels(lbl, device)
+    out = torch.empty_like(lab)
+    if lab.numel():
+        N.dcall(lab, "sd_expand_labels_device", R.ptr(lab), *R.zyx(lab.shape), *szyx, float(distance), R.ptr(out))
+    return R.like_input(out, lbl, ids)
+
+
+def expand_labels(lbl, distance=1, spacing=1, *, device=None):
+    """Grow every labelled object of a 2D / 3D label image by up to `distance` without growing into its neighbours, as
+    skimage.segmentation.expand_labels(lbl, distance, spacing) does: a background pixel takes the label of the nearest labelled pixel if
+    that pixel is at most `distance` away (Euclidean, in units of `spacing`: a scalar or one value per axis), and stays 0 otherwise.
+    A pixel equally near to several labels takes the one scipy's distance_transform_edt returns: the nearest pixel with the smallest
+    coordinate along the last axis, then along the axis before it.  distance <= 0 returns a copy.
+
+    Routing: DESIGN.md section 3p; the host code is scipy's distance_transform_edt(lbl == 0, sampling=spacing, return_indices=True) and
+    the gather, as scikit-image composes them.  The device route takes integer images and equals the host result (csrc/edt_feature.hip:
+    one exact outward scan per pixel and axis, bounded by `distance`; the input is not written).  Ids beyond int32, or sparse huge ids,
+    are compacted in ascending order for the call and mapped back.  Its own (exception 6 there): the device route takes non-negative
+    labels, so an image with a negative label (a feature like any other, as in scikit-image) goes through the host code and comes back
+    in the input's kind.  An image that is not 2D / 3D, a spacing that is not positive and finite or, on the device, more than
+    2^31 - 1 pixels raise ValueError before anything runs; an empty image gives an empty result."""
+    lbl, is_t, on_device = R.classify(lbl, device)
+    nd = len(lbl.shape)
+    if nd not in (2, 3):
+        raise ValueError("expand_labels: the label image must be 2D or 3D, got %d dimensions" % nd)
+    szyx, per_axis = R.spacing_zyx(spacing, nd, "expand_labels")
+    distance = float(distance)
+    if distance != distance:
+        raise ValueError("expand_labels: the distance is not a number")
+    size = int(np.prod(lbl.shape, dtype=np.int64))
+    if not distance > 0 or size == 0:
+        return lbl.clone() if is_t else lbl.copy()
+    integer = (str(lbl.dtype) in _DEVICE_LABEL_DTYPES) if is_t else (lbl.dtype.kind in "iu")
+    if on_device and integer and int(lbl.min()) >= 0:
+        R.check_pixel_count(lbl.shape, "expand_labels")
+        return _expand_labels_device(lbl, distance, szyx, device)
+    if is_t:
+        return R.via_host(_expand_labels_host, lbl, distance, per_axis, to=device)
+    return _expand_labels_host(lbl, distance, per_axis)
+
+
+def _distance_transform_host(img, per_axis, max_distance, return_distances, return_indices):
+    from scipy.ndimage import distance_transform_edt
+    zero = img == 0
+    if zero.any():
+        dist, idx = distance_transform_edt(img, sampling=per_axis, return_indices=True)
+        idx = idx.astype(np.int32)
+    else:
+        dist, idx = np.full(img.shape, np.inf), np.full((img.ndim,) + img.shape, -1, np.int32)
+    if max_distance is not None:
+        far = dist > max_distance
+        dist[far] = np.inf
+        idx[:, far] = -1
+    return dist if return_distances else None, idx if return_indices else None
+
+
+def _distance_transform_device(img, szyx, max_distance, return_distances, return_indices, device):
+    """(float64 distances or None, (ndim, ...) int32 indices or None) as device tensors, through sd_nearest_feature_device on the
+    uint8 mask img != 0 with the zero pixels as the features"""
+    import torch
+    N.require_device()
+    if isinstance(img, np.ndarray):
+        t = R.to_device_tensor(img != 0, device)                            # the mask of a numpy image is taken before the upload
+    else:
+        t = (R.to_device_tensor(img, device) != 0).to(torch.uint8)
+    dist = torch.empty(t.shape, dtype=torch.float64, device=t.device) if return_distances else None
+    lin = torch.empty(t.shape, dtype=torch.int32, device=t.device) if return_indices else None
+    if t.numel():
+        N.dcall(t, "sd_nearest_feature_device", R.ptr(t), 0, *R.zyx(t.shape), 1, *szyx,
+                -1.0 if max_distance is None else float(max_distance), R.opt_ptr(lin), R.opt_ptr(dist))
+    idx = None
+    if return_indices:
+        # the kernel's linear index, split into one coordinate per axis; -1 stays -1
+        none, rest, axes = lin < 0, lin.clamp(min=0), []
+        for n in reversed(t.shape):
+            axes.append(torch.where(none, lin, rest % n) if n else lin)
+            rest = torch.div(rest, max(n, 1), rounding_mode="floor")
+        idx = torch.stack(axes[::-1]) if t.numel() else torch.empty((t.dim(),) + tuple(t.shape), dtype=torch.int32, device=t.device)
+    return dist, idx
+
+
+def distance_transform(img, sampling=None, *, max_distance=None, return_distances=True, return_indices=False, device=None):
+    """scipy.ndimage.distance_transform_edt(img, sampling, return_distances, return_indices) for a 2D / 3D image: for every non-zero
+    pixel the exact Euclidean distance (float64) to the nearest zero pixel, in units of `sampling` (None: 1; a scalar or one value per
+    axis), and that pixel's coordinates as an (ndim, ...) int32 array; a zero pixel has distance 0 and its own coordinates.  Among
+    equally near zero pixels the indices are scipy's: the smallest coordinate along the last axis, then along the axis before it
+    (DESIGN.md section 3n).  Returns the distances, the indices, or (distances, indices), as scipy does.
+
+    Two departures from scipy.  (1) Where no zero pixel exists, or with max_distance given none lies within it, the distance is inf
+    and the indices are -1 (scipy leaves an image without a zero pixel undefined and has no bound).  (2) Time: on the device every pixel
+    scans outwards along each axis until the axis term alone exceeds its best distance, so an unbounded call costs time proportional
+    to the largest distance in the result -- small for images of nuclei, large for a lone zero pixel in a big image.  max_distance
+    bounds the scans.
+
+    Routing: DESIGN.md section 3p; the host code is scipy's, the device route (csrc/edt_feature.hip) equals it.  Its own (exception 7
+    there): every dtype takes the device route, the results have their own dtypes whatever the input's, and a host tensor without
+    `device=` is read in place (`.numpy()`), its results are host tensors.  An image that is not 2D / 3D, a sampling that is not
+    positive and finite, a negative or NaN max_distance, neither result asked for or, on the device, more than 2^31 - 1 pixels raise
+    ValueError before anything runs; an empty image gives empty results."""
+    img, is_t, on_device = R.classify(img, device)
+    nd = len(img.shape)
+    if nd not in (2, 3):
+        raise ValueError("distance_transform: the image must be 2D or 3D, got %d dimensions" % nd)
+    szyx, per_axis = R.spacing_zyx(sampling, nd, "distance_transform")
+    if max_distance is not None:
+        max_distance = float(max_distance)
+        if not max_distance >= 0:
+            raise ValueError("distance_transform: max_distance must be >= 0 or None")
+        if max_distance == np.inf:
+            max_distance = None
+    if not (return_distances or return_indices):
+        raise ValueError("distance_transform: at least one of return_distances / return_indices must be True")
+    if on_device:
+        R.check_pixel_count(img.shape, "distance_transform")
+        dist, idx = _distance_transform_device(img, szyx, max_distance, return_distances, return_indices, device)
+        if not is_t:
+            from .utils import to_host_many
+            dist, idx = to_host_many([dist, idx])
+    else:
+        dist, idx = _distance_transform_host(img.numpy() if is_t else img, per_axis, max_distance, return_distances, return_indices)
+        if is_t:
+            import torch
+            dist, idx = (None if a is None else torch.from_numpy(a) for a in (dist, idx))
+    return (dist, idx) if return_distances and return_indices else (dist if return_distances else idx)

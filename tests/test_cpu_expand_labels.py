@@ -269,9 +269,9 @@ def test_distance_transform_host_route_equals_scipy(name):
 
 def test_arguments_and_routing(monkeypatch):
     import torch
-    from stardist_amd import utils
-    monkeypatch.setattr(utils, "_expand_labels_device", lambda *a, **k: pytest.fail("device path taken"))
-    monkeypatch.setattr(utils, "_distance_transform_device", lambda *a, **k: pytest.fail("device path taken"))
+    from stardist_amd import label_ops
+    monkeypatch.setattr(label_ops, "_expand_labels_device", lambda *a, **k: pytest.fail("device path taken"))
+    monkeypatch.setattr(label_ops, "_distance_transform_device", lambda *a, **k: pytest.fail("device path taken"))
     a = C.case("discs")
     want = expand(a, 3, (2.0, 0.5))
     assert np.array_equal(expand(a.tolist(), 3, (2.0, 0.5)), want)
@@ -314,13 +314,13 @@ def test_arguments_and_routing(monkeypatch):
 
 
 def test_device_route_is_taken_for_integer_labels(monkeypatch):
-    from stardist_amd import utils
+    from stardist_amd import label_ops
     seen = []
 
     def fake(lbl, distance, szyx, device):
         seen.append((str(lbl.dtype), distance, szyx, device))
         raise RuntimeError("stop")
-    monkeypatch.setattr(utils, "_expand_labels_device", fake)
+    monkeypatch.setattr(label_ops, "_expand_labels_device", fake)
     for dt in ("uint8", "uint16", "int32", "int64"):
         with pytest.raises(RuntimeError, match="stop"):
             expand(np.ones((3, 4), dt), 2, (2, 0.5), device="cuda")

@@ -197,8 +197,8 @@ def test_labels_beyond_max_label_are_background(lib):
 
 def test_host_input_takes_the_host_code(monkeypatch):
     """numpy in without device=: scipy's calls as before, no native code, kwargs passed on"""
-    from stardist_amd import utils
-    monkeypatch.setattr(utils, "_fill_label_holes_device", lambda *a, **k: pytest.fail("device path taken"))
+    from stardist_amd import label_ops, utils
+    monkeypatch.setattr(label_ops, "_fill_label_holes_device", lambda *a, **k: pytest.fail("device path taken"))
     a = C.hand_2d()["diagonal_leak"]
     got = utils.fill_label_holes(a)
     assert isinstance(got, np.ndarray) and got.dtype == a.dtype and got[4, 4] == 8

@@ -180,8 +180,8 @@ def test_stand_alone_sanitizer_build_passes_every_case(tmp_path):
 
 def test_arguments_and_routing(monkeypatch):
     import torch
-    from stardist_amd import utils
-    monkeypatch.setattr(utils, "_label_components_device", lambda *a, **k: pytest.fail("device path taken"))
+    from stardist_amd import label_ops
+    monkeypatch.setattr(label_ops, "_label_components_device", lambda *a, **k: pytest.fail("device path taken"))
     img, _ = C.case("blocks_u8")
     want, n = C.host("blocks_u8", 2)
     assert np.array_equal(label(img), want) and np.array_equal(label(img, None, None), want)       # None: ndim, background 0
@@ -214,13 +214,13 @@ def test_arguments_and_routing(monkeypatch):
 
 
 def test_device_route_is_taken_for_the_kernel_dtypes(monkeypatch):
-    from stardist_amd import utils
+    from stardist_amd import label_ops
     seen = []
 
     def fake(img, connectivity, background, device):
         seen.append((str(img.dtype), connectivity, background, device))
         raise RuntimeError("stop")
-    monkeypatch.setattr(utils, "_label_components_device", fake)
+    monkeypatch.setattr(label_ops, "_label_components_device", fake)
     for dt in ("bool", "uint8", "uint16", "int32"):
         with pytest.raises(RuntimeError, match="stop"):
             label(np.zeros((3, 4), dt), device="cuda", background=np.int64(2))

@@ -247,9 +247,9 @@ def test_no_objects_gives_empty_columns_of_the_right_types():
 
 
 def test_host_input_takes_the_host_code_and_errors_come_first(monkeypatch):
-    from stardist_amd import utils
-    monkeypatch.setattr(utils, "_measure_raw_device", lambda *a, **k: pytest.fail("device path taken"))
-    monkeypatch.setattr(utils, "_device_labels", lambda *a, **k: pytest.fail("labels uploaded"))
+    from stardist_amd import _route, label_ops
+    monkeypatch.setattr(label_ops, "_measure_raw_device", lambda *a, **k: pytest.fail("device path taken"))
+    monkeypatch.setattr(_route, "_device_labels", lambda *a, **k: pytest.fail("labels uploaded"))
     lbl, img = C.case("2d_u16")
     for other in (lbl.astype(np.int64), np.maximum(lbl, 0).astype(np.uint8), lbl.tolist()):
         got = measure(other, img)

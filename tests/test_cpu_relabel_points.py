@@ -191,7 +191,7 @@ def test_host_input_makes_the_native_calls_it_made_before(monkeypatch):
 def test_kwargs_and_compacted_ids_take_the_host_function(monkeypatch):
     """with device=: a numpy array with kwargs, or with ids that would be compacted, still runs the host code"""
     from stardist_amd.geometry import geom2d, geom3d
-    from stardist_amd.utils import _ids_need_compaction
+    from stardist_amd._route import _ids_need_compaction
     for fn in ("_star_representation_device", "_region_centroids_device"):
         monkeypatch.setattr(geom2d, fn, lambda *a, **k: pytest.fail("device path taken"))
     fake = _record(monkeypatch)

@@ -685,6 +685,30 @@ int sd_label_centroid_sums_device(const int32_t* d_lbl, int Z, int Y, int X, int
 int sd_label_intensity_stats_device(const int32_t* d_lbl, int Z, int Y, int X, int max_label, const int32_t* d_boxes, const void* d_img,
                                     int dtype, int C, int64_t* d_isum2, double* d_fsum2, void* d_minmax, void* stream);
 
+/* ---- shape tables of labelled objects (csrc/measure_shape.hip, csrc/measure_shape.h): the integer sums behind the shape columns of
+ * stardist_amd.utils.measure_labels(shape=True) -- inertia tensor, axis lengths, eccentricity, orientation, perimeter, Crofton perimeter,
+ * Euler number ----------------------------------------------------------------------------------------------------------------------
+ * lbl (Z, Y, X) int32 label image as above (2D: Z = 1): labels 1 .. max_label are objects, every other value is background.  Both calls
+ * write every row of their table; row 0 and the rows of absent labels are 0.  The input is not written.  Integer arithmetic only
+ * (64-bit integer atomics, no floating point anywhere), 64-bit offsets: the tables depend on the input alone, the same bits from call
+ * to call.  Bad arguments (a null pointer, a non-positive extent, a negative max_label, more than 2^40 pixels) set the error string and
+ * return -1 before anything is launched.  Nothing is copied to the host and the stream is not synchronised.
+ *
+ * Moment sums: d_boxes is the table sd_label_boxes_device wrote for this lbl and max_label (read on the device, every box clamped to
+ * the image).  With u_d = coordinate_d - box start_d, d_m2 is [max_label + 1][6] = sum of u_z u_z, u_z u_y, u_z u_x, u_y u_y, u_y u_x,
+ * u_x u_x over the pixels of the label (2D: the three z entries are 0).  The caller keeps numel * max(extent)^2 below 2^63. */
+int sd_label_moment_sums_device(const int32_t* d_lbl, int Z, int Y, int X, int max_label, const int32_t* d_boxes, int64_t* d_m2, void* stream);
+
+/* Contour counts of a 2D label image: d_counts is [max_label + 1][18] = n_1, n_r2, n_h, h_1 .. h_15.
+ *   A border pixel of label l is a pixel of l with a 4-neighbour that is not l (outside the image and other labels are not l).  With
+ *   a / d = the number of its 4- / diagonal neighbours that are border pixels of l, it counts into n_1 for (a, d) in {(2,0), (3,0), (2,1),
+ *   (3,1), (2,2), (3,2)}, into n_r2 for {(0,2), (1,3)}, into n_h for {(1,1), (1,2)}, else into nothing: the three classes of
+ *   skimage.measure.perimeter(mask, 4), whose value is n_1 + sqrt(2) n_r2 + (1 + sqrt(2)) / 2 n_h.
+ *   h_code counts the 2 x 2 windows at the positions i in [0, Y], j in [0, X] in which l has the configuration code = 1 [L(i,j) = l] +
+ *   2 [L(i-1,j) = l] + 4 [L(i,j-1) = l] + 8 [L(i-1,j-1) = l]: the histogram of skimage.measure.perimeter_crofton(mask, 4) and
+ *   euler_number(mask, 2) (= h_8 - h_6 - h_14). */
+int sd_label_contour_counts_device(const int32_t* d_lbl, int Y, int X, int max_label, int64_t* d_counts, void* stream);
+
 /* ---- connected components (csrc/label_cc.hip, csrc/label_cc.h): what skimage.measure.label(img, background, connectivity) and, for a
  * mask, scipy.ndimage.label(mask, generate_binary_structure(ndim, connectivity)) compute ----------------------------------------------
  * d_img: (Z, Y, X) contiguous image (2D: Z = 1); dtype: 0 = uint8 (a bool mask travels as uint8), 1 = uint16, 3 = int32 (the codes above;

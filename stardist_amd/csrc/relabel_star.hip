@@ -19,15 +19,16 @@
 #include "common.h"
 #include "relabel_star.h"
 #include "stardist_hip.h"
+#include "wave_runs.h"
 #include <vector>
 
 using namespace relabelstar;
 
 namespace {
 
-enum { BLOCK = 256, WAVE = 64, MAX_BLOCKS = 1 << 16 };
-
-__device__ __forceinline__ void add64(long long* p, long long v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
+enum { BLOCK = 256, MAX_BLOCKS = 1 << 16 };
+using wave_runs::WAVE;
+using wave_runs::add64;
 
 __global__ void __launch_bounds__(BLOCK) k_centroid_sums(const int* __restrict__ lbl, long long n, int Y, int X, int max_label, bool volume,
                                                          long long* sums) {
@@ -41,26 +42,18 @@ __global__ void __launch_bounds__(BLOCK) k_centroid_sums(const int* __restrict__
       const int v = lbl[i];
       L = (v >= 1 && v <= max_label) ? v : 0;
     }
-    const int before = __shfl_up(L, 1);
-    const bool head = lane == 0 || L != before;
-    const unsigned long long heads = __ballot(head);
-    if (heads == 1ull && L == 0) continue;                                // a wave of background (uniform: every lane sees `heads`)
-    const unsigned long long later = (heads >> lane) >> 1;                // the run starts after this lane
-    const int end = later ? lane + __ffsll((long long)later) : WAVE;      // one past the last lane of this lane's run
+    const wave_runs::Runs r = wave_runs::runs_of(L, lane);
+    if (wave_runs::all_background(r, L)) continue;                        // (uniform: every lane sees the same heads)
     const long long row = i / X;
     long long sx = i - row * X, sy = volume ? row % Y : row, sz = volume ? row / Y : 0;
     for (int o = 1; o < WAVE; o <<= 1) {
-      const long long ox = __shfl_down(sx, o), oy = __shfl_down(sy, o);
-      const bool take = lane + o < end;
-      if (take) { sx += ox; sy += oy; }
-      if (volume) {
-        const long long oz = __shfl_down(sz, o);
-        if (take) sz += oz;
-      }
+      wave_runs::run_add(sx, o, lane, r);
+      wave_runs::run_add(sy, o, lane, r);
+      if (volume) wave_runs::run_add(sz, o, lane, r);
     }
-    if (head && L) {
+    if (r.head && L) {
       long long* s = sums + 4ll * L;
-      add64(s, end - lane);
+      add64(s, r.end - lane);
       if (sz) add64(s + 1, sz);
       if (sy) add64(s + 2, sy);
       if (sx) add64(s + 3, sx);

@@ -111,8 +111,24 @@ def calculate_extents(lbl, func=np.median):
 # ----------------------------------------------------------------------------- measure_labels: the per-object table
 # Both routes produce the same "raw" columns -- label (n,), area (n,), bbox (n, 2 nd), csum (n, nd) coordinate sums, all int64, and with
 # an image sum, sum2 (n, C) int64 / float64 and min, max (n, C) int64 / the image's float type -- as numpy arrays or as tensors;
-# _measure_columns derives the table from them, the one place where centroid, mean and std are computed.
-_MEASURE_RAW = ("label", "area", "bbox", "csum", "sum", "sum2", "min", "max")
+# _measure_columns derives the table from them, the one place where centroid, mean and std are computed.  With shape=True both routes add
+# m2 (n, 6), the second-order sums of the box-local coordinates in the order zz, zy, zx, yy, yx, xx, and for a 2D image contour (n, 18) =
+# [n_1, n_r2, n_h, h_1 .. h_15], the contour-pixel classes and the 2 x 2 configuration histogram (csrc/measure_shape.h), all int64;
+# _shape_columns derives the shape columns from them.
+_MEASURE_RAW = ("label", "area", "bbox", "csum", "sum", "sum2", "min", "max", "m2", "contour")
+_M2_INDEX = {(0, 0): 0, (0, 1): 1, (0, 2): 2, (1, 1): 3, (1, 2): 4, (2, 2): 5}
+_CONTOUR_WIDTH = 18
+# the counter a border pixel with a / d border neighbours along the axes / the diagonals counts into (-1: none): n_1, n_r2, n_h
+_CONTOUR_CLASS = np.full((5, 5), -1, np.int8)
+_CONTOUR_CLASS[2:4, 0:3] = 0
+_CONTOUR_CLASS[0, 2] = _CONTOUR_CLASS[1, 3] = 1
+_CONTOUR_CLASS[1, 1:3] = 2
+# skimage.measure.perimeter_crofton(., 4)'s coefficient of every 2 x 2 configuration, written as scikit-image writes them
+_CROFTON = [float(w) for w in (0, np.pi / 4 * (1 + 1 / (np.sqrt(2))), np.pi / (4 * np.sqrt(2)), np.pi / (2 * np.sqrt(2)), 0,
+                                np.pi / 4 * (1 + 1 / (np.sqrt(2))), 0, np.pi / (4 * np.sqrt(2)), np.pi / 4, np.pi / 2,
+                                np.pi / (4 * np.sqrt(2)), np.pi / (4 * np.sqrt(2)), np.pi / 4, np.pi / 2, 0, 0)]
+_SQRT2 = float(np.sqrt(2))
+_JACOBI_SWEEPS = 6
 
 
 def _measure_shapes(lbl_shape, img_shape):
@@ -141,12 +157,14 @@ def _measure_pack(raw):
                                                 else a.astype(np.int64) for a in wide], axis=1))
 
 
-def _measure_unpack(packed, nd, C, sum_dtype, mm_dtype):
+def _measure_unpack(packed, nd, C, sum_dtype, mm_dtype, shape=False):
     """the raw columns of _measure_pack's array; sum_dtype / mm_dtype: the names of the dtypes of sum, sum2 and of min, max"""
     is_t = R.is_torch(packed)
     widths = [("label", 1, "int64"), ("area", 1, "int64"), ("bbox", 2 * nd, "int64"), ("csum", nd, "int64")]
     if C is not None:
         widths += [("sum", C, sum_dtype), ("sum2", C, sum_dtype), ("min", C, mm_dtype), ("max", C, mm_dtype)]
+    if shape:
+        widths += [("m2", 6, "int64")] + ([("contour", _CONTOUR_WIDTH, "int64")] if nd == 2 else [])
     raw, at = {}, 0
     for key, w, dt in widths:
         a = packed[:, at:at + w]
@@ -162,12 +180,19 @@ def _measure_unpack(packed, nd, C, sum_dtype, mm_dtype):
     return raw
 
 
+def _tensor_sqrt(a):
+    """the correctly rounded square root of a tensor: torch's on the device; numpy's for a host tensor, where torch's goes through a
+    vector maths library that on some CPUs is an ulp off, so that host tensors and numpy arrays give the same bits"""
+    import torch
+    return torch.sqrt(a) if a.is_cuda else torch.from_numpy(np.sqrt(a.contiguous().numpy()))
+
+
 def _measure_columns(raw, nd, channel_axis):
     """the table of measure_labels from the raw columns (numpy arrays or tensors): centroid = float64(coordinate sum) / count, mean =
     float64(sum) / count, var = max(0, float64(sum2) / count - mean^2), std = sqrt(var), every operation rounded on its own"""
     if R.is_torch(raw["label"]):
         import torch
-        f64, sqrt, col = (lambda a: a.to(torch.float64)), torch.sqrt, (lambda a: a.contiguous())
+        f64, sqrt, col = (lambda a: a.to(torch.float64)), _tensor_sqrt, (lambda a: a.contiguous())
     else:
         f64, sqrt, col = (lambda a: a.astype(np.float64)), np.sqrt, np.ascontiguousarray
     out = {"label": raw["label"], "area": raw["area"]}
@@ -187,11 +212,141 @@ def _measure_columns(raw, nd, channel_axis):
         for name, a in named:
             for c in range(a.shape[1]):
                 out[("%s-%d" % (name, c)) if channel_axis else name] = col(a[:, c])
+    if "m2" in raw:
+        _shape_columns(out, raw, nd)
     return out
 
 
-def _measure_raw_host(lbl, img):
-    """the raw columns by numpy over scipy.ndimage.find_objects boxes; img: None or an array of lbl.shape (+ (C,))"""
+def _jacobi_eigvals(T, xp, sqrt):
+    """eigenvalues of the symmetric matrices T[i][j] (arrays / tensors of one length), unsorted: _JACOBI_SWEEPS cyclic Jacobi sweeps of
+    + - * / sqrt, comparisons and selects, the same code for numpy and torch (xp, sqrt).  A zero off-diagonal element is left alone; an
+    angle whose square would overflow takes its limit t = 1 / (2 theta)."""
+    n = len(T)
+    T = [list(row) for row in T]
+    for _ in range(_JACOBI_SWEEPS):
+        for p in range(n):
+            for q in range(p + 1, n):
+                apq, one = T[p][q], xp.ones_like(T[p][q])
+                zero = apq == 0
+                theta = (T[q][q] - T[p][p]) / xp.where(zero, one, 2.0 * apq)
+                big = xp.abs(theta) > 1e150
+                th = xp.where(big, one, theta)
+                t = xp.where(th < 0, -one, one) / (xp.abs(th) + sqrt(th * th + 1.0))
+                t = xp.where(big, (0.5 * one) / xp.where(big, theta, one), t)
+                t = xp.where(zero, 0.0 * one, t)
+                c = one / sqrt(t * t + 1.0)
+                s = t * c
+                T[p][p], T[q][q] = T[p][p] - t * apq, T[q][q] + t * apq
+                T[p][q] = T[q][p] = 0.0 * one
+                for r in range(n):
+                    if r not in (p, q):
+                        arp, arq = T[r][p], T[r][q]
+                        T[r][p] = T[p][r] = c * arp - s * arq
+                        T[r][q] = T[q][r] = s * arp + c * arq
+    return [T[d][d] for d in range(n)]
+
+
+def _shape_columns(out, raw, nd):
+    """adds the shape columns to the table `out` from the raw columns (numpy arrays or tensors), DESIGN.md section 3q: every operation
+    is rounded on its own, in the order written there; only orientation (atan2) and the 3D equivalent_diameter (pow) call a maths
+    library, everything else is + - * / sqrt, comparisons and selects and so has the same bits on every route"""
+    if R.is_torch(raw["label"]):
+        import torch as xp
+        f64, col, atan2, sqrt = (lambda a: a.to(xp.float64)), (lambda a: a.contiguous()), xp.atan2, _tensor_sqrt
+    else:
+        xp = np
+        f64, col, atan2, sqrt = (lambda a: a.astype(np.float64)), np.ascontiguousarray, np.arctan2, np.sqrt
+    with np.errstate(all="ignore"):
+        area = raw["area"]
+        A = f64(area)
+        start, stop = raw["bbox"][:, :nd], raw["bbox"][:, nd:]
+        s = [f64(raw["csum"][:, d] - area * start[:, d]) for d in range(nd)]
+        m2 = lambda i, j: f64(raw["m2"][:, _M2_INDEX[(i + 3 - nd, j + 3 - nd)]])
+        mu = {(i, j): m2(i, j) - s[i] * s[j] / A for i in range(nd) for j in range(i, nd)}
+        tr = mu[(0, 0)]
+        for d in range(1, nd):
+            tr = tr + mu[(d, d)]
+        T = [[((tr - mu[(i, i)]) / A) if i == j else (-mu[(min(i, j), max(i, j))] / A) for j in range(nd)] for i in range(nd)]
+        lam = [xp.where(l > 0, l, 0.0 * l) for l in _jacobi_eigvals(T, xp, sqrt)]
+        # descending by a sorting network of maxima and minima
+        for i, j in (((0, 1),) if nd == 2 else ((0, 1), (1, 2), (0, 1))):
+            lam[i], lam[j] = xp.maximum(lam[i], lam[j]), xp.minimum(lam[i], lam[j])
+        box = stop[:, 0] - start[:, 0]
+        for d in range(1, nd):
+            box = box * (stop[:, d] - start[:, d])
+        # (every division is array by array: torch divides a device tensor by a Python number by multiplying with its reciprocal)
+        one = xp.ones_like(A)
+        out["equivalent_diameter"] = sqrt(f64(4 * area) / (np.pi * one)) if nd == 2 else (f64(6 * area) / (np.pi * one)) ** (1.0 / 3.0)
+        out["extent"] = A / f64(box)
+        for i in range(nd):
+            for j in range(nd):
+                out["inertia_tensor-%d-%d" % (i, j)] = col(T[i][j])
+        for k in range(nd):
+            out["inertia_tensor_eigvals-%d" % k] = col(lam[k])
+        out["major_axis_length"] = 4.0 * sqrt(lam[0])
+        out["minor_axis_length"] = 4.0 * sqrt(lam[-1])
+        if nd == 2:
+            degenerate = lam[0] == 0
+            out["eccentricity"] = xp.where(degenerate, 0.0 * one, sqrt(1.0 - lam[1] / xp.where(degenerate, one, lam[0])))
+            a, b, c = T[0][0], T[0][1], T[1][1]
+            out["orientation"] = xp.where(a - c == 0, xp.where(b < 0, (np.pi / 4) * one, (-np.pi / 4) * one), 0.5 * atan2(-2.0 * b, c - a))
+            n = f64(raw["contour"])
+            out["perimeter"] = n[:, 0] + n[:, 1] * _SQRT2 + n[:, 2] * ((1 + _SQRT2) / 2)
+            crofton = n[:, 3] * _CROFTON[1]
+            for k in range(2, 16):
+                crofton = crofton + n[:, 2 + k] * _CROFTON[k]
+            out["perimeter_crofton"] = crofton
+            h = raw["contour"]
+            out["euler_number"] = col(h[:, 2 + 8] - h[:, 2 + 6] - h[:, 2 + 14])
+    return out
+
+
+def _shape_raw_host(lab, rows, starts):
+    """(m2 (n, 6), contour (n, 18) or None for a volume) of the labels `rows` (ascending, all that are present) of the non-negative
+    integer image lab, starts (n, nd) their boxes' starts: the definitions of csrc/measure_shape.h by numpy on the whole image"""
+    nd, n = lab.ndim, len(rows)
+    m2 = np.zeros((n, 6), np.int64)
+    contour = np.zeros((n, _CONTOUR_WIDTH), np.int64) if nd == 2 else None
+    if n == 0:
+        return m2, contour
+    row_of = np.zeros(int(rows[-1]) + 1, np.int64)
+    row_of[rows] = np.arange(n)
+    where = np.nonzero(lab)
+    r = row_of[lab[where]]
+    u = [w.astype(np.int64) - starts[r, d] for d, w in enumerate(where)]
+    for i in range(nd):
+        for j in range(i, nd):
+            np.add.at(m2[:, _M2_INDEX[(i + 3 - nd, j + 3 - nd)]], r, u[i] * u[j])
+    if nd == 3:
+        return m2, None
+    Y, X = lab.shape
+    count = lambda labels, field: np.bincount(row_of[labels] * _CONTOUR_WIDTH + field, minlength=n * _CONTOUR_WIDTH).reshape(n, _CONTOUR_WIDTH)
+    # border pixels, one pixel beyond the image too (where there are none): a pixel of l with a 4-neighbour that is not l
+    P = np.pad(lab, 2)
+    c = P[1:-1, 1:-1]
+    B = (c > 0) & ((P[:-2, 1:-1] != c) | (P[2:, 1:-1] != c) | (P[1:-1, :-2] != c) | (P[1:-1, 2:] != c))
+    near = lambda dy, dx: ((P[2 + dy:2 + dy + Y, 2 + dx:2 + dx + X] == lab) & B[1 + dy:1 + dy + Y, 1 + dx:1 + dx + X]).astype(np.uint8)
+    a = near(-1, 0) + near(1, 0) + near(0, -1) + near(0, 1)
+    d = near(-1, -1) + near(-1, 1) + near(1, -1) + near(1, 1)
+    cls = _CONTOUR_CLASS[a, d]
+    sel = B[1:-1, 1:-1] & (cls >= 0)
+    contour += count(lab[sel], cls[sel].astype(np.int64))
+    # 2 x 2 windows at i in [0, Y], j in [0, X]: bit 1 L(i, j), bit 2 L(i-1, j), bit 4 L(i, j-1), bit 8 L(i-1, j-1); every label of
+    # a window is counted at its first pixel in bit order
+    Q = np.pad(lab, 1)
+    w = [Q[1:, 1:], Q[:-1, 1:], Q[1:, :-1], Q[:-1, :-1]]
+    for k in range(4):
+        lead = w[k] > 0
+        for m in range(k):
+            lead &= w[m] != w[k]
+        code = sum((w[m] == w[k]).astype(np.uint8) << m for m in range(4))
+        contour += count(w[k][lead], 2 + code[lead].astype(np.int64))
+    return m2, contour
+
+
+def _measure_raw_host(lbl, img, shape=False):
+    """the raw columns by numpy over scipy.ndimage.find_objects boxes; img: None or an array of lbl.shape (+ (C,)); shape: with m2 and,
+    for a 2D image, contour (_shape_raw_host)"""
     if lbl.dtype.kind == "b":
         lbl = lbl.astype(np.uint8)
     if lbl.dtype.kind not in "iu":
@@ -234,12 +389,18 @@ def _measure_raw_host(lbl, img):
                 raw["sum2"][k] = (wide * wide).sum(axis=0)
                 raw["min"][k] = v.min(axis=0)
                 raw["max"][k] = v.max(axis=0)
+    if shape:
+        m2, contour = _shape_raw_host(lab, np.array([k for k, _ in boxes], np.int64), raw["bbox"][:, :nd])
+        raw["m2"] = m2
+        if contour is not None:
+            raw["contour"] = contour
     return raw
 
 
-def _measure_raw_device(lbl, img, C, device):
-    """the raw columns as tensors on the device: sd_label_boxes_device, sd_label_centroid_sums_device and, with an image,
-    sd_label_intensity_stats_device, then the rows of the labels present (one scalar, their number, comes to the host)"""
+def _measure_raw_device(lbl, img, C, device, shape=False):
+    """the raw columns as tensors on the device: sd_label_boxes_device, sd_label_centroid_sums_device, with an image
+    sd_label_intensity_stats_device and with shape sd_label_moment_sums_device and (2D) sd_label_contour_counts_device, then the rows of
+    the labels present (one scalar, their number, comes to the host)"""
     import torch
     N.require_device()
     lab, top, ids = R._device_labels(lbl, device)
@@ -256,6 +417,10 @@ def _measure_raw_device(lbl, img, C, device):
             raw.update(sum=torch.zeros((0, C), dtype=sum_t, device=dev), sum2=torch.zeros((0, C), dtype=sum_t, device=dev),
                        min=torch.zeros((0, C), dtype=torch.float32 if code == 2 else torch.int64, device=dev),
                        max=torch.zeros((0, C), dtype=torch.float32 if code == 2 else torch.int64, device=dev))
+        if shape:
+            raw["m2"] = torch.zeros((0, 6), dtype=torch.int64, device=dev)
+            if nd == 2:
+                raw["contour"] = torch.zeros((0, _CONTOUR_WIDTH), dtype=torch.int64, device=dev)
         return raw
     boxes, sums = R.label_tables(lab, top, boxes=True, sums=True)
     if img is not None:
@@ -271,10 +436,18 @@ def _measure_raw_device(lbl, img, C, device):
         a, m = acc.index_select(0, present), mm.index_select(0, present)
         raw.update(sum=a[:, :, 0], sum2=a[:, :, 1], min=m[:, :, 0] if code == 2 else m[:, :, 0].to(torch.int64),
                    max=m[:, :, 1] if code == 2 else m[:, :, 1].to(torch.int64))
+    if shape:
+        m2 = torch.empty((top + 1, 6), dtype=torch.int64, device=dev)
+        N.dcall(lab, "sd_label_moment_sums_device", R.ptr(lab), *R.zyx(lab.shape), top, R.ptr(boxes), R.ptr(m2))
+        raw["m2"] = m2.index_select(0, present)
+        if nd == 2:
+            counts = torch.empty((top + 1, _CONTOUR_WIDTH), dtype=torch.int64, device=dev)
+            N.dcall(lab, "sd_label_contour_counts_device", R.ptr(lab), *lab.shape, top, R.ptr(counts))
+            raw["contour"] = counts.index_select(0, present)
     return raw
 
 
-def measure_labels(lbl, img=None, *, device=None, as_tensors=False):
+def measure_labels(lbl, img=None, *, shape=False, device=None, as_tensors=False):
     """Per-object table of a 2D / 3D integer label image (values <= 0 are background) and, optionally, of the image `img` that was
     segmented: shape lbl.shape or lbl.shape + (C,) (channels last).  Returns a dict of 1-D columns, one row per label present,
     ascending by label, named as scikit-image 0.18's regionprops_table names them:
@@ -288,6 +461,24 @@ def measure_labels(lbl, img=None, *, device=None, as_tensors=False):
         mean_intensity         float64  float64(sum) / count
         min_intensity, max_intensity    int64 / the image's float type
         std_intensity          float64  population standard deviation: sqrt(max(0, float64(sum of squares) / count - mean^2))
+      with shape=True, after the columns above (pixel units; float64 but for euler_number, int64):
+        equivalent_diameter    sqrt(4 area / pi); 3D: (6 area / pi) ** (1 / 3)
+        extent                 area / volume of the bounding box
+        inertia_tensor-i-j     all nd^2 entries, from the second-order sums of the box-local coordinates
+        inertia_tensor_eigvals-k   descending, clipped at 0 (six cyclic Jacobi sweeps)
+        major_axis_length, minor_axis_length   4 sqrt(largest / smallest eigenvalue)
+      and for a 2D image:
+        eccentricity           sqrt(1 - l_1 / l_0), 0 where l_0 = 0
+        orientation            0.5 atan2(-2 b, c - a) of the tensor [[a, b], [b, c]]; where a - c == 0: pi / 4 for b < 0, else -pi / 4
+        perimeter              skimage.measure.perimeter(mask, 4)
+        perimeter_crofton      skimage.measure.perimeter_crofton(mask, 4)
+        euler_number           skimage.measure.euler_number(mask, connectivity=2)
+
+    The shape columns are scikit-image 0.18's regionprops_table columns of these names, computed from integer tables per object
+    (second-order coordinate sums, three counts of contour-pixel classes, a histogram of 2 x 2 pixel configurations: DESIGN.md section
+    3q), on which the routes agree exactly.  One deviation, on purpose: where a - c == 0 scikit-image 0.18.3 returns -pi / 4 for b < 0 and
+    pi / 4 otherwise, which is 90 degrees from the limit of its own general formula; this function returns the limit.  A call with
+    shape=True whose pixel count times the square of the largest extent reaches 2^63 raises ValueError before anything runs.
 
     Arithmetic: integer images are summed (values and squares) in int64, exactly, also beyond 2^53; float images in float64, where
     every square of a float32 is exact.  The derived columns are computed in one place for both routes, every operation rounded on
@@ -309,20 +500,25 @@ def measure_labels(lbl, img=None, *, device=None, as_tensors=False):
         img = np.asarray(img)
     nd = len(lbl.shape)
     C, channel_axis = _measure_shapes(tuple(lbl.shape), None if img is None else tuple(img.shape))
+    shape = bool(shape)
+    if shape and lbl.shape and int(np.prod([int(n) for n in lbl.shape], dtype=object)) * max(int(n) for n in lbl.shape) ** 2 >= 2 ** 63:
+        raise ValueError("measure_labels: shape=True needs (number of pixels) x (largest extent)^2 below 2^63, got shape %s" % (tuple(lbl.shape),))
+    more = {"shape": True} if shape else {}                                 # without shape the two halves are called as before
     lbl_ok = (str(lbl.dtype) in _DEVICE_LABEL_DTYPES) if lbl_t else (lbl.dtype.kind in "iu")
     img_ok = img is None or (str(img.dtype) if img_t else "torch." + img.dtype.name) in _DEVICE_DTYPE_CODE
     if on_device and lbl_ok and img_ok:
-        raw = _measure_raw_device(lbl, img, C, device)
+        raw = _measure_raw_device(lbl, img, C, device, **more)
         if as_tensors:
             return _measure_columns(raw, nd, channel_axis)
         from .utils import to_host
         sum_dtype, mm_dtype = (str(raw["sum"].dtype)[6:], str(raw["min"].dtype)[6:]) if img is not None else (None, None)
-        return _measure_columns(_measure_unpack(to_host(_measure_pack(raw)), nd, C, sum_dtype, mm_dtype), nd, channel_axis)
+        return _measure_columns(_measure_unpack(to_host(_measure_pack(raw)), nd, C, sum_dtype, mm_dtype, shape), nd, channel_axis)
     if not as_tensors:
-        return _measure_columns(_measure_raw_host(lbl.cpu().numpy() if lbl_t else lbl, img.cpu().numpy() if img_t else img), nd, channel_axis)
+        return _measure_columns(_measure_raw_host(lbl.cpu().numpy() if lbl_t else lbl, img.cpu().numpy() if img_t else img, **more), nd,
+                                channel_axis)
     # the host table as tensors where the labels are (or on `device`): the packed raw columns make the trip
     import torch
-    host_packed = lambda l, i=None: _measure_pack(_measure_raw_host(l, i))
+    host_packed = lambda l, i=None: _measure_pack(_measure_raw_host(l, i, **more))
     rest = () if img is None else (img,)
     if lbl_t:
         packed = R.via_host(host_packed, lbl, *rest, to=device)
@@ -334,7 +530,7 @@ def measure_labels(lbl, img=None, *, device=None, as_tensors=False):
         name = str(img.dtype)[6:] if img_t else img.dtype.name
         floating = name.startswith("float") or name.startswith("bfloat")
         sum_dtype, mm_dtype = ("float64", name) if floating else ("int64", "int64")
-    return _measure_columns(_measure_unpack(packed, nd, C, sum_dtype, mm_dtype), nd, channel_axis)
+    return _measure_columns(_measure_unpack(packed, nd, C, sum_dtype, mm_dtype, shape), nd, channel_axis)
 
 
 # ----------------------------------------------------------------------------- connected components: mask -> label image

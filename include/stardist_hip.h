@@ -750,6 +750,42 @@ int sd_nearest_feature_device(const void* d_img, int dtype, int Z, int Y, int X,
 int sd_expand_labels_device(const int32_t* d_lbl, int Z, int Y, int X, double sz, double sy, double sx, double distance, int32_t* d_out,
                             void* stream);
 
+/* ---- label clean-up (csrc/label_edit.hip, csrc/label_edit.h): the device halves of stardist_amd.utils.find_boundaries, clear_border and
+ * remove_small_objects, i.e. of skimage.segmentation.find_boundaries / clear_border and skimage.morphology.remove_small_objects (0.18) --
+ * Images are (Z, Y, X) contiguous int32 (2D: Z = 1, the z axis then takes no part).  Integer arithmetic only, 64-bit offsets, no
+ * atomics: every result depends on the input alone, the same bits from call to call.  No input is written.  Bad arguments set the
+ * error string and return -1 before anything is launched: a null pointer, a non-positive extent or table size, an output that is an
+ * input, more than 2^31 - 1 pixels, and what each entry names.  Nothing is copied to the host and the stream is not synchronised.
+ *
+ * Boundaries: d_out[p] (uint8) = 1 where p is a boundary pixel, else 0.  With N_c(p) = the in-image neighbours of p whose offsets have at
+ * most `connectivity` (1 .. 3; with Z = 1, 2 and 3 are the same) non-zero coordinates -- a neighbour outside the image does not exist --
+ *   mode 0 (thick)  some q in N_c(p) has lbl[q] != lbl[p]
+ *   mode 1 (inner)  thick and lbl[p] != background
+ *   mode 2 (outer)  thick and (lbl[p] == background or the maximum of lbl over W(p) != the minimum of lbl' over W(p)), W(p) = p and all its
+ *                   in-image neighbours (full connectivity whatever `connectivity` is), lbl' = lbl with every background pixel replaced
+ *                   by `sentinel` (scikit-image takes the largest value of the image's dtype)
+ * background and sentinel are compared as 64-bit values, so either may lie outside int32.  One workgroup per tile, the tile with a halo
+ * of 1 in LDS: one read of the labels, one byte written per pixel.  Also -1 for a connectivity or a mode outside its range. */
+int sd_find_boundaries_device(const int32_t* d_lbl, int Z, int Y, int X, int connectivity, int mode, long long background, long long sentinel,
+                              uint8_t* d_out, void* stream);
+
+/* Border flags: d_flags (n_flags bytes; the call zeroes it) gets d_flags[k] = 1 for every key k = d_key[p] in 0 .. n_flags - 1 -- the
+ * component image of sd_label_components_device, 0 being the background -- of a pixel p that
+ *   d_mask == NULL  lies within buffer_size + 1 (buffer_size >= 0) of an image edge along y or x, and with ndim = 3 along z too (ndim = 2
+ *                   needs Z = 1); only these pixels are visited
+ *   d_mask given    has d_mask[p] == 0 (uint8, (Z, Y, X)); one pass over the mask, buffer_size is ignored
+ * A key outside the table is ignored.  Every writer stores the same 1 with a vector store, so the order of the stores does not matter.
+ * Also -1 for ndim outside 2 / 3 and for a negative buffer_size. */
+int sd_label_border_flags_device(const int32_t* d_key, int Z, int Y, int X, int ndim, int buffer_size, const uint8_t* d_mask, long long n_flags,
+                                 uint8_t* d_flags, void* stream);
+
+/* Clear what is flagged: d_out[p] = d_flags[d_key[p]] ? bgval : d_val[p] over n pixels (a key outside 0 .. n_flags - 1 counts as not
+ * flagged).  d_key is the component image (clear_border) or d_val itself (remove_small_objects, whose flags say "fewer than min_size
+ * pixels", from the counts of sd_label_centroid_sums_device).  One read of each image, one write; 16-byte accesses where the
+ * pointers and n allow. */
+int sd_label_clear_flagged_device(const int32_t* d_val, const int32_t* d_key, const uint8_t* d_flags, long long n_flags, long long n, int bgval,
+                                  int32_t* d_out, void* stream);
+
 /* The augmentation chain of a training batch (stardist_amd.augment.Compose.apply_device; the rules are csrc/augment.h's) in ONE launch:
  * d_x (B, *shape) float32 and d_y (B, *shape) int32, nd = 2 or 3 extents in h_shape, give d_out_x and d_out_y of the same shapes
  * (not the inputs): per sample FlipRot90 (always, as an index map), then Warp (flags bit 0; bit 1: mode 'reflect', else 'constant'),

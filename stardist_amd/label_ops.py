@@ -1,5 +1,6 @@
 """Functions of label images with a host route (numpy + scipy, like the reference's) and a device route (hand-written HIP):
-fill_label_holes, calculate_extents, measure_labels, label_components, expand_labels, distance_transform.  stardist_amd.utils re-exports
+fill_label_holes, calculate_extents, measure_labels, label_components, expand_labels, distance_transform, find_boundaries, clear_border,
+remove_small_objects, select_labels.  stardist_amd.utils re-exports
 the public names.  Which route a call takes and what comes back is one rule, DESIGN.md section 3p, and its code is stardist_amd._route;
 a `_X_device` half here allocates its outputs and calls its kernels."""
 import numpy as np
@@ -784,3 +785,429 @@ def distance_transform(img, sampling=None, *, max_distance=None, return_distance
             import torch
             dist, idx = (None if a is None else torch.from_numpy(a) for a in (dist, idx))
     return (dist, idx) if return_distances and return_indices else (dist if return_distances else idx)
+
+
+# ----------------------------------------------------------------------------- label clean-up: find_boundaries, clear_border,
+# remove_small_objects, select_labels (csrc/label_edit.hip).  The first three are scikit-image 0.18's functions
+# of these names without `in_place`; their host routes are numpy and scipy, the device routes equal them.
+_BOUNDARY_MODES = {"thick": 0, "inner": 1, "outer": 2}
+_INT32_MIN, _INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def _whole_number(v):
+    """the int a scalar argument stands for, or None where it is no whole number below 2^63 in magnitude"""
+    if isinstance(v, (bool, np.bool_, int, np.integer)):
+        v = int(v)
+    elif isinstance(v, (float, np.floating)) and float(v).is_integer():
+        v = int(v)
+    else:
+        return None
+    return v if abs(v) < 2 ** 63 else None
+
+
+def _int32_values_device(x, device):
+    """the contiguous int32 device tensor with the values of x as they are (negative ones too), or None where x's dtype or values do
+    not fit: x a numpy array (uploaded to `device`) or a tensor (moved there if it is elsewhere) of a bool or integer dtype.  int64
+    values are checked first: a tensor's smallest and largest value come to the host in one copy."""
+    import torch
+    if isinstance(x, np.ndarray):
+        if x.dtype.kind not in "iub" or x.dtype == np.uint64:
+            return None
+        if x.dtype.itemsize >= 4 and x.dtype != np.int32 and x.size and (int(x.min()) < _INT32_MIN or int(x.max()) > _INT32_MAX):
+            return None
+        return R.to_device_tensor(x.astype(np.int32, copy=False), device)
+    if str(x.dtype) not in _DEVICE_LABEL_DTYPES + ("torch.bool",):
+        return None
+    t = R.to_device_tensor(x, device)
+    if t.dtype == torch.int64 and t.numel():
+        lo, hi = torch.stack([t.min(), t.max()]).tolist()
+        if lo < _INT32_MIN or hi > _INT32_MAX:
+            return None
+    return t.to(torch.int32).contiguous()
+
+
+def _dtype_max(x):
+    """the largest value of the integer dtype of the array / tensor x (a bool image counts as uint8), or None for another dtype"""
+    name = str(x.dtype).replace("torch.", "")
+    if name == "bool":
+        return 255
+    try:
+        return int(np.iinfo(np.dtype(name)).max)
+    except (TypeError, ValueError):
+        return None
+
+
+def _distinct_count_exceeds_two(stack):
+    """per position, whether the values stack[:, ...] hold more than two different ones"""
+    s = np.sort(stack, axis=0)
+    return (s[1:] != s[:-1]).sum(axis=0) > 1
+
+
+def _find_boundaries_subpixel_host(a):
+    """scikit-image's mode 'subpixel': the image on a grid of twice the resolution (2 n - 1 per axis), the pixels at the even positions,
+    every other position an edge cell holding the dtype's largest value; an edge cell is a boundary where its 3^nd window of the grid,
+    padded with 0, holds more than two different values"""
+    from itertools import product
+    nd = a.ndim
+    grid = np.full([max(2 * s - 1, 0) for s in a.shape], np.iinfo(a.dtype).max, a.dtype)
+    even = (slice(None, None, 2),) * nd
+    grid[even] = a
+    edge = np.ones(grid.shape, bool)
+    edge[even] = False
+    if grid.size == 0:
+        return np.zeros(grid.shape, bool)
+    padded = np.pad(grid, 1, mode="constant", constant_values=0)
+    windows = np.stack([padded[tuple(slice(1 + d, 1 + d + n) for d, n in zip(off, grid.shape))] for off in product((-1, 0, 1), repeat=nd)])
+    return _distinct_count_exceeds_two(windows) & edge
+
+
+def _find_boundaries_host(a, connectivity, mode, background):
+    """scikit-image 0.18's find_boundaries by scipy.ndimage.grey_dilation / grey_erosion, composed as there"""
+    from scipy import ndimage as ndi
+    if a.dtype == np.bool_:
+        a = a.astype(np.uint8)
+    if mode == "subpixel":
+        return _find_boundaries_subpixel_host(a)
+    if a.size == 0:
+        return np.zeros(a.shape, bool)
+    top = np.iinfo(a.dtype).max
+    if a.dtype.itemsize == 8:
+        # scipy's filters compute in float64, which holds neither every 64-bit id nor the dtype's largest value (scikit-image's result
+        # for such an image depends on how the platform converts 2^63 back).  The rules only compare values, so they are applied to the
+        # values' ranks, which float64 holds
+        values, ranks = np.unique(a, return_inverse=True)
+        at = np.searchsorted(values, background) if values[0] <= background <= values[-1] else 0
+        background = int(at) if values[at] == background else -1
+        a, top = ranks.reshape(a.shape).astype(np.int64), len(values)
+    near = ndi.generate_binary_structure(a.ndim, connectivity)
+    out = ndi.grey_dilation(a, footprint=near) != ndi.grey_erosion(a, footprint=near)
+    if mode == "inner":
+        out &= a != background
+    elif mode == "outer":
+        is_bg = a == background
+        window = ndi.generate_binary_structure(a.ndim, a.ndim)
+        raised = a.copy()
+        raised[is_bg] = top
+        adjacent = (ndi.grey_dilation(a, footprint=window) != ndi.grey_erosion(raised, footprint=window)) & ~is_bg
+        out &= is_bg | adjacent
+    return out
+
+
+def _find_boundaries_device(lab, connectivity, mode, background, sentinel):
+    """the uint8 boundary image of the int32 device tensor lab (2D / 3D) through sd_find_boundaries_device"""
+    import torch
+    out = torch.empty(lab.shape, dtype=torch.uint8, device=lab.device)
+    if lab.numel():
+        N.dcall(lab, "sd_find_boundaries_device", R.ptr(lab), *R.zyx(lab.shape), int(connectivity), _BOUNDARY_MODES[mode], int(background),
+                int(sentinel), R.ptr(out))
+    return out
+
+
+def find_boundaries(label_img, connectivity=1, mode="thick", background=0, *, device=None):
+    """The boundaries between the labelled regions of an image as a bool image, as skimage.segmentation.find_boundaries(label_img,
+    connectivity, mode, background) of scikit-image 0.18 gives them.  With N_c(p) the neighbours of p inside the image whose offsets have
+    at most c = `connectivity` (1 .. ndim) non-zero coordinates:
+
+        thick     p has a neighbour in N_c(p) with another value
+        inner     thick, and p is not background
+        outer     thick, and p is background or the largest value in p's full 3^ndim window differs from the window's smallest value
+                  after every background pixel was raised to the dtype's largest value: an object pixel next to another object
+        subpixel  the boundaries on a grid of 2 n - 1 positions per axis
+
+    A bool image is taken as uint8.  DESIGN.md section 3r states the rules and how they follow from scikit-image's morphology.
+
+    Routing: DESIGN.md section 3p; the host code is scipy.ndimage.grey_dilation / grey_erosion.  The device route takes 2D / 3D bool and
+    integer images whose values fit int32 and a background that is a whole number, and equals the host result (csrc/label_edit.hip: a
+    tile of labels with a halo of 1 in local memory, one read of the labels, one byte written per pixel; the input is not written).
+    Nothing is read back but, for an int64 tensor, its smallest and largest value in one copy.  mode="subpixel" takes the host route on
+    every input, like an image of another rank, of a float dtype or with values beyond int32, and comes back in the input's kind.  A
+    connectivity outside 1 .. ndim, an unknown mode or, on the device, more than 2^31 - 1 pixels raise ValueError before anything
+    runs."""
+    label_img, is_t, on_device = R.classify(label_img, device)
+    nd = len(label_img.shape)
+    if isinstance(connectivity, (bool, np.bool_)) or not isinstance(connectivity, (int, np.integer)) or not 1 <= connectivity <= max(nd, 1):
+        raise ValueError("find_boundaries: connectivity for %dD images must be in [1, ..., %d], got %r" % (nd, nd, connectivity))
+    if mode not in _BOUNDARY_MODES and mode != "subpixel":
+        raise ValueError("find_boundaries: mode must be 'thick', 'inner', 'outer' or 'subpixel', got %r" % (mode,))
+    connectivity = int(connectivity)
+    bg, sentinel = _whole_number(background), _dtype_max(label_img)
+    if on_device and mode != "subpixel" and nd in (2, 3) and bg is not None and sentinel is not None and sentinel < 2 ** 63:
+        R.check_pixel_count(label_img.shape, "find_boundaries")
+        N.require_device()
+        lab = _int32_values_device(label_img, device)
+        if lab is not None:
+            out = _find_boundaries_device(lab, connectivity, mode, bg, sentinel)
+            if is_t:
+                import torch
+                return out.to(torch.bool)
+            from .utils import to_host
+            return to_host(out).astype(np.bool_)
+    if is_t:
+        return R.via_host(_find_boundaries_host, label_img, connectivity, mode, background, to=device)
+    return _find_boundaries_host(label_img, connectivity, mode, background)
+
+
+def _border_band(shape, ext):
+    """bool image: the pixels within ext of an edge along any axis"""
+    band = np.zeros(shape, bool)
+    for d in range(len(shape)):
+        at = [slice(None)] * len(shape)
+        at[d] = slice(ext)
+        band[tuple(at)] = True
+        at[d] = slice(-ext, None)
+        band[tuple(at)] = True
+    return band
+
+
+def _clear_border_host(a, buffer_size, bgval, mask):
+    outside = _border_band(a.shape, buffer_size + 1) if mask is None else ~mask
+    out = a.copy()
+    if a.size == 0:
+        return out
+    comp = _label_components_host(a, a.ndim, 0)[0]
+    hit = np.zeros(int(comp.max()) + 1, bool)
+    hit[comp[outside]] = True
+    out[hit[comp]] = bgval
+    return out
+
+
+def _clear_border_device(val, nd, buffer_size, bgval, mask):
+    """clear_border of the int32 device tensor val (2D / 3D): sd_label_components_device under full connectivity, then
+    sd_label_border_flags_device and sd_label_clear_flagged_device; mask: None or a uint8 device tensor of val's shape"""
+    import torch
+    out = torch.empty_like(val)
+    if val.numel():
+        comp, _ = _label_components_device(val, nd, 0, None)
+        n, n_flags = val.numel(), val.numel() + 1                               # no more components than pixels, and the background
+        flags = torch.empty(n_flags, dtype=torch.uint8, device=val.device)
+        N.dcall(val, "sd_label_border_flags_device", R.ptr(comp), *R.zyx(val.shape), nd, int(buffer_size), R.opt_ptr(mask), n_flags, R.ptr(flags))
+        N.dcall(val, "sd_label_clear_flagged_device", R.ptr(val), R.ptr(comp), R.ptr(flags), n_flags, n, int(bgval), R.ptr(out))
+    return out
+
+
+def clear_border(labels, buffer_size=0, bgval=0, mask=None, *, device=None):
+    """Clear the objects connected to the image border, as skimage.segmentation.clear_border(labels, buffer_size, bgval, mask=mask) of
+    scikit-image 0.18 does (there is no `in_place`: the input is never written).  It works on connected components, not on ids: the
+    components are those of label_components(labels, background=0) -- equal values joined under full connectivity -- and a component is
+    cleared, its pixels set to `bgval`, when one of its pixels lies within buffer_size + 1 of an image edge along any axis; with a bool
+    `mask` of the image's shape, when one of its pixels lies where the mask is False (buffer_size is then ignored).  Of an id with two
+    components only the one at the border goes.  scikit-image's quirk is kept: the background counts as component 0, so if any
+    background pixel lies in the band (or outside the mask) every background pixel becomes `bgval`, which shows with bgval != 0.
+
+    Routing: DESIGN.md section 3p, by `labels`; a mask that is elsewhere is moved to the labels' place.  The host code is numpy on the
+    project's label_components host route.  The device route takes 2D / 3D bool and integer images whose values fit int32 and a bgval
+    that is a whole number of the image's dtype, and equals the host result (csrc/label_cc.hip, then csrc/label_edit.hip: only the
+    band's pixels are visited for the flags, or the mask in one pass; one more pass clears).  Nothing is read back but, for an int64
+    tensor, its smallest and largest value in one copy.  Everything else goes through the host code and comes back in the input's kind.
+    Errors, scikit-image's: ValueError for a buffer_size >= an extent without a mask, AssertionError for a mask of another shape,
+    TypeError for a mask that is not bool; and ValueError for a negative buffer_size or, on the device, more than 2^31 - 1 pixels."""
+    labels, is_t, on_device = R.classify(labels, device)
+    nd = len(labels.shape)
+    buffer_size = int(buffer_size)
+    if buffer_size < 0:
+        raise ValueError("clear_border: buffer_size must be >= 0")
+    if mask is None and any(buffer_size >= s for s in labels.shape):
+        raise ValueError("buffer size may not be greater than image size")
+    mask_t = mask is not None and R.is_torch(mask)
+    if mask is not None:
+        if not mask_t:
+            mask = np.asarray(mask)
+        if tuple(mask.shape) != tuple(labels.shape):
+            raise AssertionError("image and mask should have the same shape but are %s and %s" % (tuple(labels.shape), tuple(mask.shape)))
+        if str(mask.dtype).replace("torch.", "") != "bool":
+            raise TypeError("mask should be of type bool.")
+    fill, top = _whole_number(bgval), _dtype_max(labels)
+    name = str(labels.dtype).replace("torch.", "")
+    fits = fill is not None and top is not None and (name == "bool" or (0 if name.startswith("u") else -top - 1) <= fill <= top) \
+        and _INT32_MIN <= fill <= _INT32_MAX
+    if on_device and nd in (2, 3) and fits:
+        R.check_pixel_count(labels.shape, "clear_border")
+        N.require_device()
+        val = _int32_values_device(labels, device)
+        if val is not None:
+            m = None if mask is None else R.to_device_tensor(mask, val.device)
+            return R.like_input(_clear_border_device(val, nd, buffer_size, fill, m), labels)
+    host_mask = None if mask is None else (mask.cpu().numpy() if mask_t else mask)
+    if is_t:
+        return R.via_host(_clear_border_host, labels, buffer_size, bgval, host_mask, to=device)
+    return _clear_border_host(labels, buffer_size, bgval, host_mask)
+
+
+_NEGATIVE_LABELS = ("Negative value labels are not supported. Try relabeling the input with `scipy.ndimage.label` or "
+                    "`skimage.morphology.label`.")
+
+
+def _remove_small_objects_host(a, min_size, connectivity):
+    out = a.copy()
+    if min_size == 0 or a.size == 0:
+        return out
+    if a.dtype == np.bool_:
+        from scipy import ndimage as ndi
+        keys = ndi.label(a, ndi.generate_binary_structure(a.ndim, connectivity))[0]
+    else:
+        keys = a
+        if a.dtype.kind == "i" and int(a.min()) < 0:
+            raise ValueError(_NEGATIVE_LABELS)
+    if int(keys.max()) <= 4 * keys.size + 1024:
+        sizes = np.bincount(keys.reshape(-1))
+        if len(sizes) == 2 and a.dtype != np.bool_:
+            import warnings
+            warnings.warn("Only one label was provided to `remove_small_objects`. Did you mean to use a boolean array?")
+        out[(sizes < min_size)[keys]] = 0
+    else:                                                                   # sparse huge ids: the same counts without the table
+        ids, inv, sizes = np.unique(keys, return_inverse=True, return_counts=True)
+        out[(sizes < min_size)[inv.reshape(keys.shape)]] = 0
+    return out
+
+
+def _clear_small_device(val, key, top, min_size):
+    """val with the pixels cleared whose key (1 .. top; val itself or a component image) has fewer than min_size pixels: the count column
+    of sd_label_centroid_sums_device, then sd_label_clear_flagged_device"""
+    import torch
+    sizes = R.label_tables(key, top, sums=True)[1][:, 0]
+    flags = (sizes < min_size).to(torch.uint8).contiguous()
+    out = torch.empty_like(val)
+    N.dcall(val, "sd_label_clear_flagged_device", R.ptr(val), R.ptr(key), R.ptr(flags), top + 1, val.numel(), 0, R.ptr(out))
+    return out
+
+
+def remove_small_objects(ar, min_size=64, connectivity=1, *, device=None):
+    """Remove the objects smaller than `min_size` pixels, as skimage.morphology.remove_small_objects(ar, min_size, connectivity) of
+    scikit-image 0.18 does (there is no `in_place`: the input is never written).  An integer image is taken per id, not per component:
+    an id whose pixels, wherever they lie, number fewer than min_size becomes 0, and `connectivity` plays no part; a negative value
+    raises ValueError.  A bool image is taken per connected component of scipy.ndimage.label(ar, generate_binary_structure(ndim,
+    connectivity)), and bool comes back.  min_size = 0 returns a copy.
+
+    Routing: DESIGN.md section 3p; the host code is np.bincount, and it alone keeps scikit-image's warning about an image with one label.
+    The device route takes 2D / 3D bool and integer images and equals the host result: for an integer image the pixel counts of
+    sd_label_centroid_sums_device, for a mask label_components and the counts of its components, then one pass that clears
+    (csrc/label_edit.hip).  Ids beyond int32, or sparse huge ids, are compacted in ascending order for the call and mapped back.  Read
+    back: the largest value (as for every label function) and, for a tensor, the smallest, to refuse negative values; for a mask the
+    number of components instead.  An image that is neither bool nor integer or, on the device, more than 2^31 - 1 pixels raise
+    ValueError before anything runs; so does, for a mask only, a connectivity outside 1 .. ndim (scipy would clamp it; one rule for both
+    routes, as label_components has it)."""
+    ar, is_t, on_device = R.classify(ar, device)
+    nd = len(ar.shape)
+    name = str(ar.dtype).replace("torch.", "")
+    if name != "bool" and not (name.startswith("int") or name.startswith("uint")):
+        raise ValueError("Only bool or integer image types are supported. Got %s." % name)
+    if name != "bool":
+        connectivity = 1                                                    # an integer image is taken per id: no part in it
+    elif isinstance(connectivity, (bool, np.bool_)) or not isinstance(connectivity, (int, np.integer)) or not 1 <= connectivity <= max(nd, 1):
+        raise ValueError("remove_small_objects: connectivity for %dD masks must be in [1, ..., %d], got %r" % (nd, nd, connectivity))
+    size = int(np.prod(ar.shape, dtype=np.int64))
+    if min_size == 0 or size == 0:
+        return ar.clone() if is_t else ar.copy()
+    if on_device and nd in (2, 3) and (name == "bool" or not is_t or str(ar.dtype) in _DEVICE_LABEL_DTYPES) and name != "uint64":
+        import torch
+        R.check_pixel_count(ar.shape, "remove_small_objects")
+        if name.startswith("int") and not is_t and int(ar.min()) < 0:
+            raise ValueError(_NEGATIVE_LABELS)
+        N.require_device()
+        if name == "bool":
+            comp, count = _label_components_device(ar, int(connectivity), 0, device)
+            n = int(count)
+            if n == 0:
+                return ar.clone() if is_t else ar.copy()
+            mask = R.to_device_tensor(ar, comp.device).to(torch.int32)
+            return R.like_input(_clear_small_device(mask, comp, n, min_size), ar)
+        if name.startswith("int") and is_t and int(ar.min()) < 0:
+            raise ValueError(_NEGATIVE_LABELS)
+        lab, top, ids = R._device_labels(ar, device)
+        if top == 0:
+            return ar.clone() if is_t else ar.copy()
+        return R.like_input(_clear_small_device(lab, lab, top, min_size), ar, ids)
+    if is_t:
+        return R.via_host(_remove_small_objects_host, ar, min_size, int(connectivity), to=device)
+    return _remove_small_objects_host(ar, min_size, int(connectivity))
+
+
+def _wanted_ids_host(labels):
+    """the ids of `labels` (an array, a tensor, a sequence or one id) as a 1-D numpy array of an integer dtype"""
+    w = labels.detach().cpu().numpy() if R.is_torch(labels) else np.asarray(labels)
+    w = w.reshape(-1)
+    if w.size == 0:
+        return np.zeros(0, np.int64)
+    if w.dtype.kind == "b":
+        w = w.astype(np.uint8)
+    if w.dtype.kind not in "iu":
+        raise ValueError("select_labels: the ids must be integers, got %s" % w.dtype)
+    return w
+
+
+def _select_labels_host(a, wanted, invert, relabel):
+    keep = np.isin(a, wanted)
+    keep = (~keep if invert else keep) & (a > 0)
+    out = np.where(keep, a, 0).astype(a.dtype)
+    if relabel:
+        inv = np.unique(out[keep], return_inverse=True)[1]
+        out[keep] = (inv.reshape(-1) + 1).astype(a.dtype)
+    return out
+
+
+def _select_labels_device(lbl, labels, invert, relabel, device):
+    """select_labels through sd_relabel_stack_device with one frame: a table over the ids 1 .. top whose entry is the id itself (or its
+    rank among the ids kept and present, with relabel) where the id is kept, else 0; built on the device, nothing is read back"""
+    import ctypes
+    import torch
+    lab, top, ids = R._device_labels(lbl, device)
+    dev = lab.device
+    if lab.numel() == 0 or top == 0:
+        return R.like_input(torch.zeros_like(lab), lbl)
+    if R.is_torch(labels):
+        if labels.dtype.is_floating_point or labels.dtype.is_complex:
+            raise ValueError("select_labels: the ids must be integers, got %s" % labels.dtype)
+        w = labels.detach().reshape(-1).to(dev).to(torch.int64)
+    else:
+        w = _wanted_ids_host(labels)
+        w = torch.as_tensor(w[(w > 0) & (w <= 2 ** 63 - 1)].astype(np.int64), device=dev)
+    if ids is not None:                                                     # compacted: an original id -> its place among the ids
+        ids_t = (ids if R.is_torch(ids) else torch.as_tensor(ids.astype(np.int64), device=dev)).to(torch.int64)
+        at = torch.searchsorted(ids_t, w).clamp(max=top)
+        w = torch.where(ids_t[at] == w, at, torch.zeros_like(at))
+    else:
+        w = torch.where((w > 0) & (w <= top), w, torch.zeros_like(w))
+    keep = torch.zeros(top + 1, dtype=torch.bool, device=dev)
+    keep[w] = True
+    if invert:
+        keep = ~keep
+    keep[0] = False
+    if relabel:
+        keep &= R.label_tables(lab, top, sums=True)[1][:, 0] > 0
+        new = torch.cumsum(keep, 0) * keep
+    else:
+        new = torch.arange(top + 1, device=dev) * keep
+    table_ids = torch.arange(1, top + 1, dtype=torch.int32, device=dev)
+    table_new = new[1:].to(torch.int32).contiguous()
+    out = torch.empty_like(lab)
+    N.dcall(lab, "sd_relabel_stack_device", R.ptr(lab), 1, ctypes.c_longlong(lab.numel()), R.ptr(table_ids), R.ptr(table_new),
+            (ctypes.c_longlong * 2)(0, top), (ctypes.c_int32 * 1)(top), R.ptr(out))
+    return R.like_input(out, lbl, None if relabel else ids)
+
+
+def select_labels(lbl, labels, *, invert=False, relabel=False, device=None):
+    """Keep the objects of the label image `lbl` whose ids are in `labels`; every other pixel becomes 0.  `labels`: an array, a tensor
+    or a sequence of ids, for example table["label"][table["area"] > 50] of measure_labels(as_tensors=True); ids that the image does
+    not hold, and ids <= 0, select nothing (values <= 0 are background and come out as 0).  invert=True keeps the other objects
+    instead.  relabel=True renumbers what is kept to 1 .. n in ascending order of the ids.  The project's own function: with
+    measure_labels it is the filter between "labels" and "measure".
+
+    Routing: DESIGN.md section 3p, by `lbl`; the host code is np.isin.  The device route takes integer images of any rank and equals
+    the host result: a table over the ids, built on the device from `labels` wherever they live, applied by sd_relabel_stack_device
+    (csrc/relabel.hip) with one frame -- no kernel of its own; with relabel the ids present come from sd_label_centroid_sums_device
+    (2D / 3D images; another rank takes the host code).  Ids beyond int32, or sparse huge ids, are compacted in ascending order for
+    the call and mapped back.  Nothing is read back beyond the largest id.  An image or ids that are not integers raise ValueError."""
+    lbl, is_t, on_device = R.classify(lbl, device)
+    name = str(lbl.dtype).replace("torch.", "")
+    if not (name.startswith("int") or name.startswith("uint")):
+        raise ValueError("select_labels: the label image must have an integer type, got %s" % name)
+    invert, relabel = bool(invert), bool(relabel)
+    kernel_dtype = (str(lbl.dtype) in _DEVICE_LABEL_DTYPES) if is_t else name != "uint64"
+    if on_device and kernel_dtype and (not relabel or len(lbl.shape) in (2, 3)):
+        R.check_pixel_count(lbl.shape, "select_labels")
+        N.require_device()
+        return _select_labels_device(lbl, labels, invert, relabel, device)
+    wanted = _wanted_ids_host(labels)
+    if is_t:
+        return R.via_host(_select_labels_host, lbl, wanted, invert, relabel, to=device)
+    return _select_labels_host(lbl, wanted, invert, relabel)

@@ -83,7 +83,12 @@ int sd_get_option(const char* name);
  *        2 greedy rounds, 3 ordered neighbour relations (2 x the entries the lists store), 4 pair-kernel time ns (HIP events on `stream`),
  *        5 pair-kernel launches, 6 exact-join kernel ns, 7 build+bin+neighbour kernels ns, 8 capacity spills,
  *        9 pairs decided by the area enclosure (counted in 0 as well), 10 undecided pairs deferred to the tail batch,
- *        11 undecided pairs not swept because another pair had suppressed their j meanwhile (counted in 0 as well), 12.. 0}.
+ *        11 undecided pairs not swept because another pair had suppressed their j meanwhile (counted in 0 as well),
+ *        12 slot total of the single-pass neighbour lists: the sum over the candidates of the population of the cells each list is built
+ *           from, a true 64-bit sum, whichever form the lists took (0 for a call that ends before the lists),
+ *        13 form of the neighbour lists: 1 = one pass into slots, 0 = two passes (asked for by "nms2d_neighbours_single_pass" = 0, or
+ *           because the slot total is 2^31 - 1 or more or the slots do not fit the workspace), 14.. 0}.
+ * Beyond 2^31 - 2 stored neighbour entries the call fails ("exceed the capacity of one call"); every total involved is summed in 64 bits.
  */
 int sd_nms2d_host(const float* dist, const float* points, int n_polys, int n_rays,
                   int use_kdtree, int use_bbox, int verbose, float threshold,
@@ -110,6 +115,10 @@ int sd_nms2d_old_host(const int32_t* polys, int n_polys, int n_rays, const int32
                       float threshold, int max_bbox_search, int grid_y, int grid_x, int verbose, uint8_t* keep);
 int sd_nms2d_old_device(const int32_t* d_polys, int n_polys, int n_rays, const int32_t* d_mapping, int height, int width,
                         float threshold, int max_bbox_search, int grid_y, int grid_x, int verbose, uint8_t* d_keep, void* stream);
+
+/* Test hook of the exclusive sum behind the neighbour lists of both NMS and the pair list of sd_nms2d_old_device: d_out[k] = the sum of
+ * d_in[0 .. k) for k < n, int32 counts summed in 64 bits (a sum in the counts' own type would wrap at 2^32 whatever the type of d_out). */
+int sd_exclusive_sum_i32_i64_device(const int32_t* d_in, int n, int64_t* d_out, void* stream);
 
 /* Test probe: Clipper::AddPath (clipper.cpp:1045-1221) once per polygon -- the prepared-polygon records the 2D NMS
  * builds per candidate (stardist_amd/csrc/clip_beam.h, PolyPrep<MAXV>, MAXV = 32/64/128/256 for n_verts). */
@@ -218,7 +227,8 @@ void _LIB_non_maximum_suppression_sparse(const float* scores, const float* dist,
  * 8 stage-3 kernel ns, 9 stage-4 ns, 10 stage-5 ns, 11 hull-volume calls, 12 kept by hull stage,
  * 13 exact-volume decisions (stages 3 / 4) whose ratio lies within 1e-6 of the threshold -- the volumes agree with Qhull's to 1e-9
  * relative, so only such a pair could be decided differently; the count makes that observable --, 14 faces that needed the
- * large-capacity fallback, 15 broad-phase ns} */
+ * large-capacity fallback, 15 broad-phase ns}.  All sixteen entries are taken: the slot total and the form of the neighbour lists, which
+ * sd_nms2d_device reports in stats[12] and [13], have no place here (same list builder, same 64-bit totals). */
 int sd_nms3d_device(const float* d_scores, const float* d_dist, const float* d_points,
                     int n_polys, int n_rays, int n_faces, const float* d_verts,
                     const int* d_faces, float threshold, int use_bbox, int use_kdtree,

@@ -1121,14 +1121,14 @@ struct Nms2d {
     SD_LAUNCH_CHECK();
     size_t scanBytes2 = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, cellCount, cellStart, nCells + 1, s);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes2, nbrCount, nbrStart, N + 1, s);
+    (void)exclusive_sum_i64(nullptr, scanBytes2, nbrCount, nbrStart, N + 1, s);
     if (scanBytes2 > scanBytes) scanBytes = scanBytes2;
     scanTmp = A.take(scanBytes + 256);
     if (!scanTmp) return -1;
     SD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp, scanBytes, cellCount, cellStart, nCells + 1, s));
     // (k_cell_fill writes every slot capacity and the closing zero; the two-pass form clears nbrCount itself)
     hipLaunchKernelGGL(k_cell_fill, dim3(sd::div_up(N, 256)), dim3(256), 0, s, N, candCell, cellStart, cellFill, pts, bbox, area, cellRec, g, by_bbox, reach,
-                       singlePass ? nbrCount : (int*)nullptr);
+                       (singlePass || wantStats) ? nbrCount : (int*)nullptr);      // (the statistics report the slot total of either form)
     SD_LAUNCH_CHECK();
     // The N-sized work lists of the greedy rounds are set up HERE, in front of the neighbour lists: behind the read-back of the list total
     // their four small launches sat on the critical path in front of round 1 (~60 us of 5-us kernels and gaps)
@@ -1145,7 +1145,7 @@ struct Nms2d {
   // ---- neighbour CSR (build_neighbour_lists, nms_rounds.h), the helper stream's work forked from inside it; ends the broad-phase time
   int build_lists() {
     const int nbBlocks = (sd::div_up(N, 4) + 7) & ~7;
-    L.count = nbrCount; L.low = nbrLow; L.start = nbrStart; L.lowOnly = true;
+    L.count = nbrCount; L.low = nbrLow; L.start = nbrStart; L.lowOnly = true; L.wantSlotTotal = wantStats;
     auto launch_neighbours = [&](int mode, const NbrLists& l) {      // (the counting pass gets no lists)
       auto go = [&](auto kern, const i64* start, int* nbr, int* waitOn) {
         hipLaunchKernelGGL(kern, dim3(nbBlocks), dim3(256), 0, s, N, g, f, cellRec, cellStart, nbrCount, nbrLow, start, nbr, waitOn, by_bbox, reach);
@@ -1365,7 +1365,8 @@ struct Nms2d {
     SD_CHECK(hipStreamSynchronize(s));
     if (stats) { stats[0] = totalPairs; stats[1] = totalExact; stats[2] = rounds; stats[3] = totalNbr;
                  stats[4] = (int64_t)ns_pairs; stats[5] = n_pair_launches; stats[6] = (int64_t)ns_full; stats[7] = (int64_t)ns_pre;
-                 stats[8] = totalSpill; stats[9] = totalDecided; stats[10] = totalUndecDeferred; stats[11] = totalSkipped; }
+                 stats[8] = totalSpill; stats[9] = totalDecided; stats[10] = totalUndecDeferred; stats[11] = totalSkipped;
+                 stats[12] = L.slotTotal; stats[13] = L.slots ? 1 : 0; }
     if (verbose) {
       printf("NMS: %lld pair intersections (%lld on the exact-join path), %d greedy rounds, %lld neighbour entries\n",
              (long long)totalPairs, (long long)totalExact, rounds, (long long)totalNbr);
@@ -1520,10 +1521,10 @@ extern "C" int sd_nms2d_old_device(const int32_t* d_polys, int n_polys, int n_ra
   hipLaunchKernelGGL((k_old_pairs<0>), dim3(sd::div_up(N, 4)), dim3(256), 0, s, N, o, d_mapping, bbox, gmax, cnt, (const i64*)nullptr, (int2*)nullptr);
   SD_LAUNCH_CHECK();
   size_t tmpBytes = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmpBytes, cnt, start, N + 1, s);
+  (void)exclusive_sum_i64(nullptr, tmpBytes, cnt, start, N + 1, s);
   void* scanTmp = A.take(tmpBytes + 256);
   if (!scanTmp) return -1;
-  SD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp, tmpBytes, cnt, start, N + 1, s));
+  SD_CHECK(exclusive_sum_i64(scanTmp, tmpBytes, cnt, start, N + 1, s));
   i64 total = 0;
   SD_CHECK(hipMemcpyAsync(&total, start + N, sizeof(i64), hipMemcpyDeviceToHost, s));
   SD_CHECK(hipStreamSynchronize(s));
@@ -1558,6 +1559,21 @@ extern "C" int sd_nms2d_old_device(const int32_t* d_polys, int n_polys, int n_ra
   SD_LAUNCH_CHECK();
   SD_CHECK(hipStreamSynchronize(s));
   if (verbose) { printf("NMS: %lld candidate pairs evaluated\n", (long long)total); fflush(stdout); }
+  return 0;
+}
+
+// Test hook: the 64-bit exclusive sum of the neighbour-list builder and of sd_nms2d_old_device (exclusive_sum_i64, nms_rounds.h) on its own
+extern "C" int sd_exclusive_sum_i32_i64_device(const int32_t* d_in, int n, int64_t* d_out, void* stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  if (n <= 0) return 0;
+  sd::Arena& A = sd::arena();
+  if (A.begin(s)) return -1;
+  size_t tmpBytes = 0;
+  (void)exclusive_sum_i64(nullptr, tmpBytes, (const int*)d_in, (long long*)d_out, n, s);
+  void* tmp = A.take(tmpBytes + 256);
+  if (!tmp) return -1;
+  SD_CHECK(exclusive_sum_i64(tmp, tmpBytes, (const int*)d_in, (long long*)d_out, n, s));
+  SD_CHECK(hipStreamSynchronize(s));
   return 0;
 }
 

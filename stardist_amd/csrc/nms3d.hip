@@ -1177,7 +1177,7 @@ struct Nms3d {
     hipLaunchKernelGGL(k_cell_count3, dim3(sd::div_up(N, 256)), dim3(256), 0, s, pts, N, gr, cellCount, candCell);
     size_t tb2 = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, cellCount, cellStart, nCells + 1, s);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, nbrCount, nbrStart, N + 1, s);
+    (void)exclusive_sum_i64(nullptr, tb2, nbrCount, nbrStart, N + 1, s);
     if (tb2 > scanBytes) scanBytes = tb2;
     scanTmp = A.take(scanBytes + 256);
     if (!scanTmp) return -1;

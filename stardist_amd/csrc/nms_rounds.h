@@ -179,10 +179,22 @@ struct NbrLists {
   long long total, slotTotal;                  // list entries; entries of the slots (single-pass form)
   bool slots;                                  // the single-pass form was used: the lists lie in their slots, with gaps
   bool lowOnly;                                // set by the caller
+  bool wantSlotTotal;                          // set by the caller: count[] holds the capacities and slotTotal is reported even where
+                                               // the two-pass form is asked for (the statistics)
 };
 
+// Exclusive prefix sums of n int counts as 64-bit starts (tmp == nullptr: the query for the temporary bytes).  The sum itself has to run
+// in 64 bits: hipcub's ExclusiveSum takes its accumulator from the INPUT's value type, so over int counts it wraps at 2^32 whatever the
+// type of the outputs -- a slot total of 2^32 + x came back as x, past every range check.  Here the counts are widened on the way in and
+// the initial value, which rocPRIM takes the accumulator type from, is a long long.
+struct WidenCount { __host__ __device__ __forceinline__ long long operator()(const int& v) const { return (long long)v; } };
+inline hipError_t exclusive_sum_i64(void* tmp, size_t& tmpBytes, const int* count, long long* start, int n, hipStream_t s) {
+  hipcub::TransformInputIterator<long long, WidenCount, const int*> in(count, WidenCount());
+  return hipcub::DeviceScan::ExclusiveScan(tmp, tmpBytes, in, start, hipcub::Sum(), (long long)0, n, s);
+}
+
 // Builds the lists behind the caller's cell grid.  On entry count[] holds every candidate's slot capacity, the population of the cells
-// its list is built from (single-pass form; unused otherwise).
+// its list is built from (single-pass form or wantSlotTotal; unused otherwise).  Every total is a true 64-bit sum (exclusive_sum_i64).
 //   single pass: scan the slots, write the lists into them (launch(2): better-scored neighbours from the slot's front, the others --
 //                unless lowOnly -- from its back), sum the exact total on the way;
 //   two passes:  count (launch(0)), scan, fill (launch(1)): every candidate test is done twice -- the form for inputs whose slots would
@@ -195,11 +207,11 @@ template <class LaunchNeighbours, class BeforeLists>
 int build_neighbour_lists(sd::Arena& A, hipStream_t s, int N, bool singlePass, void* scanTmp, size_t scanBytes,
                           LaunchNeighbours launch, BeforeLists beforeLists, NbrLists& L) {
   L.nbr = nullptr; L.waitOn = nullptr; L.total = 0; L.slotTotal = 0; L.slots = false;
-  if (singlePass) {
-    SD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp, scanBytes, L.count, L.start, N + 1, s));
+  if (singlePass || L.wantSlotTotal) {
+    SD_CHECK(exclusive_sum_i64(scanTmp, scanBytes, L.count, L.start, N + 1, s));
     SD_CHECK(hipMemcpyAsync(&L.slotTotal, L.start + N, sizeof(long long), hipMemcpyDeviceToHost, s));
     SD_CHECK(hipStreamSynchronize(s));
-    L.slots = L.slotTotal >= 0 && L.slotTotal < 0x7fffffffll;
+    L.slots = singlePass && L.slotTotal >= 0 && L.slotTotal < 0x7fffffffll;
   }
   if (L.slots) {
     L.nbr = A.take_n<int>((size_t)L.slotTotal);
@@ -210,7 +222,7 @@ int build_neighbour_lists(sd::Arena& A, hipStream_t s, int N, bool singlePass, v
     SD_CHECK(hipMemsetAsync(L.count, 0, (N + 1) * sizeof(int), s));
     launch(0, L);
     SD_LAUNCH_CHECK();
-    SD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTmp, scanBytes, L.count, L.start, N + 1, s));
+    SD_CHECK(exclusive_sum_i64(scanTmp, scanBytes, L.count, L.start, N + 1, s));
     SD_CHECK(hipMemcpyAsync(&L.total, L.start + N, sizeof(long long), hipMemcpyDeviceToHost, s));
     SD_CHECK(hipStreamSynchronize(s));
     if (beforeLists()) return -1;

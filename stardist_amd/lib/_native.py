@@ -35,6 +35,7 @@ SIGNATURES = {
     "sd_nms2d_host": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "sd_nms2d_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "sd_nms2d_build_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sd_exclusive_sum_i32_i64_device": (_i, [_vp, _i, _vp, _vp]),
     "sd_nms2d_old_host": (_i, [_vp, _i, _i, _vp, _i, _i, _f, _i, _i, _i, _i, _vp]),
     "sd_nms2d_old_device": (_i, [_vp, _i, _i, _vp, _i, _i, _f, _i, _i, _i, _i, _vp, _vp]),
     "sd_clip_pairs_device": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

@@ -11,7 +11,9 @@ from . import _native as N
 
 def c_non_max_suppression_inds(dist, points, use_kdtree, use_bbox, verbose, threshold, return_stats=False, _as_uint8=False):
     """stardist2d.cpp:390-615. dist (n,R) f32, points (n,2) f32 sorted by score desc -> bool (n,).
-    _as_uint8 (device tensors, internal): the flags as the native wrote them (uint8 0 / 1) without the cast to bool."""
+    _as_uint8 (device tensors, internal): the flags as the native wrote them (uint8 0 / 1) without the cast to bool.
+    return_stats: also the int64[16] statistics of sd_nms2d_device (include/stardist_hip.h), among them [2] rounds, [3] ordered neighbour
+    relations, [12] slot total of the single-pass neighbour lists (64-bit), [13] their form: 1 = slots, 0 = two passes."""
     N.require_device()
     stats = np.zeros(16, np.int64)
     if N.is_torch(dist):

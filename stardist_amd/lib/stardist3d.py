@@ -13,7 +13,9 @@ from . import _native as N
 
 
 def c_non_max_suppression_inds(dist, points, verts, faces, scores, use_bbox, use_kdtree, verbose, threshold, return_stats=False, _as_uint8=False):
-    """stardist3d.cpp:13-62 -> stardist3d_impl.cpp:956-1385. Inputs sorted by score descending. Returns bool (n,)."""
+    """stardist3d.cpp:13-62 -> stardist3d_impl.cpp:956-1385. Inputs sorted by score descending. Returns bool (n,).
+    return_stats (device tensors): also the int64[16] statistics of sd_nms3d_device (include/stardist_hip.h); all sixteen are taken, the
+    slot total and form of the neighbour lists that the 2D call reports are not among them."""
     N.require_device()
     stats = np.zeros(16, np.int64)
     if N.is_torch(dist):

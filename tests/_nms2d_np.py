@@ -114,6 +114,50 @@ def neighbour_pairs(dist, points, use_kdtree, use_bbox, thr, block=512):
     return total
 
 
+def slot_capacities(dist, points, thr, use_bbox=1):
+    """The slot capacities of the single-pass neighbour lists (csrc/nms2d.hip: build_grid, cell_of, cell_window, k_cell_fill), exactly:
+    reach, cell size and grid origin as the host derives them from the largest distance and the floors of the centres (float32, the cell
+    counts by a float64 quotient), the cell of a centre and the window of a bounding box in float32 -- one subtraction, one product and
+    one truncation resp. floor each --, and per candidate the population of its window's cells minus itself.
+    -> dict(cap (n,) int64, total int: their sum, ny, nx, reach f32, cs f32)"""
+    f = np.float32
+    b = build(dist, points)
+    pts = np.ascontiguousarray(points, np.float32)
+    gs = b["gstats"]
+    max_dist = b["radius"].max()
+    reach = f(f(f(max_dist + f(1)) * f(1.0001)) + f(1e-3))
+    cs = f(f(0.5) * reach)
+    if not cs >= f(1):
+        cs = f(1)
+    while True:
+        ny = int((float(gs[2]) - float(gs[1])) / float(cs)) + 1
+        nx = int((float(gs[4]) - float(gs[3])) / float(cs)) + 1
+        if ny * nx <= (1 << 26):
+            break
+        cs = f(cs * f(2))
+    y0, x0, inv_cs = f(gs[1]), f(gs[3]), f(f(1) / cs)
+
+    def cell(v, v0, hi):                                  # cell_of: (int) truncates toward zero
+        return np.clip(np.trunc(((v - v0).astype(f) * inv_cs).astype(f)).astype(np.int64), 0, hi - 1)
+
+    def edge(v, v0, hi):                                  # cell_window: floorf((v -+ 0.5f - v0) * inv_cs), clamped
+        return np.clip(np.floor(((v - v0).astype(f) * inv_cs).astype(f)).astype(np.int64), 0, hi - 1)
+    cy, cx = cell(pts[:, 0], y0, ny), cell(pts[:, 1], x0, nx)
+    if thr >= 0 or use_bbox:
+        bb = b["bbox"].astype(f)
+        lo_x, hi_x, lo_y, hi_y = (bb[:, 0] - reach).astype(f), (bb[:, 1] + reach).astype(f), (bb[:, 2] - reach).astype(f), (bb[:, 3] + reach).astype(f)
+    else:
+        rr = f(f(2) * reach)
+        lo_x, hi_x, lo_y, hi_y = (pts[:, 1] - rr).astype(f), (pts[:, 1] + rr).astype(f), (pts[:, 0] - rr).astype(f), (pts[:, 0] + rr).astype(f)
+    ylo, yhi = edge((lo_y - f(0.5)).astype(f), y0, ny), edge((hi_y + f(0.5)).astype(f), y0, ny)
+    xlo, xhi = edge((lo_x - f(0.5)).astype(f), x0, nx), edge((hi_x + f(0.5)).astype(f), x0, nx)
+    pop = np.zeros((ny + 1, nx + 1), np.int64)             # pop[a, b] = candidates in the cells [0, a) x [0, b)
+    np.add.at(pop, (cy + 1, cx + 1), 1)
+    pop = pop.cumsum(0).cumsum(1)
+    cap = pop[yhi + 1, xhi + 1] - pop[ylo, xhi + 1] - pop[yhi + 1, xlo] + pop[ylo, xlo] - 1
+    return dict(cap=cap, total=int(cap.sum()), ny=ny, nx=nx, reach=reach, cs=cs)
+
+
 # ---- the triples scene: pairs whose j is suppressed by a decided pair of the same round
 TRIPLES = 200
 TRIPLES_THR = np.float32(0.4)

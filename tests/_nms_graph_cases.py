@@ -20,6 +20,9 @@ in them are checked pair by pair against the compiled reference in the CPU test)
       diagonals 10.6 (0.15).
   hub: small discs (radius 3, pitch 7.3) / balls (radius 2, face-centred cubic, nearest neighbours 4.15 apart) are pairwise disjoint; the
       inner ones lie inside the hub polygon / polyhedron (overlap / smaller = 1), the outer ones outside its bounding box.
+
+The hubs of SLOT_LIMIT_2D (hub radius 1000 and 1300, 49 061 to 72 601 candidates) are sized by the slot total of the neighbour lists, not by
+the scheduler: tests/test_gpu_nms_slot_limits.py.
 """
 import numpy as np
 
@@ -82,13 +85,17 @@ def _assemble(name, dim, pos, radius, rank, edges_c, n_rays, seed, amp=0.25, cop
     pts = pts - pts.min(0) + np.array([30.37, 31.61, 32.83][:dim]) + (np.asarray(radius).max() if n else 0)
     rank = np.asarray(rank, np.int64)
     order = np.argsort(rank)
-    edges = rank[np.asarray(edges_c, np.int64).reshape(-1, 2)]
-    edges = np.sort(edges, 1)
+    if edges_c is None:                                  # a clique too large to list: candidate 0 suppresses every other one
+        edges, keep = None, np.arange(n) == 0
+    else:
+        edges = rank[np.asarray(edges_c, np.int64).reshape(-1, 2)]
+        edges = np.sort(edges, 1)
+        keep = greedy(n, edges)
     labelings = [np.asarray(l)[order] for l in kw.pop("labelings", [])]
     big = kw.pop("big", None)
     return Scene(name=name, dim=dim, n_rays=n_rays, thr=np.float32(THR[dim]),
                  dist=np.ascontiguousarray(dist[order], np.float32), points=np.ascontiguousarray(pts[order], np.float32),
-                 scores=np.linspace(0.99, 0.5, n).astype(np.float32), edges=edges, keep=greedy(n, edges),
+                 scores=np.linspace(0.99, 0.5, n).astype(np.float32), edges=edges, keep=keep,
                  labelings=labelings, big=None if big is None else int(rank[big]), **kw)
 
 
@@ -147,10 +154,11 @@ def _inradius(dim, n_rays):
     return float(np.abs((nrm * a).sum(1) / np.linalg.norm(nrm, axis=1)).min())
 
 
-def hub(dim, m, hub_first, n_rays=None, seed=3):
-    """one large disc / ball, m small ones inside it, m // 10 outside its bounding box; the small ones pairwise disjoint"""
+def hub(dim, m, hub_first, n_rays=None, seed=3, hub_radius=None):
+    """one large disc / ball (radius HUB_RADIUS unless given), m small ones inside it, m // 10 outside its bounding box; the small ones
+    pairwise disjoint"""
     n_rays = n_rays or (32 if dim == 2 else 96)
-    R, r = HUB_RADIUS[dim], SMALL_RADIUS[dim]
+    R, r = float(hub_radius or HUB_RADIUS[dim]), SMALL_RADIUS[dim]
     rs, amp = r * (1 + RAY_NOISE), 0.1 if dim == 2 else 0.015
     room = R * (1 - RAY_NOISE) * _inradius(dim, n_rays) - rs - (1.5 if dim == 2 else 0.1) - 2 * amp      # (2D: vertices are truncated to integers)
     if dim == 2:
@@ -178,13 +186,15 @@ def hub(dim, m, hub_first, n_rays=None, seed=3):
     rank = np.concatenate([[0], 1 + small_rank]) if hub_first else np.concatenate([[n - 1], small_rank])
     lab_small = np.concatenate([[-1], np.arange(n - 1)])
     lab_hub = np.concatenate([[0], np.full(m, -1), 1 + np.arange(m // 10) * (dim == 2)])      # (3D: the hub against the outer ones only)
-    return _assemble("hub%dd-%d-%s" % (dim, m, "first" if hub_first else "last"), dim, pos, np.concatenate([[R], np.full(n - 1, r)]), rank,
+    return _assemble("hub%dd-%d-%s%s" % (dim, m, "first" if hub_first else "last", "-R%g" % R if hub_radius else ""), dim, pos, np.concatenate([[R], np.full(n - 1, r)]), rank,
                      [(0, 1 + k) for k in range(m)], n_rays, seed, amp=amp, edge_dist=None, non_edge_min=sep, big=0,
                      labelings=[lab_small, lab_hub] if dim == 2 else [lab_hub], m=m)
 
 
-def clique(dim, k, duplicates=0, n_rays=None, seed=4):
-    """k near-coincident candidates (centres within one pixel); `duplicates` of them are exact copies of one candidate"""
+def clique(dim, k, duplicates=0, n_rays=None, seed=4, list_edges=True):
+    """k near-coincident candidates (centres within one pixel); `duplicates` of them are exact copies of one candidate.  list_edges=False
+    (the cliques of the capacity tests, whose k (k - 1) / 2 edges no list holds): edges is None, keep is the greedy result all the same --
+    the best-scored candidate alone"""
     n_rays = n_rays or (32 if dim == 2 else 96)
     rng = np.random.RandomState(seed)
     pos = rng.uniform(0, 0.75, (k, dim))
@@ -193,7 +203,8 @@ def clique(dim, k, duplicates=0, n_rays=None, seed=4):
         sel = rng.choice(np.arange(1, k), duplicates, replace=False)
         copies = [(int(sel[0]), int(b)) for b in sel[1:]]
     return _assemble("clique%dd-%d%s" % (dim, k, "-dup%d" % duplicates if duplicates else ""), dim, pos, np.full(k, RADIUS[dim]), _ranks(k, "random", seed),
-                     [(a, b) for a in range(k) for b in range(a + 1, k)], n_rays, seed, copies=copies, edge_dist=(0.0, 1.0 * np.sqrt(dim)), non_edge_min=None)
+                     [(a, b) for a in range(k) for b in range(a + 1, k)] if list_edges else None, n_rays, seed, copies=copies,
+                     edge_dist=(0.0, 1.0 * np.sqrt(dim)), non_edge_min=None)
 
 
 def forest(dim, n, n_rays=None, seed=5):
@@ -254,8 +265,25 @@ HUBS_3D = [_register(3, hub, 600, True), _register(3, hub, 600, False)]
 OTHERS_3D = [_register(3, ladder, 400), _register(3, clique, 120), _register(3, clique, 120, duplicates=20), _register(3, forest, 1500)]
 SCENES_3D = CHAINS_3D + HUBS_3D + OTHERS_3D
 
-# the compiled reference (one Qhull thread) takes the 3D scenes up to this many candidates in the CPU test; every 2D scene
+# ---- the slot-limit scenes of tests/test_gpu_nms_slot_limits.py: hubs so large that the slot total of the single-pass neighbour lists
+# (tests/_nms2d_np.py: slot_capacities, the exact mirror; about n^2, every window covers nearly every cell) reaches the 32-bit limits of
+# csrc/nms_rounds.h.  NOT in SCENES_2D: the option sweep over that list would allocate gigabytes per case.  SLOT_TOTALS: the mirrored
+# totals, asserted by tests/test_cpu_nms_graph_cases.py.
+#   below2d  hub radius 1000, the largest m in steps of 100 whose total stays 5 10^6 below 2^31 - 1: the slots, 8.6 GB of them
+#   band2d   hub radius 1000, total in [2^31 + 5 10^6, 2^32 - 10^9]: the two-pass lists by size alone; hub first and hub last
+#   wrap2d   hub radius 1300, total T with 10^8 <= T - 2^32 <= 2^31 - 10^8: a 32-bit sum would return T - 2^32, a plausible total
+BELOW_2D = _register(2, hub, 44600, True, hub_radius=1000.0)
+BAND_2D = [_register(2, hub, 52000, True, hub_radius=1000.0), _register(2, hub, 52000, False, hub_radius=1000.0)]
+WRAP_2D = _register(2, hub, 66000, True, hub_radius=1300.0)
+SLOT_LIMIT_2D = [BELOW_2D] + BAND_2D + [WRAP_2D]
+SLOT_TOTALS = {BELOW_2D: 2138780136, BAND_2D[0]: 2744655308, BAND_2D[1]: 2744655308, WRAP_2D: 4796631484}
+SLOT_LIMIT = 2 ** 31 - 1                                 # the slots are used below this total
+
+# the compiled reference (one Qhull thread) takes the 3D scenes up to this many candidates in the CPU test; every 2D scene of SCENES_2D.
+# REF_MAX_2D: the largest slot-limit scene it takes, the largest whose call stays within about 5 s on 8 threads; the larger ones are
+# checked against the constructed flags only
 REF_MAX_3D = 700
+REF_MAX_2D = 35000
 
 _BUILT = {}
 

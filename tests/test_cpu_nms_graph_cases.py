@@ -1,6 +1,7 @@
 """Proof of the scenes of tests/_nms_graph_cases.py (no GPU): the compiled reference returns the constructed keep flags, it suppresses across
 sampled designed edges and not across sampled designed non-edges when given the two candidates alone, and the generators keep their own
-invariants -- so whatever tests/test_gpu_nms_graph.py finds different on these scenes is the scheduler's."""
+invariants -- so whatever tests/test_gpu_nms_graph.py finds different on these scenes is the scheduler's.  At the end the large hubs of
+tests/test_gpu_nms_slot_limits.py: their slot totals by the numpy mirror, their invariants, the reference at a reduced size."""
 import os
 import sys
 
@@ -121,3 +122,103 @@ def test_sampled_pairs_alone(refmods, key):
     near = near[~np.isin(near[:, 0] * n + near[:, 1], sc.edges[:, 0] * n + sc.edges[:, 1])]
     for i, j in _sample(rng, near, k):
         assert np.asarray(_ref_keep(refmods, sc, [i, j])).tolist() == [True, True], (key, "non-edge", i, j)
+
+
+# ---- the slot-limit scenes (tests/test_gpu_nms_slot_limits.py): tens of thousands of candidates, so the pair searches go through a k-d tree
+def _mirror_total(key):
+    import _nms2d_np as M
+    sc = C.scene(key)
+    return M.slot_capacities(sc.dist, sc.points, sc.thr)["total"]
+
+
+def test_slot_capacity_mirror_on_the_small_hub():
+    """the figure the scene list was sized from: hub radius 200, m = 2000"""
+    assert _mirror_total(C.HUBS_2D[0]) == 4194674
+
+
+@pytest.mark.parametrize("key", C.SLOT_LIMIT_2D)
+def test_slot_limit_scene_lies_on_its_side_of_the_limit(key):
+    """the mirrored slot total (float32 cell arithmetic of cell_of / cell_window, reach, cell size and origin of build_grid) is the recorded
+    one and keeps the margins to 2^31 - 1, 2^31, 2^32 that the scene was sized for"""
+    t = _mirror_total(key)
+    assert t == C.SLOT_TOTALS[key], (key, t)
+    if key == C.BELOW_2D:
+        assert t <= C.SLOT_LIMIT - 5 * 10 ** 6
+        f, a, kw = C._FACTORIES[key]                     # the largest m in steps of 100 that keeps the margin
+        nxt = C.hub(2, a[1] + 100, True, hub_radius=kw["hub_radius"])
+        import _nms2d_np as M
+        assert M.slot_capacities(nxt.dist, nxt.points, nxt.thr)["total"] > C.SLOT_LIMIT - 5 * 10 ** 6
+    elif key in C.BAND_2D:
+        assert 2 ** 31 + 5 * 10 ** 6 <= t <= 2 ** 32 - 10 ** 9
+    else:
+        assert key == C.WRAP_2D and 10 ** 8 <= t - 2 ** 32 <= 2 ** 31 - 10 ** 8
+
+
+@pytest.mark.parametrize("key", C.SLOT_LIMIT_2D)
+def test_slot_limit_scene_invariants(key):
+    """test_generator_invariants for the large hubs: the small candidates keep their distance (non_edge_min) and the claimed bounding boxes
+    are disjoint (labelings) -- pairs found by scipy's cKDTree"""
+    from scipy.spatial import cKDTree
+    sc = C.scene(key)
+    n = sc.n
+    assert sc.dist.shape == (n, sc.n_rays) and sc.points.shape == (n, 2) and sc.keep.shape == (n,)
+    assert sc.dist.dtype == np.float32 and sc.points.dtype == np.float32
+    assert np.all(np.diff(sc.scores) < 0)
+    assert (sc.points - sc.dist.max(1, keepdims=True) > 1).all(), "every vertex has positive coordinates"
+    assert np.any(sc.points != np.round(sc.points), 1).all()
+    e = sc.edges
+    assert len(e) == sc.m and (e[:, 0] < e[:, 1]).all() and (e == sc.big).any(1).all(), "every edge joins the hub and a small candidate"
+    assert np.array_equal(sc.keep, C.greedy(n, e)) and sc.keep[0]
+    assert int(sc.keep.sum()) == (n - sc.m if sc.big == 0 else n - 1)
+    p = sc.points.astype(np.float64)
+    small = np.flatnonzero(np.arange(n) != sc.big)
+    assert len(cKDTree(p[small]).query_pairs(sc.non_edge_min)) == 0, "small candidates closer than %g" % sc.non_edge_min
+    lo, hi = _boxes(sc)
+    lab_small, lab_hub = sc.labelings
+    assert lab_small[sc.big] == -1 and len(np.unique(lab_small[small])) == n - 1        # every pair of small candidates is claimed
+    reach = float((hi - lo)[small].max()) + 1.0                                            # boxes further apart than this (Chebyshev) cannot meet
+    near = small[cKDTree(p[small]).query_pairs(reach, p=np.inf, output_type="ndarray")]
+    apart = ((hi[near[:, 0]] < lo[near[:, 1]]) | (hi[near[:, 1]] < lo[near[:, 0]])).any(1)
+    assert len(near) > n and apart.all(), near[~apart][:5]
+    outer = np.flatnonzero(lab_hub > 0)
+    assert lab_hub[sc.big] == 0 and len(outer) == sc.m // 10
+    assert ((hi[outer] < lo[sc.big]) | (hi[sc.big] < lo[outer])).any(1).all(), "an outer candidate's box meets the hub's"
+
+
+@pytest.mark.parametrize("hub_radius,m,hub_first", [(1000.0, 20000, True), (1000.0, 5000, False), (1300.0, 20000, True)])
+def test_reference_on_the_large_hubs_at_reduced_m(refmods, hub_radius, m, hub_first):
+    """The reference's time grows with n^2 (every candidate's radius search covers the scene): 9.4, 11.2, 254 and 19.7 s on 8 threads for
+    the four full scenes, where it returned the constructed flags when the scenes were sized.  Beyond C.REF_MAX_2D candidates it is not run in
+    the suite; here the same hubs with fewer small candidates (the first m of the same lattice: the scene's innermost part)."""
+    sc = C.hub(2, m, hub_first, hub_radius=hub_radius)
+    assert sc.n <= C.REF_MAX_2D
+    refmods.set_threads(8)
+    ref = np.asarray(_ref_keep(refmods, sc), bool)
+    diff = np.flatnonzero(ref != sc.keep)
+    assert len(diff) == 0, (diff[:10], int(ref.sum()), int(sc.keep.sum()))
+
+
+@pytest.mark.parametrize("key", C.SLOT_LIMIT_2D)
+def test_slot_limit_scene_margins_at_the_rim(refmods, key):
+    """the pairs of the full scenes that could be mistaken, given to the reference alone: the hub with the inner small candidates furthest
+    from its centre (suppressed, or suppressing it) and with the outer ones nearest to it (both kept)"""
+    sc = C.scene(key)
+    p = sc.points.astype(np.float64)
+    d = np.linalg.norm(p - p[sc.big], axis=1)
+    inner = np.setdiff1d(np.unique(sc.edges), [sc.big])
+    outer = np.flatnonzero(sc.labelings[1] > 0)
+    for j in inner[np.argsort(d[inner])[-12:]]:
+        pair = sorted([sc.big, int(j)])
+        assert np.asarray(_ref_keep(refmods, sc, pair)).tolist() == [True, False], (key, "edge", pair)
+    for j in outer[np.argsort(d[outer])[:12]]:
+        pair = sorted([sc.big, int(j)])
+        assert np.asarray(_ref_keep(refmods, sc, pair)).tolist() == [True, True], (key, "non-edge", pair)
+
+
+def test_clique_without_an_edge_list():
+    """the cliques of the capacity tests: same candidates and flags as the listed form"""
+    a, b = C.clique(2, 300), C.clique(2, 300, list_edges=False)
+    assert b.edges is None and np.array_equal(a.dist, b.dist) and np.array_equal(a.points, b.points) and np.array_equal(a.keep, b.keep)
+    big = C.clique(2, 93000, list_edges=False)
+    assert big.n == 93000 and int(big.keep.sum()) == 1 and big.keep[0]
+    assert np.ptp(big.points, 0).max() < 1.0 and big.n * (big.n - 1) // 2 >= 2 ** 32

@@ -695,6 +695,28 @@ int sd_label_centroid_sums_device(const int32_t* d_lbl, int Z, int Y, int X, int
 int sd_label_intensity_stats_device(const int32_t* d_lbl, int Z, int Y, int X, int max_label, const int32_t* d_boxes, const void* d_img,
                                     int dtype, int C, int64_t* d_isum2, double* d_fsum2, void* d_minmax, void* stream);
 
+/* ---- exact intensity percentiles of labelled objects (csrc/measure_rank.hip, csrc/measure_rank.h): the columns of
+ * stardist_amd.utils.measure_labels(percentiles=) -----------------------------------------------------------------------------------
+ * lbl, d_boxes, d_img, dtype and C as for sd_label_intensity_stats_device (every box is clamped to the image, and the kernels count an
+ * object's pixels themselves while they read its box: no table can make them read or write outside their buffers).  h_q: n_q
+ * percentiles in [0, 100] on the host, 1 <= n_q <= 8.  d_out is [max_label + 1][C][n_q] float64 and the call writes every entry:
+ *   d_out[l][c][j] = np.percentile(v, h_q[j]) (method 'linear') of the values v of label l in channel c, bit for bit: exact order
+ *   statistics, then numpy's interpolation between the two neighbouring ones.  Integer images interpolate in float64.  float32 images:
+ *   interp_f32 = 1: virtual index, weight and interpolation in float32 -- what numpy >= 2.0 does for float32 data and a Python-scalar q;
+ *   0: in float64, rounded to float32 at the end; either way the entry is the float32 result widened to double.
+ *   Row 0 and the rows of absent labels hold NaN.  A NaN among an object's values of a channel makes that object's entries of that
+ *   channel NaN, and only those; +-inf follow numpy's interpolation (inf - inf = NaN).
+ * Per object: a box of at most 1024 pixels has its keys compacted into LDS and sorted there by one wave; a larger box of at most 65536
+ * pixels gets one radix-selection pass per 8-bit digit by one workgroup; the chunks of a larger box are spread over the grid, their
+ * counts merged by 64-bit integer atomics in a workspace of 128 (object, channel) slots, beyond which an object falls back to the single
+ * workgroup.  Counting is in integers only, without floating-point atomics: the result depends on (extents, lbl, img, q) alone, the
+ * same bits from call to call and on any grid.  64-bit offsets.  Bad arguments set the error string and return -1 before anything is
+ * launched: a null pointer, a non-positive extent, a negative max_label, a dtype outside 0 .. 2, C outside 1 .. 64, n_q outside 1 .. 8,
+ * a q outside [0, 100] or not finite, more than 2^40 pixels or Z * Y beyond int.  The inputs are not written, nothing is copied to the
+ * host and the stream is not synchronised (the workspace grows on a first call of a larger size). */
+int sd_label_percentiles_device(const int32_t* d_lbl, int Z, int Y, int X, int max_label, const int32_t* d_boxes, const void* d_img,
+                                int dtype, int C, const double* h_q, int n_q, int interp_f32, double* d_out, void* stream);
+
 /* ---- shape tables of labelled objects (csrc/measure_shape.hip, csrc/measure_shape.h): the integer sums behind the shape columns of
  * stardist_amd.utils.measure_labels(shape=True) -- inertia tensor, axis lengths, eccentricity, orientation, perimeter, Crofton perimeter,
  * Euler number ----------------------------------------------------------------------------------------------------------------------

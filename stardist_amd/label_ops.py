@@ -117,6 +117,9 @@ def calculate_extents(lbl, func=np.median):
 # [n_1, n_r2, n_h, h_1 .. h_15], the contour-pixel classes and the 2 x 2 configuration histogram (csrc/measure_shape.h), all int64;
 # _shape_columns derives the shape columns from them.
 _MEASURE_RAW = ("label", "area", "bbox", "csum", "sum", "sum2", "min", "max", "m2", "contour")
+# With percentiles both routes add pct (n, C, n_q): float64 for integer images, else the image's float type.  It is no part of the packed
+# table: it travels as an array of its own.  _MAX_PERCENTILES is csrc/measure_rank.h's MR_MAX_Q.
+_MAX_PERCENTILES = 8
 _M2_INDEX = {(0, 0): 0, (0, 1): 1, (0, 2): 2, (1, 1): 3, (1, 2): 4, (2, 2): 5}
 _CONTOUR_WIDTH = 18
 # the counter a border pixel with a / d border neighbours along the axes / the diagonals counts into (-1: none): n_1, n_r2, n_h
@@ -188,9 +191,10 @@ def _tensor_sqrt(a):
     return torch.sqrt(a) if a.is_cuda else torch.from_numpy(np.sqrt(a.contiguous().numpy()))
 
 
-def _measure_columns(raw, nd, channel_axis):
+def _measure_columns(raw, nd, channel_axis, qs=None):
     """the table of measure_labels from the raw columns (numpy arrays or tensors): centroid = float64(coordinate sum) / count, mean =
-    float64(sum) / count, var = max(0, float64(sum2) / count - mean^2), std = sqrt(var), every operation rounded on its own"""
+    float64(sum) / count, var = max(0, float64(sum2) / count - mean^2), std = sqrt(var), every operation rounded on its own; qs: the
+    percentiles of raw["pct"] (n, C, len(qs)), whose columns come after the intensity columns"""
     if R.is_torch(raw["label"]):
         import torch
         f64, sqrt, col = (lambda a: a.to(torch.float64)), _tensor_sqrt, (lambda a: a.contiguous())
@@ -213,6 +217,13 @@ def _measure_columns(raw, nd, channel_axis):
         for name, a in named:
             for c in range(a.shape[1]):
                 out[("%s-%d" % (name, c)) if channel_axis else name] = col(a[:, c])
+    if qs:
+        for j, q in enumerate(qs):
+            name = "p%g_intensity" % q
+            if ("%s-0" % name if channel_axis else name) in out:            # a duplicate q: the column is there already
+                continue
+            for c in range(raw["pct"].shape[1]):
+                out[("%s-%d" % (name, c)) if channel_axis else name] = col(raw["pct"][:, c, j])
     if "m2" in raw:
         _shape_columns(out, raw, nd)
     return out
@@ -345,9 +356,27 @@ def _shape_raw_host(lab, rows, starts):
     return m2, contour
 
 
-def _measure_raw_host(lbl, img, shape=False):
+def _percentile_list(percentiles, has_img):
+    """the percentiles of measure_labels as a tuple of Python floats (None for None); raises its ValueErrors"""
+    if percentiles is None:
+        return None
+    try:
+        qs = tuple(float(q) for q in percentiles)
+    except TypeError:
+        raise ValueError("measure_labels: percentiles must be None or a sequence of real numbers, got %r" % (percentiles,))
+    if not 1 <= len(qs) <= _MAX_PERCENTILES:
+        raise ValueError("measure_labels: percentiles takes 1 to %d values, got %d" % (_MAX_PERCENTILES, len(qs)))
+    if not all(np.isfinite(q) and 0.0 <= q <= 100.0 for q in qs):
+        raise ValueError("measure_labels: percentiles must be finite and in the range [0, 100], got %r" % (qs,))
+    if not has_img:
+        raise ValueError("measure_labels: percentiles needs the image `img`")
+    return qs
+
+
+def _measure_raw_host(lbl, img, shape=False, percentiles=None):
     """the raw columns by numpy over scipy.ndimage.find_objects boxes; img: None or an array of lbl.shape (+ (C,)); shape: with m2 and,
-    for a 2D image, contour (_shape_raw_host)"""
+    for a 2D image, contour (_shape_raw_host); percentiles: a tuple of Python floats, with pct (n, C, len(percentiles)) =
+    np.percentile(values of the object in the channel, q), one q at a time"""
     if lbl.dtype.kind == "b":
         lbl = lbl.astype(np.uint8)
     if lbl.dtype.kind not in "iu":
@@ -375,6 +404,13 @@ def _measure_raw_host(lbl, img, shape=False):
         raw["sum2"] = np.zeros((n, C), np.int64 if exact else np.float64)
         raw["min"] = np.zeros((n, C), np.int64 if exact else img.dtype)
         raw["max"] = np.zeros((n, C), np.int64 if exact else img.dtype)
+        if percentiles:
+            if img.dtype.kind == "b":
+                img = img.astype(np.uint8)
+            # integer images: float64; float32: float32 (an older numpy interpolates in float64, rounded here); else numpy's type
+            pct_dtype = (np.float64 if exact else np.float32 if img.dtype == np.float32
+                         else np.asarray(np.percentile(np.zeros(1, img.dtype), 50.0)).dtype)
+            raw["pct"] = np.zeros((n, C, len(percentiles)), pct_dtype)
     with np.errstate(all="ignore"):
         for k, (l, box) in enumerate(boxes):
             mask = lab[box] == l
@@ -390,6 +426,10 @@ def _measure_raw_host(lbl, img, shape=False):
                 raw["sum2"][k] = (wide * wide).sum(axis=0)
                 raw["min"][k] = v.min(axis=0)
                 raw["max"][k] = v.max(axis=0)
+                if percentiles:
+                    for c in range(C):
+                        for j, q in enumerate(percentiles):
+                            raw["pct"][k, c, j] = np.percentile(v[:, c], q)
     if shape:
         m2, contour = _shape_raw_host(lab, np.array([k for k, _ in boxes], np.int64), raw["bbox"][:, :nd])
         raw["m2"] = m2
@@ -398,10 +438,10 @@ def _measure_raw_host(lbl, img, shape=False):
     return raw
 
 
-def _measure_raw_device(lbl, img, C, device, shape=False):
+def _measure_raw_device(lbl, img, C, device, shape=False, percentiles=None):
     """the raw columns as tensors on the device: sd_label_boxes_device, sd_label_centroid_sums_device, with an image
-    sd_label_intensity_stats_device and with shape sd_label_moment_sums_device and (2D) sd_label_contour_counts_device, then the rows of
-    the labels present (one scalar, their number, comes to the host)"""
+    sd_label_intensity_stats_device, with percentiles sd_label_percentiles_device and with shape sd_label_moment_sums_device and (2D)
+    sd_label_contour_counts_device, then the rows of the labels present (one scalar, their number, comes to the host)"""
     import torch
     N.require_device()
     lab, top, ids = R._device_labels(lbl, device)
@@ -411,6 +451,7 @@ def _measure_raw_device(lbl, img, C, device, shape=False):
         img = R.to_device_tensor(img, dev)                                  # an image that is elsewhere is moved to the labels' device
         code = _DEVICE_DTYPE_CODE[str(img.dtype)]
     sum_t, mm_t = (torch.float64, torch.float32) if code == 2 else (torch.int64, torch.int32)
+    pct_t = torch.float32 if code == 2 else torch.float64
     if lab.numel() == 0 or top <= 0:
         raw = {"label": torch.zeros(0, dtype=torch.int64, device=dev), "area": torch.zeros(0, dtype=torch.int64, device=dev),
                "bbox": torch.zeros((0, 2 * nd), dtype=torch.int64, device=dev), "csum": torch.zeros((0, nd), dtype=torch.int64, device=dev)}
@@ -418,6 +459,8 @@ def _measure_raw_device(lbl, img, C, device, shape=False):
             raw.update(sum=torch.zeros((0, C), dtype=sum_t, device=dev), sum2=torch.zeros((0, C), dtype=sum_t, device=dev),
                        min=torch.zeros((0, C), dtype=torch.float32 if code == 2 else torch.int64, device=dev),
                        max=torch.zeros((0, C), dtype=torch.float32 if code == 2 else torch.int64, device=dev))
+        if percentiles:
+            raw["pct"] = torch.zeros((0, C, len(percentiles)), dtype=pct_t, device=dev)
         if shape:
             raw["m2"] = torch.zeros((0, 6), dtype=torch.int64, device=dev)
             if nd == 2:
@@ -429,6 +472,13 @@ def _measure_raw_device(lbl, img, C, device, shape=False):
         mm = torch.empty((top + 1, C, 2), dtype=mm_t, device=dev)
         N.dcall(lab, "sd_label_intensity_stats_device", R.ptr(lab), *R.zyx(lab.shape), top, R.ptr(boxes), R.ptr(img), code, C,
                 R.ptr(acc) if code != 2 else None, R.ptr(acc) if code == 2 else None, R.ptr(mm))
+        if percentiles:
+            import ctypes
+            from .utils import _interp_mode
+            pct = torch.empty((top + 1, C, len(percentiles)), dtype=torch.float64, device=dev)
+            q = (ctypes.c_double * len(percentiles))(*percentiles)
+            N.dcall(lab, "sd_label_percentiles_device", R.ptr(lab), *R.zyx(lab.shape), top, R.ptr(boxes), R.ptr(img), code, C,
+                    ctypes.cast(q, ctypes.c_void_p), len(percentiles), _interp_mode(img, percentiles[0]), R.ptr(pct))
     present = torch.nonzero(sums[:, 0]).reshape(-1)
     s = sums.index_select(0, present)
     b = boxes.index_select(0, present).to(torch.int64)
@@ -437,6 +487,8 @@ def _measure_raw_device(lbl, img, C, device, shape=False):
         a, m = acc.index_select(0, present), mm.index_select(0, present)
         raw.update(sum=a[:, :, 0], sum2=a[:, :, 1], min=m[:, :, 0] if code == 2 else m[:, :, 0].to(torch.int64),
                    max=m[:, :, 1] if code == 2 else m[:, :, 1].to(torch.int64))
+        if percentiles:
+            raw["pct"] = pct.index_select(0, present).to(pct_t)             # a float32 result came widened to double: narrowed back
     if shape:
         m2 = torch.empty((top + 1, 6), dtype=torch.int64, device=dev)
         N.dcall(lab, "sd_label_moment_sums_device", R.ptr(lab), *R.zyx(lab.shape), top, R.ptr(boxes), R.ptr(m2))
@@ -448,7 +500,7 @@ def _measure_raw_device(lbl, img, C, device, shape=False):
     return raw
 
 
-def measure_labels(lbl, img=None, *, shape=False, device=None, as_tensors=False):
+def measure_labels(lbl, img=None, *, shape=False, percentiles=None, device=None, as_tensors=False):
     """Per-object table of a 2D / 3D integer label image (values <= 0 are background) and, optionally, of the image `img` that was
     segmented: shape lbl.shape or lbl.shape + (C,) (channels last).  Returns a dict of 1-D columns, one row per label present,
     ascending by label, named as scikit-image 0.18's regionprops_table names them:
@@ -462,6 +514,8 @@ def measure_labels(lbl, img=None, *, shape=False, device=None, as_tensors=False)
         mean_intensity         float64  float64(sum) / count
         min_intensity, max_intensity    int64 / the image's float type
         std_intensity          float64  population standard deviation: sqrt(max(0, float64(sum of squares) / count - mean^2))
+      with percentiles=(q, ...), after the intensity columns, in the order given (a q given twice gives one column):
+        p<q>_intensity         float64 (integer images) / the image's float type; <q> as "%g" writes it: p50_intensity, p99.8_intensity
       with shape=True, after the columns above (pixel units; float64 but for euler_number, int64):
         equivalent_diameter    sqrt(4 area / pi); 3D: (6 area / pi) ** (1 / 3)
         extent                 area / volume of the bounding box
@@ -486,6 +540,15 @@ def measure_labels(lbl, img=None, *, shape=False, device=None, as_tensors=False)
     its own.  A NaN pixel makes sum, mean, min, max and std of its object and channel NaN, as numpy does; +-inf follow IEEE.  Without
     objects every column is an empty array of its dtype.
 
+    Percentiles: `percentiles` is None or 1 to 8 finite real numbers in [0, 100] (Python or numpy scalars; each is taken as float(q))
+    and needs `img`; anything else raises ValueError before anything runs.  With v the object's values in a channel, the column holds
+    np.percentile(v, float(q)) (method 'linear'), q one at a time -- the host route calls exactly that, the device route
+    (csrc/measure_rank.hip) finds the two order statistics exactly and interpolates as numpy does, so the two agree
+    bit for bit: float64 for integer images; for float32 images float32, interpolated in float32 under numpy >= 2.0 and in float64
+    rounded at the end under an older numpy.  A NaN among an object's values of a channel makes its percentiles of that channel NaN,
+    and only those; +-inf follow numpy's interpolation ([1, inf] at q = 0 is NaN); the sign of a zero result is not pinned (numpy does
+    not order -0.0 against +0.0).  Other float types take the host route and numpy's result type.
+
     Routing: DESIGN.md section 3p, by the label image; an image that is elsewhere is moved to the labels' device.  The device route
     takes integer labels and uint8 / uint16 / float32 images (csrc/measure.hip and the box and centroid-sum kernels; the inputs are not
     written): its float64 sums are added in a fixed order without floating-point atomics, so they depend on (shape, lbl, img) alone --
@@ -504,34 +567,39 @@ def measure_labels(lbl, img=None, *, shape=False, device=None, as_tensors=False)
     shape = bool(shape)
     if shape and lbl.shape and int(np.prod([int(n) for n in lbl.shape], dtype=object)) * max(int(n) for n in lbl.shape) ** 2 >= 2 ** 63:
         raise ValueError("measure_labels: shape=True needs (number of pixels) x (largest extent)^2 below 2^63, got shape %s" % (tuple(lbl.shape),))
-    more = {"shape": True} if shape else {}                                 # without shape the two halves are called as before
+    qs = _percentile_list(percentiles, img is not None)
+    more = {"shape": True} if shape else {}                                 # without shape / percentiles the two halves are called as before
+    if qs:
+        more["percentiles"] = qs
     lbl_ok = (str(lbl.dtype) in _DEVICE_LABEL_DTYPES) if lbl_t else (lbl.dtype.kind in "iu")
     img_ok = img is None or (str(img.dtype) if img_t else "torch." + img.dtype.name) in _DEVICE_DTYPE_CODE
     if on_device and lbl_ok and img_ok:
         raw = _measure_raw_device(lbl, img, C, device, **more)
         if as_tensors:
-            return _measure_columns(raw, nd, channel_axis)
+            return _measure_columns(raw, nd, channel_axis, qs)
         from .utils import to_host
         sum_dtype, mm_dtype = (str(raw["sum"].dtype)[6:], str(raw["min"].dtype)[6:]) if img is not None else (None, None)
-        return _measure_columns(_measure_unpack(to_host(_measure_pack(raw)), nd, C, sum_dtype, mm_dtype, shape), nd, channel_axis)
+        back = _measure_unpack(to_host(_measure_pack(raw)), nd, C, sum_dtype, mm_dtype, shape)
+        if qs:
+            back["pct"] = to_host(raw["pct"].contiguous())                  # a second, small copy: the packed table keeps its layout
+        return _measure_columns(back, nd, channel_axis, qs)
     if not as_tensors:
         return _measure_columns(_measure_raw_host(lbl.cpu().numpy() if lbl_t else lbl, img.cpu().numpy() if img_t else img, **more), nd,
-                                channel_axis)
+                                channel_axis, qs)
     # the host table as tensors where the labels are (or on `device`): the packed raw columns make the trip
     import torch
-    host_packed = lambda l, i=None: _measure_pack(_measure_raw_host(l, i, **more))
-    rest = () if img is None else (img,)
-    if lbl_t:
-        packed = R.via_host(host_packed, lbl, *rest, to=device)
-    else:
-        packed = torch.as_tensor(host_packed(lbl, *[i.cpu().numpy() if img_t else i for i in rest]),
-                                 device=torch.device("cpu" if device is None else device))
+    where = torch.device(device) if device is not None else (lbl.device if lbl_t else torch.device("cpu"))
+    raw = _measure_raw_host(lbl.cpu().numpy() if lbl_t else lbl, img.cpu().numpy() if img_t else img, **more)
+    packed = torch.as_tensor(_measure_pack(raw), device=where)
     sum_dtype = mm_dtype = None
     if img is not None:
         name = str(img.dtype)[6:] if img_t else img.dtype.name
         floating = name.startswith("float") or name.startswith("bfloat")
         sum_dtype, mm_dtype = ("float64", name) if floating else ("int64", "int64")
-    return _measure_columns(_measure_unpack(packed, nd, C, sum_dtype, mm_dtype, shape), nd, channel_axis)
+    back = _measure_unpack(packed, nd, C, sum_dtype, mm_dtype, shape)
+    if qs:
+        back["pct"] = torch.as_tensor(raw["pct"], device=where)
+    return _measure_columns(back, nd, channel_axis, qs)
 
 
 # ----------------------------------------------------------------------------- connected components: mask -> label image

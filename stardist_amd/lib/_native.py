@@ -118,6 +118,7 @@ SIGNATURES = {
     "sd_fill_label_holes_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "sd_label_centroid_sums_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "sd_label_intensity_stats_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "sd_label_percentiles_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "sd_label_moment_sums_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sd_label_contour_counts_device": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "sd_label_components_device": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.c_longlong, _vp, _vp, _vp]),

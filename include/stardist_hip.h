@@ -818,6 +818,22 @@ int sd_label_border_flags_device(const int32_t* d_key, int Z, int Y, int X, int 
 int sd_label_clear_flagged_device(const int32_t* d_val, const int32_t* d_key, const uint8_t* d_flags, long long n_flags, long long n, int bgval,
                                   int32_t* d_out, void* stream);
 
+/* ---- label contacts (stardist_amd.utils.label_contacts, measure_labels(neighbors=); csrc/label_contacts.hip) ----
+ * d_lbl: an int32 label image of rank ndim = 2 (Z = 1) or 3 with extents Z, Y, X; connectivity in 1 .. ndim.  A contact is a pair of
+ * pixels (p, p + o), o one of the lexicographically positive offsets with at most `connectivity` non-zero coordinates, both inside the
+ * image, whose labels differ.  Result: every unordered pair {a, b}, a < b, of labels with at least one contact, ascending by (a, b), as
+ * d_keys[i] = a << 32 | b and d_counts[i] = its number of contacts; the pairs with a = 0 (the background) only with
+ * with_background != 0.  Buffer protocol of sd_label_overlap_device: *h_count (host) receives the number of pairs, the first
+ * min(*h_count, cap) of them are written (cap = 0 with NULL buffers is a pure count query).  h_minmax (host, 2 ints) receives {min, max}
+ * of d_lbl ({0, 0} for an extent <= 0, which is no error and gives no pair); if the minimum is negative nothing else is computed and
+ * *h_count = 0.  h_runs (host, may be NULL) receives the number of (key, length) runs the append pass wrote, before they are reduced:
+ * the sum of d_counts is the number of contacts, so runs < sum says that lanes were combined.  Integer arithmetic only: the table is
+ * bit-identical from call to call.  Synchronises the stream, as sd_label_overlap_device does: once for the number of runs, which sizes
+ * the sort, and once for the size of the table.  At most 2^31 - 1 runs; extents up to 2^31 - 1 - 128, their product is not bounded.
+ * -1 also for a rank or connectivity outside its range. */
+int sd_label_contacts_device(const int32_t* d_lbl, int ndim, int Z, int Y, int X, int connectivity, int with_background, long long cap,
+                             int64_t* d_keys, int64_t* d_counts, long long* h_count, int32_t* h_minmax, long long* h_runs, void* stream);
+
 /* The augmentation chain of a training batch (stardist_amd.augment.Compose.apply_device; the rules are csrc/augment.h's) in ONE launch:
  * d_x (B, *shape) float32 and d_y (B, *shape) int32, nd = 2 or 3 extents in h_shape, give d_out_x and d_out_y of the same shapes
  * (not the inputs): per sample FlipRot90 (always, as an index map), then Warp (flags bit 0; bit 1: mode 'reflect', else 'constant'),

@@ -1,6 +1,6 @@
 """Functions of label images with a host route (numpy + scipy, like the reference's) and a device route (hand-written HIP):
 fill_label_holes, calculate_extents, measure_labels, label_components, expand_labels, distance_transform, find_boundaries, clear_border,
-remove_small_objects, select_labels.  stardist_amd.utils re-exports
+remove_small_objects, select_labels, label_contacts.  stardist_amd.utils re-exports
 the public names.  Which route a call takes and what comes back is one rule, DESIGN.md section 3p, and its code is stardist_amd._route;
 a `_X_device` half here allocates its outputs and calls its kernels."""
 import numpy as np
@@ -313,6 +313,9 @@ def _shape_columns(out, raw, nd):
     return out
 
 
+_NEIGHBOR_NAMES = ("neighbors", "contact_objects", "contact_background")      # the columns of measure_labels(neighbors=), after all others
+
+
 def _shape_raw_host(lab, rows, starts):
     """(m2 (n, 6), contour (n, 18) or None for a volume) of the labels `rows` (ascending, all that are present) of the non-negative
     integer image lab, starts (n, nd) their boxes' starts: the definitions of csrc/measure_shape.h by numpy on the whole image"""
@@ -500,7 +503,7 @@ def _measure_raw_device(lbl, img, C, device, shape=False, percentiles=None):
     return raw
 
 
-def measure_labels(lbl, img=None, *, shape=False, percentiles=None, device=None, as_tensors=False):
+def measure_labels(lbl, img=None, *, shape=False, percentiles=None, neighbors=None, device=None, as_tensors=False):
     """Per-object table of a 2D / 3D integer label image (values <= 0 are background) and, optionally, of the image `img` that was
     segmented: shape lbl.shape or lbl.shape + (C,) (channels last).  Returns a dict of 1-D columns, one row per label present,
     ascending by label, named as scikit-image 0.18's regionprops_table names them:
@@ -528,6 +531,11 @@ def measure_labels(lbl, img=None, *, shape=False, percentiles=None, device=None,
         perimeter              skimage.measure.perimeter(mask, 4)
         perimeter_crofton      skimage.measure.perimeter_crofton(mask, 4)
         euler_number           skimage.measure.euler_number(mask, connectivity=2)
+      with neighbors=c (a connectivity, 1 .. ndim), after all columns above (int64; from label_contacts(lbl, c, background=True)):
+        neighbors              the number of other objects the object is in contact with
+        contact_objects        its contacts with other objects, summed
+        contact_background     its contacts with the background, value 0
+      A negative label raises ValueError with neighbors=, as in label_contacts.
 
     The shape columns are scikit-image 0.18's regionprops_table columns of these names, computed from integer tables per object
     (second-order coordinate sums, three counts of contour-pixel classes, a histogram of 2 x 2 pixel configurations: DESIGN.md section
@@ -568,6 +576,8 @@ def measure_labels(lbl, img=None, *, shape=False, percentiles=None, device=None,
     if shape and lbl.shape and int(np.prod([int(n) for n in lbl.shape], dtype=object)) * max(int(n) for n in lbl.shape) ** 2 >= 2 ** 63:
         raise ValueError("measure_labels: shape=True needs (number of pixels) x (largest extent)^2 below 2^63, got shape %s" % (tuple(lbl.shape),))
     qs = _percentile_list(percentiles, img is not None)
+    if neighbors is not None:
+        neighbors = _contacts_connectivity(neighbors, nd, "measure_labels: neighbors")
     more = {"shape": True} if shape else {}                                 # without shape / percentiles the two halves are called as before
     if qs:
         more["percentiles"] = qs
@@ -575,21 +585,35 @@ def measure_labels(lbl, img=None, *, shape=False, percentiles=None, device=None,
     img_ok = img is None or (str(img.dtype) if img_t else "torch." + img.dtype.name) in _DEVICE_DTYPE_CODE
     if on_device and lbl_ok and img_ok:
         raw = _measure_raw_device(lbl, img, C, device, **more)
+        near = None
+        if neighbors is not None:                                          # on the device, from the edge table there
+            near = _neighbor_columns(raw["label"], *_label_contacts_device(lbl, neighbors, True, device))
         if as_tensors:
-            return _measure_columns(raw, nd, channel_axis, qs)
+            out = _measure_columns(raw, nd, channel_axis, qs)
+            out.update(zip(_NEIGHBOR_NAMES, near or ()))
+            return out
         from .utils import to_host
         sum_dtype, mm_dtype = (str(raw["sum"].dtype)[6:], str(raw["min"].dtype)[6:]) if img is not None else (None, None)
         back = _measure_unpack(to_host(_measure_pack(raw)), nd, C, sum_dtype, mm_dtype, shape)
         if qs:
             back["pct"] = to_host(raw["pct"].contiguous())                  # a second, small copy: the packed table keeps its layout
-        return _measure_columns(back, nd, channel_axis, qs)
+        out = _measure_columns(back, nd, channel_axis, qs)
+        if near is not None:
+            import torch
+            near = to_host(torch.stack(near))                               # one more small copy, as for the percentiles
+            out.update((name, np.ascontiguousarray(near[k])) for k, name in enumerate(_NEIGHBOR_NAMES))
+        return out
+    host_lbl = lbl.cpu().numpy() if lbl_t else lbl
+    raw = _measure_raw_host(host_lbl, img.cpu().numpy() if img_t else img, **more)
+    contacts = None if neighbors is None else _label_contacts_host(host_lbl, neighbors, True)
     if not as_tensors:
-        return _measure_columns(_measure_raw_host(lbl.cpu().numpy() if lbl_t else lbl, img.cpu().numpy() if img_t else img, **more), nd,
-                                channel_axis, qs)
+        out = _measure_columns(raw, nd, channel_axis, qs)
+        if contacts is not None:
+            out.update(zip(_NEIGHBOR_NAMES, _neighbor_columns(out["label"], *contacts)))
+        return out
     # the host table as tensors where the labels are (or on `device`): the packed raw columns make the trip
     import torch
     where = torch.device(device) if device is not None else (lbl.device if lbl_t else torch.device("cpu"))
-    raw = _measure_raw_host(lbl.cpu().numpy() if lbl_t else lbl, img.cpu().numpy() if img_t else img, **more)
     packed = torch.as_tensor(_measure_pack(raw), device=where)
     sum_dtype = mm_dtype = None
     if img is not None:
@@ -599,7 +623,10 @@ def measure_labels(lbl, img=None, *, shape=False, percentiles=None, device=None,
     back = _measure_unpack(packed, nd, C, sum_dtype, mm_dtype, shape)
     if qs:
         back["pct"] = torch.as_tensor(raw["pct"], device=where)
-    return _measure_columns(back, nd, channel_axis, qs)
+    out = _measure_columns(back, nd, channel_axis, qs)
+    if contacts is not None:
+        out.update(zip(_NEIGHBOR_NAMES, _neighbor_columns(out["label"], *[torch.as_tensor(c, device=where) for c in contacts])))
+    return out
 
 
 # ----------------------------------------------------------------------------- connected components: mask -> label image
@@ -1279,3 +1306,207 @@ def select_labels(lbl, labels, *, invert=False, relabel=False, device=None):
     if is_t:
         return R.via_host(_select_labels_host, lbl, wanted, invert, relabel, to=device)
     return _select_labels_host(lbl, wanted, invert, relabel)
+
+
+# ----------------------------------------------------------------------------- label contacts: which objects touch, and by how much
+# (csrc/label_contacts.hip).  Both routes produce the plain table -- label_a < label_b and contacts, int64, ascending
+# by (label_a, label_b), original ids -- as numpy arrays or as tensors; _symmetric_contacts and _neighbor_columns derive everything else
+# from it with the same integer operations on either kind.
+
+def _forward_offsets(nd, connectivity):
+    """the offsets of generate_binary_structure(nd, connectivity) that are lexicographically positive: every unordered pair of
+    neighbouring pixels once (2 / 4 of them in 2D, 3 / 9 / 13 in 3D)"""
+    from itertools import product
+    return [o for o in product((-1, 0, 1), repeat=nd) if o > (0,) * nd and sum(1 for c in o if c) <= connectivity]
+
+
+def _contacts_connectivity(connectivity, nd, who):
+    if isinstance(connectivity, (bool, np.bool_)) or not isinstance(connectivity, (int, np.integer)) or not 1 <= connectivity <= nd:
+        raise ValueError("%s: connectivity for %dD images must be in [1, ..., %d], got %r" % (who, nd, nd, connectivity))
+    return int(connectivity)
+
+
+def _label_contacts_host(lbl, connectivity, background):
+    """(label_a, label_b, contacts) of a 2D / 3D numpy array of a bool or integer dtype: per forward offset two shifted slices, a != b,
+    the pairs as keys min << 32 | max and np.unique(..., return_counts=True), then a merge over the offsets"""
+    if lbl.dtype.kind == "b":
+        lbl = lbl.astype(np.uint8)
+    if lbl.size and lbl.dtype.kind == "i" and int(lbl.min()) < 0:
+        raise ValueError(_NEGATIVE_LABELS)
+    top = int(lbl.max()) if lbl.size else 0
+    ids = None
+    lab = lbl
+    if _ids_need_compaction(top, lbl.size):
+        pos = lbl > 0
+        ids, inv = np.unique(lbl[pos], return_inverse=True)
+        lab = np.zeros(lbl.shape, np.int64)
+        lab[pos] = inv.reshape(-1) + 1
+        ids = np.concatenate([np.zeros(1, np.int64), ids.astype(np.int64)])
+    keys, counts = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for off in _forward_offsets(lab.ndim, connectivity):
+        here = tuple(slice(max(0, -d), n - max(0, d)) for d, n in zip(off, lab.shape))
+        there = tuple(slice(max(0, d), n - max(0, -d)) for d, n in zip(off, lab.shape))
+        a, b = lab[here], lab[there]
+        keep = a != b
+        if not background:
+            keep &= (a != 0) & (b != 0)
+        a, b = a[keep].astype(np.int64), b[keep].astype(np.int64)
+        k, c = np.unique((np.minimum(a, b) << 32) | np.maximum(a, b), return_counts=True)
+        keys.append(k)
+        counts.append(c.astype(np.int64))
+    key, inv = np.unique(np.concatenate(keys), return_inverse=True)
+    total = np.zeros(len(key), np.int64)
+    np.add.at(total, inv.reshape(-1), np.concatenate(counts))
+    a, b = key >> 32, key & 0xFFFFFFFF
+    return (a, b, total) if ids is None else (ids[a], ids[b], total)
+
+
+def _label_contacts_device(lbl, connectivity, background, device=None, runs=None):
+    """(label_a, label_b, contacts) as int64 tensors on the device through sd_label_contacts_device; lbl a numpy array (uploaded to
+    `device`) or a tensor of an integer dtype.  Two scalars come to the host besides what reading the largest label needs: the number
+    of runs and the number of rows.  runs: a list that receives the number of runs the kernel appended"""
+    import ctypes
+    import torch
+    N.require_device()
+    if lbl.dtype.is_signed if R.is_torch(lbl) else lbl.dtype.kind == "i":
+        if (lbl.numel() if R.is_torch(lbl) else lbl.size) and int(lbl.min()) < 0:
+            raise ValueError(_NEGATIVE_LABELS)
+    lab, top, ids = R._device_labels(lbl, device)
+    dev = lab.device
+    if lab.numel() == 0 or top <= 0:
+        if runs is not None:
+            runs.append(0)
+        return tuple(torch.zeros(0, dtype=torch.int64, device=dev) for _ in range(3))
+    count, n_runs, mm = ctypes.c_longlong(0), ctypes.c_longlong(0), (ctypes.c_int32 * 2)()
+    cap = max(1024, lab.numel() // 64)        # a first guess; a table that is larger takes a second call with the real count
+    while True:
+        keys = torch.empty(cap, dtype=torch.int64, device=dev)
+        counts = torch.empty(cap, dtype=torch.int64, device=dev)
+        N.dcall(lab, "sd_label_contacts_device", R.ptr(lab), lab.dim(), *R.zyx(lab.shape), int(connectivity), int(bool(background)),
+                ctypes.c_longlong(cap), R.ptr(keys), R.ptr(counts), ctypes.byref(count), mm, ctypes.byref(n_runs))
+        if count.value <= cap:
+            break
+        cap = count.value
+    if runs is not None:
+        runs.append(n_runs.value)
+    m = count.value
+    keys, counts = keys[:m].clone(), counts[:m].clone()                     # the first guess's buffers go back to the allocator
+    return R.original_labels(keys >> 32, ids), R.original_labels(keys & 0xFFFFFFFF, ids), counts
+
+
+def _int64_ops(x):
+    """(concatenate, searchsorted, zeros like x of a length, add-at in place, stable argsort) for numpy arrays or tensors, after x"""
+    if R.is_torch(x):
+        import torch
+        return (torch.cat, torch.searchsorted, lambda n: torch.zeros(n, dtype=torch.int64, device=x.device),
+                lambda out, at, v: out.index_add_(0, at, v), lambda k: torch.sort(k, stable=True)[1])
+    return (np.concatenate, np.searchsorted, lambda n: np.zeros(n, np.int64), lambda out, at, v: np.add.at(out, at, v),
+            lambda k: np.argsort(k, kind="stable"))
+
+
+def _symmetric_contacts(a, b, contacts, present):
+    """the plain table listed both ways, sorted by (label_a, label_b), and the CSR offsets of the labels `present` (ascending, > 0):
+    the rows of present[i] are offsets[i] : offsets[i + 1]; the rows of label_a = 0 come before offsets[0]"""
+    cat, searchsorted, zeros, _, argsort = _int64_ops(a)
+    sa, sb, sc = cat([a, b]), cat([b, a]), cat([contacts, contacts])
+    # two stable sorts, by label_b and then by label_a: no key of two ids has to fit 64 bits
+    order = argsort(sb)
+    order = order[argsort(sa[order])]
+    sa, sb, sc = sa[order], sb[order], sc[order]
+    offsets = zeros(len(present) + 1)
+    offsets[:len(present)] = searchsorted(sa, present)
+    offsets[len(present):] = len(sa)
+    return sa, sb, sc, offsets
+
+
+def _neighbor_columns(label, a, b, contacts):
+    """(neighbors, contact_objects, contact_background) of the objects `label` (ascending, all > 0) from the plain contact table with
+    the background's pairs: the number of rows an object shares with another object, the contacts of those rows, and the contacts of
+    its row with 0"""
+    _, searchsorted, zeros, add_at, _ = _int64_ops(label)
+    n = len(label)
+    neighbors, objects, bg = zeros(n), zeros(n), zeros(n)
+    if len(a):
+        with_bg = a == 0
+        both = ~with_bg
+        ia, ib, c = searchsorted(label, a[both]), searchsorted(label, b[both]), contacts[both]
+        one = c * 0 + 1
+        for at in (ia, ib):
+            add_at(neighbors, at, one)
+            add_at(objects, at, c)
+        add_at(bg, searchsorted(label, b[with_bg]), contacts[with_bg])
+    return neighbors, objects, bg
+
+
+def _labels_present(lbl, on_device, device):
+    """the labels > 0 of the image, ascending, int64: a tensor on the device for the device route, else a numpy array"""
+    if on_device:
+        import torch
+        lab, top, ids = R._device_labels(lbl, device)
+        if lab.numel() == 0 or top <= 0:
+            return torch.zeros(0, dtype=torch.int64, device=lab.device)
+        sums = R.label_tables(lab, top, sums=True)[1]
+        return R.original_labels(torch.nonzero(sums[:, 0]).reshape(-1), ids)
+    u = np.unique(lbl)
+    return u[u > 0].astype(np.int64)
+
+
+def label_contacts(lbl, connectivity=1, *, background=False, symmetric=False, device=None, as_tensors=False):
+    """Which objects of a 2D / 3D integer label image touch, and over how many pixel pairs: the region adjacency graph with its edge
+    weights (scikit-image's future.graph.RAG has the edges, CLIJ's touch matrix the same relation).  With `connectivity` c in 1 .. ndim,
+    the forward offsets are the offsets of scipy.ndimage.generate_binary_structure(ndim, c) that are lexicographically positive (2 / 4
+    in 2D, 3 / 9 / 13 in 3D), and a contact is a pixel pair (p, p + o), o a forward offset, both inside the image, with
+    lbl[p] != lbl[p + o].  The image edge is no contact.  Returns a dict of int64 columns, one row per unordered pair of values that has
+    a contact:
+
+        label_a, label_b   the pair, label_a < label_b; rows ascend by (label_a, label_b)
+        contacts           its number of contacts
+
+    Value 0 is the background: its pairs (0, b) are listed only with background=True.  symmetric=True lists every row both ways,
+    (a, b) and (b, a), sorted by (label_a, label_b), so that the neighbours of one object are a contiguous slice, and adds
+
+        offsets            CSR offsets over the labels > 0 present in the image, ascending -- the rows of measure_labels: the neighbours
+                           of the i-th label are the rows offsets[i] : offsets[i + 1]; with background=True the rows with
+                           label_a = 0 come first, before offsets[0]
+
+    Objects "within a gap of d pixels" of each other are label_contacts(expand_labels(lbl, d / 2)); there is no distance argument.
+
+    Routing: DESIGN.md section 3p, like measure_labels (exception 4 there): the columns are numpy arrays whatever the input's kind,
+    which the device route reads back in one copy; as_tensors=True makes them tensors, on the device for the device route, else where
+    the labels are or on `device`.  The host code is numpy: per forward offset two shifted slices and np.unique.  The device route
+    takes bool and integer images and equals the host result exactly (csrc/label_contacts.hip: a tile of labels with a halo of 1 in
+    local memory, runs of equal pairs combined within a wave, a radix sort and a reduce-by-key; integers only, the same bits from call
+    to call; the input is not written).  Ids beyond int32, or sparse huge ids, are compacted in ascending order for the call and mapped
+    back.  A negative label, an image that is not 2D / 3D or not of a bool or integer dtype, or a connectivity outside 1 .. ndim
+    raise ValueError."""
+    lbl, is_t, on_device = R.classify(lbl, device)
+    nd = len(lbl.shape)
+    if nd not in (2, 3):
+        raise ValueError("label_contacts: the label image must be 2D or 3D, got %d dimensions" % nd)
+    connectivity = _contacts_connectivity(connectivity, nd, "label_contacts")
+    name = str(lbl.dtype).replace("torch.", "")
+    if name != "bool" and not (name.startswith("int") or name.startswith("uint")):
+        raise ValueError("label_contacts: the label image must have a bool or integer type, got %s" % name)
+    background, symmetric = bool(background), bool(symmetric)
+    taken = on_device and ((str(lbl.dtype) in _DEVICE_LABEL_DTYPES + ("torch.bool",)) if is_t else True)
+    if taken:
+        cols = _label_contacts_device(lbl, connectivity, background, device)
+    else:
+        host = lbl.cpu().numpy() if is_t else lbl
+        cols = _label_contacts_host(host, connectivity, background)
+    names = ("label_a", "label_b", "contacts")
+    if symmetric:
+        present = _labels_present(lbl if taken else (host.astype(np.uint8) if host.dtype.kind == "b" else host), taken, device)
+        cols = _symmetric_contacts(*cols, present)
+        names += ("offsets",)
+    if taken and not as_tensors:
+        import torch
+        from .utils import to_host
+        m = len(cols[0])
+        flat = to_host(torch.cat([c.reshape(-1) for c in cols]))           # one copy
+        cols = [np.ascontiguousarray(flat[k * m:(k + 1) * m]) for k in range(3)] + ([np.ascontiguousarray(flat[3 * m:])] if symmetric else [])
+    elif not taken and as_tensors:
+        import torch
+        where = torch.device(device) if device is not None else (lbl.device if is_t else torch.device("cpu"))
+        cols = [torch.as_tensor(np.ascontiguousarray(c), device=where) for c in cols]
+    return dict(zip(names, cols))

@@ -127,6 +127,7 @@ SIGNATURES = {
     "sd_find_boundaries_device": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp]),
     "sd_label_border_flags_device": (_i, [_vp, _i, _i, _i, _i, _i, _vp, ctypes.c_longlong, _vp, _vp]),
     "sd_label_clear_flagged_device": (_i, [_vp, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _i, _vp, _vp]),
+    "sd_label_contacts_device": (_i, [_vp, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sd_augment_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "sd_star_dist2d_points_device": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "sd_star_dist3d_points_device": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _vp, _vp]),

@@ -741,6 +741,21 @@ int sd_label_moment_sums_device(const int32_t* d_lbl, int Z, int Y, int X, int m
  *   euler_number(mask, 2) (= h_8 - h_6 - h_14). */
 int sd_label_contour_counts_device(const int32_t* d_lbl, int Y, int X, int max_label, int64_t* d_counts, void* stream);
 
+/* ---- hull table of labelled objects (csrc/measure_hull.hip, csrc/measure_hull.h): the two integers behind the hull columns of
+ * stardist_amd.utils.measure_labels(hull=True) -- convex_area, solidity, feret_diameter_max of scikit-image 0.18 ---------------------
+ * lbl (Y, X) int32 label image of a 2D image: labels 1 .. max_label are objects, every other value is background; d_boxes is the table
+ * sd_label_boxes_device wrote for this lbl and max_label (read on the device, every box clamped to the image; a row outside its
+ * label's box is ignored).  d_hull is [max_label + 1][2] = convex_area, F2; every row is written, row 0 and absent labels are 0.
+ *   In doubled coordinates pixel (r, c) has the centre (2 r, 2 c) and the diamond points (2 r +- 1, 2 c), (2 r, 2 c +- 1).  H = the
+ *   convex hull of the diamond points of the pixels of l; the convex image = the pixels whose centre lies in H or on its boundary;
+ *   convex_area = their number (pixels of other labels count); F2 = the largest squared distance between two diamond points of the
+ *   convex image's pixels, so that feret_diameter_max = sqrt(F2 / 4).
+ * Integer arithmetic only (int32 coordinates, int64 products, integer min / max atomics), 64-bit offsets: the table depends on the
+ * input alone.  Bad arguments (a null pointer, a non-positive extent, an extent of 2^30 or more, a negative max_label, more than 2^40
+ * pixels) set the error string and return -1 before anything is launched.  Two scalars, the summed heights of the boxes and the
+ * workspace of the objects too tall for LDS, come to the host to size the row table: the stream is synchronised once. */
+int sd_label_hull_device(const int32_t* d_lbl, int Y, int X, int max_label, const int32_t* d_boxes, int64_t* d_hull, void* stream);
+
 /* ---- connected components (csrc/label_cc.hip, csrc/label_cc.h): what skimage.measure.label(img, background, connectivity) and, for a
  * mask, scipy.ndimage.label(mask, generate_binary_structure(ndim, connectivity)) compute ----------------------------------------------
  * d_img: (Z, Y, X) contiguous image (2D: Z = 1); dtype: 0 = uint8 (a bool mask travels as uint8), 1 = uint16, 3 = int32 (the codes above;

@@ -115,8 +115,9 @@ def calculate_extents(lbl, func=np.median):
 # _measure_columns derives the table from them, the one place where centroid, mean and std are computed.  With shape=True both routes add
 # m2 (n, 6), the second-order sums of the box-local coordinates in the order zz, zy, zx, yy, yx, xx, and for a 2D image contour (n, 18) =
 # [n_1, n_r2, n_h, h_1 .. h_15], the contour-pixel classes and the 2 x 2 configuration histogram (csrc/measure_shape.h), all int64;
-# _shape_columns derives the shape columns from them.
-_MEASURE_RAW = ("label", "area", "bbox", "csum", "sum", "sum2", "min", "max", "m2", "contour")
+# _shape_columns derives the shape columns from them.  With hull=True both routes add hull (n, 2) = [convex_area, F2],
+# int64 (csrc/measure_hull.h); _hull_columns derives the hull columns from it.
+_MEASURE_RAW = ("label", "area", "bbox", "csum", "sum", "sum2", "min", "max", "m2", "contour", "hull")
 # With percentiles both routes add pct (n, C, n_q): float64 for integer images, else the image's float type.  It is no part of the packed
 # table: it travels as an array of its own.  _MAX_PERCENTILES is csrc/measure_rank.h's MR_MAX_Q.
 _MAX_PERCENTILES = 8
@@ -133,6 +134,7 @@ _CROFTON = [float(w) for w in (0, np.pi / 4 * (1 + 1 / (np.sqrt(2))), np.pi / (4
                                 np.pi / (4 * np.sqrt(2)), np.pi / (4 * np.sqrt(2)), np.pi / 4, np.pi / 2, 0, 0)]
 _SQRT2 = float(np.sqrt(2))
 _JACOBI_SWEEPS = 6
+_HULL_MAX_EXTENT = 2 ** 30                                                   # csrc/measure_hull.h's MH_MAX_EXTENT
 
 
 def _measure_shapes(lbl_shape, img_shape):
@@ -161,7 +163,7 @@ def _measure_pack(raw):
                                                 else a.astype(np.int64) for a in wide], axis=1))
 
 
-def _measure_unpack(packed, nd, C, sum_dtype, mm_dtype, shape=False):
+def _measure_unpack(packed, nd, C, sum_dtype, mm_dtype, shape=False, hull=False):
     """the raw columns of _measure_pack's array; sum_dtype / mm_dtype: the names of the dtypes of sum, sum2 and of min, max"""
     is_t = R.is_torch(packed)
     widths = [("label", 1, "int64"), ("area", 1, "int64"), ("bbox", 2 * nd, "int64"), ("csum", nd, "int64")]
@@ -169,6 +171,8 @@ def _measure_unpack(packed, nd, C, sum_dtype, mm_dtype, shape=False):
         widths += [("sum", C, sum_dtype), ("sum2", C, sum_dtype), ("min", C, mm_dtype), ("max", C, mm_dtype)]
     if shape:
         widths += [("m2", 6, "int64")] + ([("contour", _CONTOUR_WIDTH, "int64")] if nd == 2 else [])
+    if hull:
+        widths += [("hull", 2, "int64")]
     raw, at = {}, 0
     for key, w, dt in widths:
         a = packed[:, at:at + w]
@@ -226,6 +230,8 @@ def _measure_columns(raw, nd, channel_axis, qs=None):
                 out[("%s-%d" % (name, c)) if channel_axis else name] = col(raw["pct"][:, c, j])
     if "m2" in raw:
         _shape_columns(out, raw, nd)
+    if "hull" in raw:
+        _hull_columns(out, raw)
     return out
 
 
@@ -313,6 +319,109 @@ def _shape_columns(out, raw, nd):
     return out
 
 
+def _hull_columns(out, raw):
+    """adds the hull columns to the table `out` from the raw columns (numpy arrays or tensors), DESIGN.md section 3u: convex_area as it
+    is, solidity = float64(area) / float64(convex_area), feret_diameter_max = sqrt(float64(F2) / 4), every operation rounded on its own"""
+    if R.is_torch(raw["label"]):
+        import torch
+        f64, col, sqrt = (lambda a: a.to(torch.float64)), (lambda a: a.contiguous()), _tensor_sqrt
+    else:
+        f64, col, sqrt = (lambda a: a.astype(np.float64)), np.ascontiguousarray, np.sqrt
+    convex = col(raw["hull"][:, 0])
+    f2 = f64(raw["hull"][:, 1])
+    out["convex_area"] = convex
+    out["solidity"] = f64(raw["area"]) / f64(convex)
+    out["feret_diameter_max"] = sqrt(f2 / 4.0)                              # (a power of two: exact also as a product with 0.25)
+    return out
+
+
+def _hull_chain(points, side):
+    """the left (side < 0) or right chain of the hull of `points` [(y, x)], ascending in y: csrc/measure_hull.h's chain_step"""
+    st = []
+    for p in points:
+        while len(st) >= 2:
+            a, b = st[-2], st[-1]
+            c = (b[0] - a[0]) * (p[1] - a[1]) - (b[1] - a[1]) * (p[0] - a[0])
+            if (c > 0) if side < 0 else (c < 0):
+                break
+            st.pop()
+        st.append(p)
+    return st
+
+
+def _hull_chains(first, last):
+    """(left chain, right chain) of the hull of the diamond points of a row table -- first[j] .. last[j] the columns of row j, first >
+    last for a row without a pixel -- in doubled coordinates with row 0 at y = 0: level k = 0 .. 2 h lies at y = k - 1"""
+    h = len(first)
+    left, right = [], []
+    for k in range(2 * h + 1):
+        j = k >> 1
+        if k & 1:
+            if first[j] <= last[j]:
+                left.append((k - 1, 2 * first[j] - 1))
+                right.append((k - 1, 2 * last[j] + 1))
+        else:
+            rows = [r for r in (j - 1, j) if 0 <= r < h and first[r] <= last[r]]
+            if rows:
+                left.append((k - 1, 2 * min(first[r] for r in rows)))
+                right.append((k - 1, 2 * max(last[r] for r in rows)))
+    return _hull_chain(left, -1), _hull_chain(right, 1)
+
+
+def _hull_chain_at(st, ys, y):
+    """the chain's x at the height y as (numerator, denominator > 0); None outside the chain's heights"""
+    from bisect import bisect_right
+    if not st or y < ys[0] or y > ys[-1]:
+        return None
+    i = bisect_right(ys, y)                                                 # st[i - 1]: the last vertex at or above y
+    a = st[i - 1]
+    if a[0] == y:
+        return a[1], 1
+    b = st[i]
+    den = b[0] - a[0]
+    return a[1] * den + (b[1] - a[1]) * (y - a[0]), den
+
+
+def _hull_of_rows(first, last):
+    """(convex_area, F2) of the object with the row table first, last (lists of Python integers): the definition of DESIGN.md section
+    3u in Python integers, stage by stage as csrc/measure_hull.h"""
+    h = len(first)
+    left, right = _hull_chains(first, last)
+    ly, ry = [p[0] for p in left], [p[0] for p in right]
+    cfirst, clast, area = [], [], 0
+    for j in range(h):
+        lo, hi = _hull_chain_at(left, ly, 2 * j), _hull_chain_at(right, ry, 2 * j)
+        a, b = 1, 0
+        if lo is not None and hi is not None:
+            a, b = -((-lo[0]) // (2 * lo[1])), hi[0] // (2 * hi[1])          # ceil(xl / 2), floor(xr / 2)
+            if a > b:
+                a, b = 1, 0
+        cfirst.append(a)
+        clast.append(b)
+        area += b - a + 1
+    left, right = _hull_chains(cfirst, clast)
+    v = left + right
+    if len(v) <= 48:
+        f2 = max([(p[0] - q[0]) ** 2 + (p[1] - q[1]) ** 2 for i, p in enumerate(v) for q in v[i + 1:]] or [0])
+    else:
+        vy, vx = np.array([p[0] for p in v], np.int64), np.array([p[1] for p in v], np.int64)
+        f2 = max(int(((vy[i + 1:] - vy[i]) ** 2 + (vx[i + 1:] - vx[i]) ** 2).max()) for i in range(len(v) - 1))
+    return area, f2
+
+
+def _hull_raw_host(lab, boxes):
+    """hull (n, 2) int64 = [convex_area, F2] of the objects `boxes` [(label, slices)] of the 2D non-negative integer image lab"""
+    out = np.zeros((len(boxes), 2), np.int64)
+    for k, (l, box) in enumerate(boxes):
+        mask = lab[box] == l
+        w = mask.shape[1]
+        has = mask.any(axis=1)
+        first = np.where(has, mask.argmax(axis=1), 1)
+        last = np.where(has, w - 1 - mask[:, ::-1].argmax(axis=1), 0)
+        out[k] = _hull_of_rows(first.tolist(), last.tolist())
+    return out
+
+
 _NEIGHBOR_NAMES = ("neighbors", "contact_objects", "contact_background")      # the columns of measure_labels(neighbors=), after all others
 
 
@@ -376,10 +485,10 @@ def _percentile_list(percentiles, has_img):
     return qs
 
 
-def _measure_raw_host(lbl, img, shape=False, percentiles=None):
+def _measure_raw_host(lbl, img, shape=False, percentiles=None, hull=False):
     """the raw columns by numpy over scipy.ndimage.find_objects boxes; img: None or an array of lbl.shape (+ (C,)); shape: with m2 and,
-    for a 2D image, contour (_shape_raw_host); percentiles: a tuple of Python floats, with pct (n, C, len(percentiles)) =
-    np.percentile(values of the object in the channel, q), one q at a time"""
+    for a 2D image, contour (_shape_raw_host); hull: with hull (_hull_raw_host); percentiles: a tuple of Python floats, with pct (n, C,
+    len(percentiles)) = np.percentile(values of the object in the channel, q), one q at a time"""
     if lbl.dtype.kind == "b":
         lbl = lbl.astype(np.uint8)
     if lbl.dtype.kind not in "iu":
@@ -438,13 +547,16 @@ def _measure_raw_host(lbl, img, shape=False, percentiles=None):
         raw["m2"] = m2
         if contour is not None:
             raw["contour"] = contour
+    if hull:
+        raw["hull"] = _hull_raw_host(lab, boxes)
     return raw
 
 
-def _measure_raw_device(lbl, img, C, device, shape=False, percentiles=None):
+def _measure_raw_device(lbl, img, C, device, shape=False, percentiles=None, hull=False):
     """the raw columns as tensors on the device: sd_label_boxes_device, sd_label_centroid_sums_device, with an image
     sd_label_intensity_stats_device, with percentiles sd_label_percentiles_device and with shape sd_label_moment_sums_device and (2D)
-    sd_label_contour_counts_device, then the rows of the labels present (one scalar, their number, comes to the host)"""
+    sd_label_contour_counts_device, with hull sd_label_hull_device (which reads two scalars back to size its row table), then the rows
+    of the labels present (one scalar, their number, comes to the host)"""
     import torch
     N.require_device()
     lab, top, ids = R._device_labels(lbl, device)
@@ -468,6 +580,8 @@ def _measure_raw_device(lbl, img, C, device, shape=False, percentiles=None):
             raw["m2"] = torch.zeros((0, 6), dtype=torch.int64, device=dev)
             if nd == 2:
                 raw["contour"] = torch.zeros((0, _CONTOUR_WIDTH), dtype=torch.int64, device=dev)
+        if hull:
+            raw["hull"] = torch.zeros((0, 2), dtype=torch.int64, device=dev)
         return raw
     boxes, sums = R.label_tables(lab, top, boxes=True, sums=True)
     if img is not None:
@@ -500,10 +614,14 @@ def _measure_raw_device(lbl, img, C, device, shape=False, percentiles=None):
             counts = torch.empty((top + 1, _CONTOUR_WIDTH), dtype=torch.int64, device=dev)
             N.dcall(lab, "sd_label_contour_counts_device", R.ptr(lab), *lab.shape, top, R.ptr(counts))
             raw["contour"] = counts.index_select(0, present)
+    if hull:
+        table = torch.empty((top + 1, 2), dtype=torch.int64, device=dev)
+        N.dcall(lab, "sd_label_hull_device", R.ptr(lab), *lab.shape, top, R.ptr(boxes), R.ptr(table))
+        raw["hull"] = table.index_select(0, present)
     return raw
 
 
-def measure_labels(lbl, img=None, *, shape=False, percentiles=None, neighbors=None, device=None, as_tensors=False):
+def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, neighbors=None, device=None, as_tensors=False):
     """Per-object table of a 2D / 3D integer label image (values <= 0 are background) and, optionally, of the image `img` that was
     segmented: shape lbl.shape or lbl.shape + (C,) (channels last).  Returns a dict of 1-D columns, one row per label present,
     ascending by label, named as scikit-image 0.18's regionprops_table names them:
@@ -531,6 +649,10 @@ def measure_labels(lbl, img=None, *, shape=False, percentiles=None, neighbors=No
         perimeter              skimage.measure.perimeter(mask, 4)
         perimeter_crofton      skimage.measure.perimeter_crofton(mask, 4)
         euler_number           skimage.measure.euler_number(mask, connectivity=2)
+      with hull=True (2D images only; it does not need shape), after the columns above:
+        convex_area            int64    pixels of the convex image, counted over the object's box (pixels of other labels count)
+        solidity               float64  float64(area) / float64(convex_area)
+        feret_diameter_max     float64  sqrt(float64(F2) / 4), F2 the largest squared distance between two contour points, doubled
       with neighbors=c (a connectivity, 1 .. ndim), after all columns above (int64; from label_contacts(lbl, c, background=True)):
         neighbors              the number of other objects the object is in contact with
         contact_objects        its contacts with other objects, summed
@@ -542,6 +664,17 @@ def measure_labels(lbl, img=None, *, shape=False, percentiles=None, neighbors=No
     3q), on which the routes agree exactly.  One deviation, on purpose: where a - c == 0 scikit-image 0.18.3 returns -pi / 4 for b < 0 and
     pi / 4 otherwise, which is 90 degrees from the limit of its own general formula; this function returns the limit.  A call with
     shape=True whose pixel count times the square of the largest extent reaches 2^63 raises ValueError before anything runs.
+
+    The hull columns are scikit-image 0.18's regionprops_table columns of these names, stated in integers: in
+    doubled coordinates pixel (r, c) has the diamond points (2 r +- 1, 2 c), (2 r, 2 c +- 1); the convex image holds the pixels of the
+    object's box whose centre (2 r, 2 c) lies in the convex hull of the object's diamond points or on its boundary (cross products in
+    int64); F2 is the largest squared distance between two diamond points of the convex image's pixels, which are the extreme points of
+    skimage.measure.find_contours(convex image, 0.5).  Both routes produce the two integers convex_area and F2 per object (the host
+    route in Python integers over the find_objects boxes, the device route by csrc/measure_hull.hip) and agree on them exactly; they
+    equal scikit-image 0.18.3 bit for bit on tests/golden/hull_reference.npz.  hull=True on a 3D label image raises ValueError before
+    anything runs: scikit-image's 3D hull goes through Qhull with a floating tolerance, so voxels on facets cannot be matched (README
+    limit 3); so does an extent of 2^30 or more (doubled coordinates are int32).  On the device the call costs, besides the read-backs
+    named under Routing, one synchronisation that brings two scalars to the host, which size the table of object rows.
 
     Arithmetic: integer images are summed (values and squares) in int64, exactly, also beyond 2^53; float images in float64, where
     every square of a float32 is exact.  The derived columns are computed in one place for both routes, every operation rounded on
@@ -575,12 +708,20 @@ def measure_labels(lbl, img=None, *, shape=False, percentiles=None, neighbors=No
     shape = bool(shape)
     if shape and lbl.shape and int(np.prod([int(n) for n in lbl.shape], dtype=object)) * max(int(n) for n in lbl.shape) ** 2 >= 2 ** 63:
         raise ValueError("measure_labels: shape=True needs (number of pixels) x (largest extent)^2 below 2^63, got shape %s" % (tuple(lbl.shape),))
+    hull = bool(hull)
+    if hull and nd != 2:
+        raise ValueError("measure_labels: hull=True takes a 2D label image (scikit-image's 3D hull is Qhull's, with a floating tolerance "
+                         "that integers cannot restate), got %d axes" % nd)
+    if hull and max(int(n) for n in lbl.shape) >= _HULL_MAX_EXTENT:
+        raise ValueError("measure_labels: hull=True needs extents below 2^30, got shape %s" % (tuple(lbl.shape),))
     qs = _percentile_list(percentiles, img is not None)
     if neighbors is not None:
         neighbors = _contacts_connectivity(neighbors, nd, "measure_labels: neighbors")
     more = {"shape": True} if shape else {}                                 # without shape / percentiles the two halves are called as before
     if qs:
         more["percentiles"] = qs
+    if hull:
+        more["hull"] = True
     lbl_ok = (str(lbl.dtype) in _DEVICE_LABEL_DTYPES) if lbl_t else (lbl.dtype.kind in "iu")
     img_ok = img is None or (str(img.dtype) if img_t else "torch." + img.dtype.name) in _DEVICE_DTYPE_CODE
     if on_device and lbl_ok and img_ok:
@@ -594,7 +735,7 @@ def measure_labels(lbl, img=None, *, shape=False, percentiles=None, neighbors=No
             return out
         from .utils import to_host
         sum_dtype, mm_dtype = (str(raw["sum"].dtype)[6:], str(raw["min"].dtype)[6:]) if img is not None else (None, None)
-        back = _measure_unpack(to_host(_measure_pack(raw)), nd, C, sum_dtype, mm_dtype, shape)
+        back = _measure_unpack(to_host(_measure_pack(raw)), nd, C, sum_dtype, mm_dtype, shape, hull)
         if qs:
             back["pct"] = to_host(raw["pct"].contiguous())                  # a second, small copy: the packed table keeps its layout
         out = _measure_columns(back, nd, channel_axis, qs)
@@ -620,7 +761,7 @@ def measure_labels(lbl, img=None, *, shape=False, percentiles=None, neighbors=No
         name = str(img.dtype)[6:] if img_t else img.dtype.name
         floating = name.startswith("float") or name.startswith("bfloat")
         sum_dtype, mm_dtype = ("float64", name) if floating else ("int64", "int64")
-    back = _measure_unpack(packed, nd, C, sum_dtype, mm_dtype, shape)
+    back = _measure_unpack(packed, nd, C, sum_dtype, mm_dtype, shape, hull)
     if qs:
         back["pct"] = torch.as_tensor(raw["pct"], device=where)
     out = _measure_columns(back, nd, channel_axis, qs)

@@ -121,6 +121,7 @@ SIGNATURES = {
     "sd_label_percentiles_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "sd_label_moment_sums_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sd_label_contour_counts_device": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "sd_label_hull_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "sd_label_components_device": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.c_longlong, _vp, _vp, _vp]),
     "sd_nearest_feature_device": (_i, [_vp, _i, _i, _i, _i, _i] + [ctypes.c_double] * 4 + [_vp, _vp, _vp]),
     "sd_expand_labels_device": (_i, [_vp, _i, _i, _i] + [ctypes.c_double] * 4 + [_vp, _vp]),

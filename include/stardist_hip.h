@@ -849,6 +849,30 @@ int sd_label_clear_flagged_device(const int32_t* d_val, const int32_t* d_key, co
 int sd_label_contacts_device(const int32_t* d_lbl, int ndim, int Z, int Y, int X, int connectivity, int with_background, long long cap,
                              int64_t* d_keys, int64_t* d_counts, long long* h_count, int32_t* h_minmax, long long* h_runs, void* stream);
 
+/* ---- point neighbours (stardist_amd.utils.point_neighbors, measure_labels(nearest=, within=); DESIGN.md section 3v;
+ * csrc/point_neighbors.hip) ----
+ * d_points (n, nd) and d_queries (m, nd) float64, nd = 2 or 3, already scaled by the caller; d_queries = NULL (then m = n): the points
+ * are their own queries and query i skips point i, and only that one.  d2(q, p) = ((q0 - p0)^2 + (q1 - p1)^2) + (q2 - p2)^2, every
+ * operation rounded in float64, no fused multiply-add; candidates are ordered by (d2, index); with use_radius a candidate needs
+ * d2 <= r2 (the caller forms r2 = fl(radius * radius)).  Results hold d2, not its root.
+ *   mode 0   d_indices, d_d2 (m, k), k in 1 .. 64: the first k candidates of every query, -1 / +inf where there are fewer
+ *   mode 1   d_offsets (m): the number of candidates of every query (needs use_radius); nothing else is written
+ *   mode 2   d_offsets (m + 1): the exclusive sums of those numbers, *h_total (host) the last of them; if 0 < *h_total <= cap, d_indices
+ *            and d_d2 (cap entries each) receive row i at d_offsets[i] .. d_offsets[i + 1], ascending by index; a caller that
+ *            finds *h_total > cap comes again with room (cap = 0 with NULL lists is a pure size query)
+ * cell_size: 0 lets the library choose the edge of the grid's cells from the points' box and n, about two points per cell; a value
+ * in [2^-500, 2^500] is taken as given (-1 if that makes more than 2^21 cells along an axis or 2^27 in all).  *h_cell (host, may be
+ * NULL) receives the edge used.  The result does not depend on the cell size.  Synchronises the stream once, to read the box of the
+ * points (128 x 6 doubles), and in mode 2 once more for the total.  No atomics: the same bits from call to call.  n = 0 or m = 0 is no
+ * error (mode 0 fills -1 / +inf, the others zeros).  -1 also for nd, mode or k outside their range, n or m beyond 2^31 - 2, a radius
+ * mode without use_radius, r2 < 0 or NaN, a cell size outside its range, a point coordinate that is not finite or not below 2^500 in
+ * magnitude (the queries are the caller's to check), a missing buffer.  Time grows with the fullest cells: one far outlier that
+ * stretches the box can leave all other points in one cell (correct, but quadratic), and a query far from everything walks up to
+ * every cell once. */
+int sd_point_neighbors_device(const double* d_points, long long n, const double* d_queries, long long m, int nd, int mode, int k,
+                              int use_radius, double r2, double cell_size, long long cap, int64_t* d_indices, double* d_d2,
+                              int64_t* d_offsets, long long* h_total, double* h_cell, void* stream);
+
 /* The augmentation chain of a training batch (stardist_amd.augment.Compose.apply_device; the rules are csrc/augment.h's) in ONE launch:
  * d_x (B, *shape) float32 and d_y (B, *shape) int32, nd = 2 or 3 extents in h_shape, give d_out_x and d_out_y of the same shapes
  * (not the inputs): per sample FlipRot90 (always, as an index map), then Warp (flags bit 0; bit 1: mode 'reflect', else 'constant'),

@@ -1,7 +1,7 @@
 """Functions of label images with a host route (numpy + scipy, like the reference's) and a device route (hand-written HIP):
 fill_label_holes, calculate_extents, measure_labels, label_components, expand_labels, distance_transform, find_boundaries, clear_border,
-remove_small_objects, select_labels, label_contacts.  stardist_amd.utils re-exports
-the public names.  Which route a call takes and what comes back is one rule, DESIGN.md section 3p, and its code is stardist_amd._route;
+remove_small_objects, select_labels, label_contacts -- and point_neighbors, which takes the objects' centroids.  stardist_amd.utils
+re-exports the public names.  Which route a call takes and what comes back is one rule, DESIGN.md section 3p, and its code is stardist_amd._route;
 a `_X_device` half here allocates its outputs and calls its kernels."""
 import numpy as np
 
@@ -621,7 +621,56 @@ def _measure_raw_device(lbl, img, C, device, shape=False, percentiles=None, hull
     return raw
 
 
-def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, neighbors=None, device=None, as_tensors=False):
+def _proximity_args(nearest, within, spacing, nd):
+    """(k, radius, r2, per-axis spacing) of measure_labels' nearest=, within= and spacing=, checked; spacing without the two is refused"""
+    if nearest is None and within is None:
+        if not (np.ndim(spacing) == 0 and not isinstance(spacing, (str, bytes)) and spacing == 1):
+            raise ValueError("measure_labels: spacing applies to nearest= and within= only; give one of them")
+        return None, None, None, None
+    k = radius = r2 = None
+    if nearest is not None:
+        k = _point_neighbors_args(nearest, None, False, "measure_labels: nearest")[0]
+    if within is not None:
+        _, radius, r2 = _point_neighbors_args(None, within, False, "measure_labels: within")
+    return k, radius, r2, R.spacing_zyx(spacing, nd, "measure_labels")[1]
+
+
+def _proximity_names(k, radius):
+    names = [n % j for j in range(k or 0) for n in ("nearest_label-%d", "nearest_distance-%d")]
+    return names + (["neighbors_within"] if radius is not None else [])
+
+
+def _proximity_columns(label, csum, area, k, radius, r2, per_axis):
+    """the columns of _proximity_names from the objects' labels, coordinate sums and pixel counts (numpy arrays, or tensors on the
+    device): point_neighbors over the centroids float64(sum) / count times the spacing, the points their own queries; an index becomes
+    the label of that row, 0 where there is none"""
+    cols = []
+    if R.is_torch(label):
+        import torch
+        P = (csum.to(torch.float64) / area.to(torch.float64)[:, None] * torch.as_tensor(per_axis, dtype=torch.float64, device=label.device)).contiguous()
+        if k is not None:
+            idx, d2 = _point_neighbors_device(P, None, 0, k, None)
+            lab = torch.where(idx >= 0, label[idx.clamp(min=0)] if len(label) else idx, torch.zeros_like(idx))
+            dist = _tensor_sqrt(d2)
+            for j in range(k):
+                cols += [lab[:, j].contiguous(), dist[:, j].contiguous()]
+        if radius is not None:
+            cols.append(_point_neighbors_device(P, None, 1, None, r2))
+        return cols
+    P = csum.astype(np.float64) / area.astype(np.float64)[:, None] * np.asarray(per_axis, np.float64)
+    if k is not None:
+        idx, d2 = _nearest_host(P, P, True, k, None)
+        lab = np.where(idx >= 0, label[np.maximum(idx, 0)] if len(label) else idx, 0).astype(np.int64)
+        dist = np.sqrt(d2)
+        for j in range(k):
+            cols += [np.ascontiguousarray(lab[:, j]), np.ascontiguousarray(dist[:, j])]
+    if radius is not None:
+        cols.append(_within_host(P, P, True, radius, r2, True)[0])
+    return cols
+
+
+def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, neighbors=None, nearest=None, within=None, spacing=1,
+                   device=None, as_tensors=False):
     """Per-object table of a 2D / 3D integer label image (values <= 0 are background) and, optionally, of the image `img` that was
     segmented: shape lbl.shape or lbl.shape + (C,) (channels last).  Returns a dict of 1-D columns, one row per label present,
     ascending by label, named as scikit-image 0.18's regionprops_table names them:
@@ -658,6 +707,17 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
         contact_objects        its contacts with other objects, summed
         contact_background     its contacts with the background, value 0
       A negative label raises ValueError with neighbors=, as in label_contacts.
+      with nearest=k (1 .. 64), after all columns above, for j = 0 .. k - 1 (the k nearest other objects by centroid, in the order
+      (squared distance, row) of point_neighbors, whose definition they follow):
+        nearest_label-j        int64    the label of the j-th nearest other object, 0 where there is none
+        nearest_distance-j     float64  the distance between the two centroids, inf where there is none
+      with within=r (finite, >= 0), after those:
+        neighbors_within       int64    the number of other objects whose centroid lies within r of the object's
+      spacing (a positive scalar or one value per axis, default 1) scales the centroids for these two keywords only -- the centroid-*
+      columns stay in pixels -- and raises ValueError without them.  The two are point_neighbors(centroids, k, spacing=spacing) and
+      point_neighbors(centroids, radius=r, spacing=spacing, count_only=True) over the table's own centroid columns; on the device
+      route the centroids stay on the device (the read-backs of point_neighbors' device route apply: the box of the points, once per
+      keyword) and the new columns come to the host in one more small copy.
 
     The shape columns are scikit-image 0.18's regionprops_table columns of these names, computed from integer tables per object
     (second-order coordinate sums, three counts of contour-pixel classes, a histogram of 2 x 2 pixel configurations: DESIGN.md section
@@ -717,6 +777,8 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
     qs = _percentile_list(percentiles, img is not None)
     if neighbors is not None:
         neighbors = _contacts_connectivity(neighbors, nd, "measure_labels: neighbors")
+    near_k, near_r, near_r2, near_spacing = _proximity_args(nearest, within, spacing, nd)
+    near_names = _proximity_names(near_k, near_r)
     more = {"shape": True} if shape else {}                                 # without shape / percentiles the two halves are called as before
     if qs:
         more["percentiles"] = qs
@@ -729,9 +791,11 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
         near = None
         if neighbors is not None:                                          # on the device, from the edge table there
             near = _neighbor_columns(raw["label"], *_label_contacts_device(lbl, neighbors, True, device))
+        close = _proximity_columns(raw["label"], raw["csum"], raw["area"], near_k, near_r, near_r2, near_spacing) if near_names else []
         if as_tensors:
             out = _measure_columns(raw, nd, channel_axis, qs)
             out.update(zip(_NEIGHBOR_NAMES, near or ()))
+            out.update(zip(near_names, close))
             return out
         from .utils import to_host
         sum_dtype, mm_dtype = (str(raw["sum"].dtype)[6:], str(raw["min"].dtype)[6:]) if img is not None else (None, None)
@@ -743,6 +807,11 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
             import torch
             near = to_host(torch.stack(near))                               # one more small copy, as for the percentiles
             out.update((name, np.ascontiguousarray(near[k])) for k, name in enumerate(_NEIGHBOR_NAMES))
+        if close:
+            import torch
+            back = to_host(torch.stack([c.view(torch.int64) if c.dtype.is_floating_point else c for c in close]))      # one small copy
+            out.update((name, np.ascontiguousarray(back[j]).view(np.float64 if "distance" in name else np.int64))
+                       for j, name in enumerate(near_names))
         return out
     host_lbl = lbl.cpu().numpy() if lbl_t else lbl
     raw = _measure_raw_host(host_lbl, img.cpu().numpy() if img_t else img, **more)
@@ -751,6 +820,8 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
         out = _measure_columns(raw, nd, channel_axis, qs)
         if contacts is not None:
             out.update(zip(_NEIGHBOR_NAMES, _neighbor_columns(out["label"], *contacts)))
+        if near_names:
+            out.update(zip(near_names, _proximity_columns(raw["label"], raw["csum"], raw["area"], near_k, near_r, near_r2, near_spacing)))
         return out
     # the host table as tensors where the labels are (or on `device`): the packed raw columns make the trip
     import torch
@@ -767,6 +838,9 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
     out = _measure_columns(back, nd, channel_axis, qs)
     if contacts is not None:
         out.update(zip(_NEIGHBOR_NAMES, _neighbor_columns(out["label"], *[torch.as_tensor(c, device=where) for c in contacts])))
+    if near_names:
+        close = _proximity_columns(raw["label"], raw["csum"], raw["area"], near_k, near_r, near_r2, near_spacing)
+        out.update((name, torch.as_tensor(c, device=where)) for name, c in zip(near_names, close))
     return out
 
 
@@ -1611,6 +1685,7 @@ def label_contacts(lbl, connectivity=1, *, background=False, symmetric=False, de
                            label_a = 0 come first, before offsets[0]
 
     Objects "within a gap of d pixels" of each other are label_contacts(expand_labels(lbl, d / 2)); there is no distance argument.
+    The objects near an object by centroid, with their distances, are point_neighbors'.
 
     Routing: DESIGN.md section 3p, like measure_labels (exception 4 there): the columns are numpy arrays whatever the input's kind,
     which the device route reads back in one copy; as_tensors=True makes them tensors, on the device for the device route, else where
@@ -1649,5 +1724,271 @@ def label_contacts(lbl, connectivity=1, *, background=False, symmetric=False, de
     elif not taken and as_tensors:
         import torch
         where = torch.device(device) if device is not None else (lbl.device if is_t else torch.device("cpu"))
+        cols = [torch.as_tensor(np.ascontiguousarray(c), device=where) for c in cols]
+    return dict(zip(names, cols))
+
+
+# ----------------------------------------------------------------------------- point neighbours: the nearest points, the points within a radius
+# (csrc/point_neighbors.hip).  Both routes work on scaled float64 coordinates and produce squared distances by the
+# one definition: d2 = ((q0 - p0)^2 + (q1 - p1)^2) + (q2 - p2)^2, every operation rounded, candidates ordered by (d2, index).
+
+_POINT_NEIGHBORS_MAX_K = 64                                                 # csrc/point_neighbors.h's PN_MAX_K
+_POINT_NEIGHBORS_MAX_COORD = 2.0 ** 500                                     # PN_MAX_COORD
+_POINT_NEIGHBORS_SLACK = 2.0 ** -40                                         # by how much a k-d tree's own distances may differ from d2's
+_POINT_NEIGHBORS_WORKERS = 1                                                # threads of the host route's tree queries (tools/time_point_neighbors.py tries 16)
+
+
+def _points_as_float64(x, what, nd=None):
+    """the (n, nd) float64 array / tensor of the points x (numpy, tensor or nested lists; integer, float32 or float64)"""
+    if R.is_torch(x):
+        import torch
+        name = str(x.dtype).replace("torch.", "")
+        ok = name in ("float32", "float64", "uint8", "int8", "int16", "int32", "int64")
+        p = x.to(torch.float64) if ok else x
+    else:
+        x = np.asarray(x)
+        if x.size == 0 and x.dtype.kind not in "iuf":
+            x = x.astype(np.float64)
+        ok = x.dtype.kind in "iu" or x.dtype in (np.float32, np.float64)
+        p = x.astype(np.float64) if ok else x
+    if not ok:
+        raise ValueError("point_neighbors: the %s must be integer, float32 or float64, got %s" % (what, x.dtype))
+    if len(p.shape) != 2 or p.shape[1] not in (2, 3) or (nd is not None and p.shape[1] != nd):
+        raise ValueError("point_neighbors: the %s must have the shape (n, %s), got %s" % (what, nd or "2 or 3", tuple(p.shape)))
+    if p.shape[0] >= 2 ** 31:
+        raise ValueError("point_neighbors: 2^31 or more %s" % what)
+    return p
+
+
+def _scaled_points(p, per_axis, what):
+    """p * spacing, rounded once per coordinate; ValueError for a coordinate that is not finite or reaches 2^500 in magnitude"""
+    if R.is_torch(p):
+        import torch
+        s = p * torch.as_tensor(per_axis, dtype=torch.float64, device=p.device)
+        fine = p.numel() == 0 or bool((torch.isfinite(p).all() & (s.abs() < _POINT_NEIGHBORS_MAX_COORD).all()))
+    else:
+        with np.errstate(all="ignore"):
+            s = p * np.asarray(per_axis, np.float64)
+            fine = bool(np.isfinite(p).all() and (np.abs(s) < _POINT_NEIGHBORS_MAX_COORD).all())
+    if not fine:
+        raise ValueError("point_neighbors: the %s must be finite and below 2^500 in magnitude (after the spacing)" % what)
+    return s
+
+
+def _squared_distances(q, p):
+    """d2 of the definition between q (..., nd) and p (..., nd), numpy"""
+    d = q - p
+    s = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]
+    return s + d[..., 2] * d[..., 2] if d.shape[-1] == 3 else s
+
+
+def _nearest_host(P, Q, own, k, r2):
+    """(indices (m, k) int64, d2 (m, k) float64) of the definition; the k-d tree supplies candidates only: K = min(n, k + 9) per row, a
+    row is accepted when K >= n or when its k-th recomputed d2 is below (1 - 2^-40) times its largest recomputed d2 (then nothing the
+    tree left out can reach the first k), and K doubles for the rows left.  own: the points are their own queries"""
+    from scipy.spatial import cKDTree
+    n, m = len(P), len(Q)
+    out_i, out_d = np.full((m, k), -1, np.int64), np.full((m, k), np.inf)
+    if n == 0 or m == 0:
+        return out_i, out_d
+    tree = cKDTree(P)
+    rows, K = np.arange(m), min(n, k + 9)
+    while len(rows):
+        idx = np.asarray(tree.query(Q[rows], k=K, workers=_POINT_NEIGHBORS_WORKERS)[1], np.int64).reshape(len(rows), K)
+        d2 = _squared_distances(Q[rows][:, None, :], P[idx])
+        largest = d2.max(axis=1)
+        if own:
+            d2 = np.where(idx == rows[:, None], np.inf, d2)                 # a point is not its own neighbour; its slot sorts last
+        order = np.lexsort((idx, d2), axis=1)[:, :k]                        # by (d2, index)
+        best_d, best_i = np.take_along_axis(d2, order, axis=1), np.take_along_axis(idx, order, axis=1)
+        if K >= n:
+            done = np.ones(len(rows), bool)
+        elif best_d.shape[1] < k:
+            done = np.zeros(len(rows), bool)
+        else:
+            done = best_d[:, k - 1] < (1.0 - _POINT_NEIGHBORS_SLACK) * largest
+        w = best_d.shape[1]
+        got_d, got_i = best_d[done], best_i[done]
+        keep = np.isfinite(got_d) if r2 is None else (got_d <= r2)          # inf: the own slot; the rest of a row is beyond r2 too
+        out_d[rows[done], :w] = np.where(keep, got_d, np.inf)
+        out_i[rows[done], :w] = np.where(keep, got_i, -1)
+        rows, K = rows[~done], min(n, 2 * K)
+    return out_i, out_d
+
+
+def _within_host(P, Q, own, radius, r2, count_only):
+    """(counts (m,), indices, d2) of the points within the radius, the rows ascending by index (indices and d2 None with count_only):
+    the tree's ball of radius * (1 + 2^-40) supplies the candidates, d2 <= r2 decides"""
+    from scipy.spatial import cKDTree
+    n, m = len(P), len(Q)
+    if n == 0 or m == 0:
+        return np.zeros(m, np.int64), None if count_only else np.zeros(0, np.int64), None if count_only else np.zeros(0)
+    lists = cKDTree(P).query_ball_point(Q, radius * (1.0 + _POINT_NEIGHBORS_SLACK), workers=_POINT_NEIGHBORS_WORKERS)
+    lens = np.fromiter((len(l) for l in lists), np.int64, m)
+    idx = np.fromiter((i for l in lists for i in l), np.int64, int(lens.sum()))
+    row = np.repeat(np.arange(m), lens)
+    d2 = _squared_distances(Q[row], P[idx])
+    keep = d2 <= r2
+    if own:
+        keep &= idx != row
+    row, idx, d2 = row[keep], idx[keep], d2[keep]
+    counts = np.bincount(row, minlength=m).astype(np.int64)
+    if count_only:
+        return counts, None, None
+    order = np.lexsort((idx, row))
+    return counts, idx[order], d2[order]
+
+
+def _point_neighbors_device(P, Q, mode, k, r2, cell_size=0.0, cell=None):
+    """sd_point_neighbors_device on the contiguous float64 device tensors P (n, nd) and Q (m, nd) or None (the points are their own
+    queries): mode 0 -> (indices (m, k), d2 (m, k)); mode 1 -> counts (m,); mode 2 -> (offsets (m + 1,), indices, d2), for which the
+    total comes to the host to size the lists.  cell: a list that receives the cell edge the library used"""
+    import ctypes
+    import torch
+    N.require_device()
+    dev, n, nd = P.device, int(P.shape[0]), int(P.shape[1])
+    m = n if Q is None else int(Q.shape[0])
+    total, used = ctypes.c_longlong(0), ctypes.c_double(0.0)
+    i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device=dev)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    fixed = (R.ptr(P), ctypes.c_longlong(n), None if Q is None else R.ptr(Q), ctypes.c_longlong(m), nd, int(mode), int(k or 0),
+             int(r2 is not None), ctypes.c_double(0.0 if r2 is None else r2), ctypes.c_double(cell_size))
+    tail = (ctypes.byref(total), ctypes.byref(used))
+    if m == 0:                                    # no query: an empty tensor has no address to tell it from "no queries"
+        out = (i64(0, k), f64(0, k)) if mode == 0 else i64(0) if mode == 1 else (torch.zeros(1, dtype=torch.int64, device=dev), i64(0), f64(0))
+    elif mode == 0:
+        idx, d2 = i64(m, k), f64(m, k)
+        N.dcall(P, "sd_point_neighbors_device", *fixed, ctypes.c_longlong(0), R.ptr(idx), R.ptr(d2), None, *tail)
+        out = idx, d2
+    elif mode == 1:
+        out = i64(m)
+        N.dcall(P, "sd_point_neighbors_device", *fixed, ctypes.c_longlong(0), None, None, R.ptr(out), *tail)
+    else:
+        offsets = i64(m + 1)
+        cap = max(1024, 32 * m)                   # a first guess; longer lists take a second call with the real total
+        while True:
+            idx, d2 = i64(cap), f64(cap)
+            N.dcall(P, "sd_point_neighbors_device", *fixed, ctypes.c_longlong(cap), R.ptr(idx), R.ptr(d2), R.ptr(offsets), *tail)
+            if total.value <= cap:
+                break
+            cap = total.value
+        out = offsets, idx[:total.value].clone(), d2[:total.value].clone()
+    if cell is not None:
+        cell.append(used.value)
+    return out
+
+
+def _point_neighbors_args(k, radius, count_only, who="point_neighbors"):
+    if k is None and radius is None:
+        raise ValueError("%s: give k, radius or both" % who)
+    if k is not None:
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _POINT_NEIGHBORS_MAX_K:
+            raise ValueError("%s: k must be an integer in 1 .. %d, got %r" % (who, _POINT_NEIGHBORS_MAX_K, k))
+        k = int(k)
+    r2 = None
+    if radius is not None:
+        if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(radius) or radius < 0:
+            raise ValueError("%s: the radius must be a finite number >= 0, got %r" % (who, radius))
+        radius = float(radius)
+        with np.errstate(over="ignore"):
+            r2 = float(np.float64(radius) * np.float64(radius))
+    if count_only and radius is None:
+        raise ValueError("%s: count_only needs a radius" % who)
+    if count_only and k is not None:
+        raise ValueError("%s: count_only counts the points within a radius; it takes no k" % who)
+    return k, radius, r2
+
+
+def point_neighbors(points, k=None, radius=None, *, queries=None, spacing=1, count_only=False, device=None, as_tensors=False):
+    """The nearest points of every query, and the points within a radius of it: the k-nearest / radius graph over object centroids
+    (CellProfiler's MeasureObjectNeighbors reports FirstClosestDistance, SecondClosestDistance and NumberOfNeighbors within a distance
+    from it), or the nearest nucleus of every spot with a second point set.
+
+    points: (n, nd), nd 2 or 3, a numpy array, a tensor or nested lists of an integer, float32 or float64 type, converted to float64
+    (exactly, but for integers beyond 2^53) -- the stacked centroid-* columns of measure_labels, or details["points"].  queries: (m, nd)
+    or None; with None the points are their own queries and point i is never a neighbour of query i -- only index i is left out, other
+    points at the same place count, at distance 0.  spacing: a positive finite scalar or nd values.  At least one of k (1 .. 64) and
+    radius (finite, >= 0) is needed.
+
+    The definition, which both routes follow bit for bit.  A coordinate is scaled once, p[a] = fl(x[a] * spacing[a]).
+    d2(q, p) = ((q0 - p0)^2 + (q1 - p1)^2) + (q2 - p2)^2, left to right (two terms for nd = 2), every operation rounded in float64, no
+    fused multiply-add.  The candidates of a query are ordered by (d2, index).  "Within the radius" means d2 <= fl(radius * radius).
+    A distance is sqrt(d2), correctly rounded.
+
+    Returns a dict:
+        with k            indices (m, k) int64 and distances (m, k) float64: the first k candidates of every query in that order --
+                          with a radius as well, only those within it; -1 and inf where there are fewer
+        radius alone      offsets (m + 1,) int64, and indices, distances (offsets[-1],): the points within the radius of query i are
+                          the rows offsets[i] : offsets[i + 1], ascending by index
+        count_only=True   counts (m,) int64, the lengths of those rows; the lists are not made
+
+    Routing: DESIGN.md section 3p, like label_contacts: numpy or host input without device= runs the host code, a tensor on a HIP
+    device or device= the kernels; the columns are numpy arrays (the device route reads them back with one synchronisation) unless
+    as_tensors=True, which makes them tensors -- on the device for the device route, else where the points are or on `device`.  The
+    host code asks scipy.spatial.cKDTree for candidates only (a few more than k, doubled while ties or near-ties reach the last of
+    them; the ball of radius * (1 + 2^-40)) and recomputes d2, the order and the radius test by the definition.  The device route
+    (csrc/point_neighbors.hip) sorts the points into a uniform grid of about two points per cell and walks the
+    rings of cells around every query, one lane per query, until a bound that is safe under rounding says nothing nearer is left; no
+    atomics, so the same bits from call to call.  It brings the points' box to the host once (a synchronisation), the total length
+    for the radius lists once more, and for tensors one flag per point set that says the coordinates are fine.  Its time grows with
+    the fullest cells: a single far outlier stretches the box and can put all other points into one cell, which is correct but
+    quadratic, and a query far from all points walks up to every cell once.
+
+    ValueError before anything runs: points that are not (n, 2) or (n, 3) or queries of another width, another dtype, a coordinate
+    that is not finite, |coordinate * spacing| >= 2^500, n or m >= 2^31, k outside 1 .. 64, a radius that is negative or not finite,
+    neither k nor radius, count_only without a radius or with k, a spacing that is not positive and finite."""
+    if not R.is_torch(points):
+        points = np.asarray(points)
+    if queries is not None and not R.is_torch(queries):
+        queries = np.asarray(queries)
+    is_t = R.is_torch(points)
+    on_device = device is not None or (is_t and points.is_cuda) or (queries is not None and R.is_device_tensor(queries))
+    count_only = bool(count_only)
+    k, radius, r2 = _point_neighbors_args(k, radius, count_only)
+    P = _points_as_float64(points, "points")
+    nd = int(P.shape[1])
+    Q = None if queries is None else _points_as_float64(queries, "queries", nd)
+    per_axis = R.spacing_zyx(spacing, nd, "point_neighbors")[1]
+    own = Q is None
+    P = _scaled_points(P, per_axis, "points")
+    if not own:
+        Q = _scaled_points(Q, per_axis, "queries")
+    names = ("counts",) if count_only else ("indices", "distances") if k is not None else ("offsets", "indices", "distances")
+    if on_device:
+        import torch
+        N.require_device()
+        where = None
+        for t in (points, queries):
+            if where is None and R.is_device_tensor(t):
+                where = t.device
+        where = torch.device(device) if device is not None else where
+        P = R.to_device_tensor(P, where)
+        Q = None if own else R.to_device_tensor(Q, P.device)
+        if count_only:
+            cols = [_point_neighbors_device(P, Q, 1, None, r2)]
+        elif k is not None:
+            idx, d2 = _point_neighbors_device(P, Q, 0, k, r2)
+            cols = [idx, _tensor_sqrt(d2)]
+        else:
+            offsets, idx, d2 = _point_neighbors_device(P, Q, 2, None, r2)
+            cols = [offsets, idx, _tensor_sqrt(d2)]
+        if not as_tensors:
+            from .utils import to_host_many
+            cols = to_host_many(cols)                                       # one synchronisation
+        return dict(zip(names, cols))
+    hP = P.cpu().numpy() if is_t else P
+    hQ = hP if own else (Q.cpu().numpy() if R.is_torch(Q) else Q)
+    if count_only:
+        cols = [_within_host(hP, hQ, own, radius, r2, True)[0]]
+    elif k is not None:
+        idx, d2 = _nearest_host(hP, hQ, own, k, r2)
+        cols = [idx, np.sqrt(d2)]
+    else:
+        counts, idx, d2 = _within_host(hP, hQ, own, radius, r2, False)
+        cols = [np.concatenate([np.zeros(1, np.int64), np.cumsum(counts, dtype=np.int64)]), idx, np.sqrt(d2)]
+    if as_tensors:
+        import torch
+        where = points.device if is_t else torch.device("cpu")
         cols = [torch.as_tensor(np.ascontiguousarray(c), device=where) for c in cols]
     return dict(zip(names, cols))

@@ -129,6 +129,8 @@ SIGNATURES = {
     "sd_label_border_flags_device": (_i, [_vp, _i, _i, _i, _i, _i, _vp, ctypes.c_longlong, _vp, _vp]),
     "sd_label_clear_flagged_device": (_i, [_vp, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _i, _vp, _vp]),
     "sd_label_contacts_device": (_i, [_vp, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sd_point_neighbors_device": (_i, [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double,
+                                       ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sd_augment_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "sd_star_dist2d_points_device": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "sd_star_dist3d_points_device": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _vp, _vp]),

@@ -603,4 +603,4 @@ def optimize_threshold(Y, Yhat, model, nms_thresh, measure="accuracy", iou_thres
 # the label-image functions with a host and a device route live in stardist_amd.label_ops; their public names stay importable from here
 from .label_ops import (clear_border, find_boundaries, remove_small_objects, select_labels,  # noqa: E402, F401
                         calculate_extents, distance_transform, expand_labels, fill_label_holes, label_components,
-                        label_contacts, measure_labels)
+                        label_contacts, measure_labels, point_neighbors)

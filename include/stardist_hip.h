@@ -873,6 +873,43 @@ int sd_point_neighbors_device(const double* d_points, long long n, const double*
                               int use_radius, double r2, double cell_size, long long cap, int64_t* d_indices, double* d_d2,
                               int64_t* d_offsets, long long* h_total, double* h_cell, void* stream);
 
+/* Spot detection (stardist_amd.spots; the per-element rules are csrc/spots.h's).  An image is nd = 2 or 3 axes of
+ * extents n0, n1, n2 (n0 = 1 for nd = 2), at most 2^32 - 1 pixels, dtype 0 uint8, 1 uint16, 2 float32; it is never written.
+ *
+ * sd_gaussian_filter_device: scipy.ndimage.gaussian_filter(img, output=float32, mode="reflect") bit for bit (NaN positions; not their
+ * payload).  h_radius (host, 3 ints, z y x): the window's radius per axis, < 0 for an axis that is skipped, at most 512.  d_weights:
+ * the float64 tables of the axes that are not skipped, one after the other in axis order, 2 r + 1 entries each, w[r] the centre.  One
+ * output element of a line: tmp = in[l] w[r]; for j = r .. 1: tmp += (in[l - j] + in[l + j]) w[r - j], in double, every operation
+ * rounded, indices reflected with period 2 n; stored as float.  Axes in the order 0, 1, 2; between axes the image is float32.  d_out
+ * receives the result, d_work (as large; needed for two or three passes) is scratch.  With every axis skipped d_out is the cast.
+ * A pass along the last axis keeps its tile and halo in LDS always, a pass along another axis up to r = 80 and reads global memory
+ * beyond.  No read-back, no synchronisation.
+ *
+ * sd_peak_local_max_device: the peaks of stardist_amd.spots.peak_local_max's definition.  h_distance (host, 3 ints): min_distance per
+ * axis, 0 .. 2^20; h_border (host, 3 long long): the border width per axis, >= 0.  d_labels: int32 like the image, or NULL.  The
+ * threshold is threshold_abs if has_abs else the least non-NaN value, raised to fl64(threshold_rel * greatest non-NaN value) if
+ * has_rel; it is computed and read on the device.  per_label < 0: no per-label cap (it needs d_labels); num_peaks < 0: no cap.
+ * d_keys (cap entries) receives the keys ((~value key) << 32 | raster index), ascending, which is (-value, index) ascending;
+ * h_count[0] (host) the number of peaks found before the cuts, h_count[1] the number of keys that are the result, or -1 if
+ * h_count[0] > cap: nothing is delivered then, and the caller comes again with room for all.  The halo of a tile lives in LDS while
+ * (t0 + 2 d0) (t1 + 2 d1) (64 + 2 d2) floats fit in 48 KiB (tiles 1 x 16 x 64, 3D 4 x 4 x 64: d <= 36 for a 2D image and one d),
+ * beyond that the window is read from global memory.  Synchronises the stream once for h_count[0] and, with a per-label cap, once
+ * more.  Integer atomics only: the same keys from call to call.
+ *
+ * sd_peaks_emit_device: for the first `count` keys, d_coords (count x nd int64), d_values (count, the image's dtype, the pixel's own
+ * bits) and d_out_labels (count int32; zeros without d_labels).  No synchronisation.
+ *
+ * All three return -1 before any launch for a null pointer, nd outside 2 .. 3, a dtype code outside 0 .. 2, an extent < 1, more
+ * than 2^32 - 1 pixels, a radius beyond 512 / a distance beyond 2^20, a negative border or a NaN threshold. */
+int sd_gaussian_filter_device(const void* d_in, int dtype, int nd, long long n0, long long n1, long long n2, const int* h_radius,
+                              const double* d_weights, float* d_out, float* d_work, void* stream);
+int sd_peak_local_max_device(const void* d_in, int dtype, int nd, long long n0, long long n1, long long n2, const int32_t* d_labels,
+                             const int* h_distance, const long long* h_border, int has_abs, double threshold_abs, int has_rel,
+                             double threshold_rel, long long per_label, long long num_peaks, long long cap, uint64_t* d_keys,
+                             long long* h_count, void* stream);
+int sd_peaks_emit_device(const void* d_in, int dtype, int nd, long long n0, long long n1, long long n2, const int32_t* d_labels,
+                         const uint64_t* d_keys, long long count, int64_t* d_coords, void* d_values, int32_t* d_out_labels, void* stream);
+
 /* The augmentation chain of a training batch (stardist_amd.augment.Compose.apply_device; the rules are csrc/augment.h's) in ONE launch:
  * d_x (B, *shape) float32 and d_y (B, *shape) int32, nd = 2 or 3 extents in h_shape, give d_out_x and d_out_y of the same shapes
  * (not the inputs): per sample FlipRot90 (always, as an index map), then Warp (flags bit 0; bit 1: mode 'reflect', else 'constant'),

@@ -669,8 +669,46 @@ def _proximity_columns(label, csum, area, k, radius, r2, per_axis):
     return cols
 
 
+def _spot_coords(spots, nd):
+    """measure_labels' spots= as an (n, nd) integer array or tensor, checked"""
+    if not R.is_torch(spots):
+        spots = np.asarray(spots)
+        if spots.size == 0 and spots.ndim == 2 and spots.shape[1] == nd:
+            spots = spots.astype(np.int64)
+    integer = (not spots.dtype.is_floating_point and str(spots.dtype) != "torch.bool") if R.is_torch(spots) else spots.dtype.kind in "iu"
+    if len(spots.shape) != 2 or int(spots.shape[1]) != nd or not integer:
+        raise ValueError("measure_labels: spots must be (n, %d) integer coordinates, got shape %r of %s" % (nd, tuple(spots.shape), spots.dtype))
+    return spots
+
+
+def _spot_counts(label, lbl, coords):
+    """the spot_count column: for every row of the label column `label` (ascending ids) the number of rows of `coords` whose pixel of
+    the label image `lbl` carries that id -- gather, search in the label column, bincount; numpy arrays, or tensors on one device"""
+    if R.is_torch(label):
+        import torch
+        c = coords.to(device=label.device, dtype=torch.int64)
+        extent = torch.as_tensor([int(n) for n in lbl.shape], dtype=torch.int64, device=label.device)
+        if c.numel() and bool(((c < 0) | (c >= extent)).any()):
+            raise ValueError("measure_labels: a coordinate of spots lies outside the image")
+        ids = lbl[tuple(c.t())].to(torch.int64) if lbl.dtype != torch.uint16 else lbl.to(torch.int32)[tuple(c.t())].to(torch.int64)
+        if not len(label):
+            return torch.zeros(0, dtype=torch.int64, device=label.device)
+        at = torch.searchsorted(label, ids).clamp(max=len(label) - 1)
+        hit = (ids > 0) & (label[at] == ids)
+        return torch.bincount(at[hit], minlength=len(label))
+    c = coords.astype(np.int64)
+    if c.size and ((c < 0) | (c >= np.asarray(lbl.shape, np.int64))).any():
+        raise ValueError("measure_labels: a coordinate of spots lies outside the image")
+    ids = lbl[tuple(c.T)].astype(np.int64)
+    if not len(label):
+        return np.zeros(0, np.int64)
+    at = np.minimum(np.searchsorted(label, ids), len(label) - 1)
+    hit = (ids > 0) & (label[at] == ids)
+    return np.bincount(at[hit], minlength=len(label)).astype(np.int64)
+
+
 def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, neighbors=None, nearest=None, within=None, spacing=1,
-                   device=None, as_tensors=False):
+                   spots=None, device=None, as_tensors=False):
     """Per-object table of a 2D / 3D integer label image (values <= 0 are background) and, optionally, of the image `img` that was
     segmented: shape lbl.shape or lbl.shape + (C,) (channels last).  Returns a dict of 1-D columns, one row per label present,
     ascending by label, named as scikit-image 0.18's regionprops_table names them:
@@ -718,6 +756,11 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
       point_neighbors(centroids, radius=r, spacing=spacing, count_only=True) over the table's own centroid columns; on the device
       route the centroids stay on the device (the read-backs of point_neighbors' device route apply: the box of the points, once per
       keyword) and the new columns come to the host in one more small copy.
+      with spots=coords ((n, ndim) integer coordinates, numpy or tensor: peak_local_max's), after every column above:
+        spot_count             int64    the number of rows of coords whose pixel carries the object's label
+      Rows on the background count for nobody, a coordinate given twice counts twice; a coordinate outside the image raises
+      ValueError.  On the device route the column is made there by tensor operations (gather, search, bincount), one flag comes to
+      the host for that check, and the column comes to the host in one more small copy.
 
     The shape columns are scikit-image 0.18's regionprops_table columns of these names, computed from integer tables per object
     (second-order coordinate sums, three counts of contour-pixel classes, a histogram of 2 x 2 pixel configurations: DESIGN.md section
@@ -779,6 +822,8 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
         neighbors = _contacts_connectivity(neighbors, nd, "measure_labels: neighbors")
     near_k, near_r, near_r2, near_spacing = _proximity_args(nearest, within, spacing, nd)
     near_names = _proximity_names(near_k, near_r)
+    if spots is not None:
+        spots = _spot_coords(spots, nd)
     more = {"shape": True} if shape else {}                                 # without shape / percentiles the two halves are called as before
     if qs:
         more["percentiles"] = qs
@@ -792,10 +837,16 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
         if neighbors is not None:                                          # on the device, from the edge table there
             near = _neighbor_columns(raw["label"], *_label_contacts_device(lbl, neighbors, True, device))
         close = _proximity_columns(raw["label"], raw["csum"], raw["area"], near_k, near_r, near_r2, near_spacing) if near_names else []
+        spot = None
+        if spots is not None:
+            where = raw["label"].device
+            spot = _spot_counts(raw["label"], R.to_device_tensor(lbl, where), R.to_device_tensor(spots, where))
         if as_tensors:
             out = _measure_columns(raw, nd, channel_axis, qs)
             out.update(zip(_NEIGHBOR_NAMES, near or ()))
             out.update(zip(near_names, close))
+            if spot is not None:
+                out["spot_count"] = spot
             return out
         from .utils import to_host
         sum_dtype, mm_dtype = (str(raw["sum"].dtype)[6:], str(raw["min"].dtype)[6:]) if img is not None else (None, None)
@@ -812,16 +863,21 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
             back = to_host(torch.stack([c.view(torch.int64) if c.dtype.is_floating_point else c for c in close]))      # one small copy
             out.update((name, np.ascontiguousarray(back[j]).view(np.float64 if "distance" in name else np.int64))
                        for j, name in enumerate(near_names))
+        if spot is not None:
+            out["spot_count"] = to_host(spot)
         return out
     host_lbl = lbl.cpu().numpy() if lbl_t else lbl
     raw = _measure_raw_host(host_lbl, img.cpu().numpy() if img_t else img, **more)
     contacts = None if neighbors is None else _label_contacts_host(host_lbl, neighbors, True)
+    spot = None if spots is None else _spot_counts(raw["label"], host_lbl, spots.cpu().numpy() if R.is_torch(spots) else spots)
     if not as_tensors:
         out = _measure_columns(raw, nd, channel_axis, qs)
         if contacts is not None:
             out.update(zip(_NEIGHBOR_NAMES, _neighbor_columns(out["label"], *contacts)))
         if near_names:
             out.update(zip(near_names, _proximity_columns(raw["label"], raw["csum"], raw["area"], near_k, near_r, near_r2, near_spacing)))
+        if spot is not None:
+            out["spot_count"] = spot
         return out
     # the host table as tensors where the labels are (or on `device`): the packed raw columns make the trip
     import torch
@@ -841,6 +897,8 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
     if near_names:
         close = _proximity_columns(raw["label"], raw["csum"], raw["area"], near_k, near_r, near_r2, near_spacing)
         out.update((name, torch.as_tensor(c, device=where)) for name, c in zip(near_names, close))
+    if spot is not None:
+        out["spot_count"] = torch.as_tensor(spot, device=where)
     return out
 
 

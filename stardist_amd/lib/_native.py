@@ -131,6 +131,10 @@ SIGNATURES = {
     "sd_label_contacts_device": (_i, [_vp, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sd_point_neighbors_device": (_i, [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sd_gaussian_filter_device": (_i, [_vp, _i, _i] + [ctypes.c_longlong] * 3 + [_vp, _vp, _vp, _vp, _vp]),
+    "sd_peak_local_max_device": (_i, [_vp, _i, _i] + [ctypes.c_longlong] * 3 + [_vp, _vp, _vp, _i, ctypes.c_double, _i, ctypes.c_double]
+                                 + [ctypes.c_longlong] * 3 + [_vp, _vp, _vp]),
+    "sd_peaks_emit_device": (_i, [_vp, _i, _i] + [ctypes.c_longlong] * 3 + [_vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp]),
     "sd_augment_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "sd_star_dist2d_points_device": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "sd_star_dist3d_points_device": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _vp, _vp]),

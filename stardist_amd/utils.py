@@ -604,3 +604,4 @@ def optimize_threshold(Y, Yhat, model, nms_thresh, measure="accuracy", iou_thres
 from .label_ops import (clear_border, find_boundaries, remove_small_objects, select_labels,  # noqa: E402, F401
                         calculate_extents, distance_transform, expand_labels, fill_label_holes, label_components,
                         label_contacts, measure_labels, point_neighbors)
+from .spots import gaussian_filter, difference_of_gaussians, peak_local_max, detect_spots  # noqa: E402, F401

@@ -2,6 +2,7 @@
 normalisation and zoom in stardist_amd.utils): what an input is, where a call runs, how an input gets to the device and how a result comes
 back like the input.  DESIGN.md section 3p states the rule and the functions' exceptions."""
 import math
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -26,6 +27,73 @@ def classify(x, device=None):
     if not is_t:
         x = np.asarray(x)
     return x, is_t, device is not None or (is_t and x.is_cuda)
+
+
+def dtype_name(x):
+    """the name of x's dtype, the same for an array and a tensor: "int64", "float32" """
+    return str(x.dtype).replace("torch.", "")
+
+
+def _tensor_sqrt(a):
+    """the correctly rounded square root of a tensor: torch's on the device; numpy's for a host tensor, where torch's goes through a
+    vector maths library that on some CPUs is an ulp off, so that host tensors and numpy arrays give the same bits"""
+    import torch
+    return torch.sqrt(a) if a.is_cuda else torch.from_numpy(np.sqrt(a.contiguous().numpy()))
+
+
+_NUMPY_OPS = SimpleNamespace(
+    xp=np, is_torch=False, int64=np.dtype("int64"), float64=np.dtype("float64"), astype=lambda a, name: a.astype(name),
+    f64=lambda a: np.asarray(a).astype(np.float64), i64=lambda a: np.asarray(a).astype(np.int64),
+    col=np.ascontiguousarray, sqrt=np.sqrt, atan2=np.arctan2, cat=lambda arrays, axis=0: np.concatenate(arrays, axis=axis),
+    searchsorted=np.searchsorted, zeros_i64=lambda n: np.zeros(n, np.int64), add_at=lambda out, at, v: np.add.at(out, at, v),
+    stable_argsort=lambda k: np.argsort(k, kind="stable"), bincount=lambda at, n: np.bincount(at, minlength=n).astype(np.int64),
+    clip_max=lambda a, top: np.minimum(a, top))
+
+
+def _torch_ops(dev):
+    import torch
+    as_kind = lambda dtype: lambda a: a.to(dev, dtype) if torch.is_tensor(a) else torch.as_tensor(a, dtype=dtype, device=dev)
+    return SimpleNamespace(
+        xp=torch, is_torch=True, int64=torch.int64, float64=torch.float64, astype=lambda a, name: a.to(getattr(torch, name)),
+        f64=as_kind(torch.float64), i64=as_kind(torch.int64),
+        col=lambda a: a.contiguous(), sqrt=_tensor_sqrt, atan2=torch.atan2, cat=lambda tensors, axis=0: torch.cat(tensors, dim=axis),
+        searchsorted=torch.searchsorted, zeros_i64=lambda n: torch.zeros(n, dtype=torch.int64, device=dev),
+        add_at=lambda out, at, v: out.index_add_(0, at, v), stable_argsort=lambda k: torch.sort(k, stable=True)[1],
+        bincount=lambda at, n: torch.bincount(at, minlength=n), clip_max=lambda a, top: a.clamp(max=top))
+
+
+_TORCH_OPS = {}                                                             # per device, made once
+
+
+def ops(x):
+    """The operations that the table functions apply to numpy arrays and to tensors alike, for arrays of x's kind (tensors: on x's
+    device).  The routes agree to the bit because each name is one numpy call and the one torch call that computes the same:
+    xp (the module, for where / abs / maximum / minimum / ones_like), int64 and float64 (the dtypes), astype(a, name), f64(a) and
+    i64(a) (of an array or a sequence), col(a) (contiguous), sqrt (_tensor_sqrt), atan2, cat(arrays, axis), searchsorted, zeros_i64(n), add_at(out, at, v) (in
+    place, duplicates add up), stable_argsort, bincount(at, n) (int64, n long), clip_max(a, top)."""
+    if not is_torch(x):
+        return _NUMPY_OPS
+    o = _TORCH_OPS.get(x.device)
+    if o is None:
+        o = _TORCH_OPS[x.device] = _torch_ops(x.device)
+    return o
+
+
+def table_exit(cols, as_tensors, x=None, device=None):
+    """A route's finished columns as the caller asked for them (exception 4): numpy arrays whatever the input's
+    kind, tensors with as_tensors.  The device route's tensors become numpy arrays with one stream synchronisation for all of them
+    (utils.to_host_many); the host route's arrays become tensors on `device` if given, else where the input x lives if it is a
+    tensor, else on the CPU; in every other case the columns pass through.  A None among the columns stays None."""
+    cols = list(cols)
+    from_device_route = any(is_torch(c) for c in cols)
+    if from_device_route and not as_tensors:
+        from .utils import to_host_many
+        return to_host_many(cols)
+    if as_tensors and not from_device_route:
+        import torch
+        where = torch.device(device) if device is not None else (x.device if is_torch(x) else torch.device("cpu"))
+        return [None if c is None else torch.as_tensor(np.ascontiguousarray(c), device=where) for c in cols]
+    return cols
 
 
 def opt_ptr(t):

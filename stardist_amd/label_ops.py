@@ -110,14 +110,13 @@ def calculate_extents(lbl, func=np.median):
 
 
 # ----------------------------------------------------------------------------- measure_labels: the per-object table
-# Both routes produce the same "raw" columns -- label (n,), area (n,), bbox (n, 2 nd), csum (n, nd) coordinate sums, all int64, and with
-# an image sum, sum2 (n, C) int64 / float64 and min, max (n, C) int64 / the image's float type -- as numpy arrays or as tensors;
-# _measure_columns derives the table from them, the one place where centroid, mean and std are computed.  With shape=True both routes add
-# m2 (n, 6), the second-order sums of the box-local coordinates in the order zz, zy, zx, yy, yx, xx, and for a 2D image contour (n, 18) =
-# [n_1, n_r2, n_h, h_1 .. h_15], the contour-pixel classes and the 2 x 2 configuration histogram (csrc/measure_shape.h), all int64;
-# _shape_columns derives the shape columns from them.  With hull=True both routes add hull (n, 2) = [convex_area, F2],
-# int64 (csrc/measure_hull.h); _hull_columns derives the hull columns from it.
-_MEASURE_RAW = ("label", "area", "bbox", "csum", "sum", "sum2", "min", "max", "m2", "contour", "hull")
+# Both routes produce the same "raw" columns, as numpy arrays or as tensors: _measure_schema states their keys, widths and dtypes, once,
+# for the host half's allocations, the device half's empty table and the packed form in which a table travels (_measure_pack,
+# _measure_unpack).  _measure_columns derives the table from them, the one place where centroid, mean and std are computed.  csum holds
+# the coordinate sums; m2 the second-order sums of the box-local coordinates in the order zz, zy, zx, yy, yx, xx and, for a 2D image,
+# contour = [n_1, n_r2, n_h, h_1 .. h_15], the contour-pixel classes and the 2 x 2 configuration histogram (csrc/measure_shape.h), from
+# which _shape_columns derives the shape columns; hull = [convex_area, F2] (csrc/measure_hull.h), from which
+# _hull_columns derives the hull columns.
 # With percentiles both routes add pct (n, C, n_q): float64 for integer images, else the image's float type.  It is no part of the packed
 # table: it travels as an array of its own.  _MAX_PERCENTILES is csrc/measure_rank.h's MR_MAX_Q.
 _MAX_PERCENTILES = 8
@@ -152,58 +151,52 @@ def _measure_shapes(lbl_shape, img_shape):
                      % (tuple(img_shape), tuple(lbl_shape)))
 
 
-def _measure_pack(raw):
-    """the raw columns side by side as one (n, K) int64 array / tensor (floats as the bits of their float64 value): one copy moves it"""
-    wide = [raw[key] if raw[key].ndim == 2 else raw[key].reshape(raw[key].shape[0], 1) for key in _MEASURE_RAW if key in raw]
-    if R.is_torch(raw["label"]):
-        import torch
-        return torch.cat([a.to(torch.float64).contiguous().view(torch.int64) if a.dtype.is_floating_point else a.to(torch.int64)
-                          for a in wide], dim=1).contiguous()
-    return np.ascontiguousarray(np.concatenate([np.ascontiguousarray(a, np.float64).view(np.int64) if a.dtype.kind == "f"
-                                                else a.astype(np.int64) for a in wide], axis=1))
-
-
-def _measure_unpack(packed, nd, C, sum_dtype, mm_dtype, shape=False, hull=False):
-    """the raw columns of _measure_pack's array; sum_dtype / mm_dtype: the names of the dtypes of sum, sum2 and of min, max"""
-    is_t = R.is_torch(packed)
-    widths = [("label", 1, "int64"), ("area", 1, "int64"), ("bbox", 2 * nd, "int64"), ("csum", nd, "int64")]
+def _measure_schema(nd, C, mm_dtype, shape=False, hull=False):
+    """[(key, width, dtype name)] of the raw columns, in their order: a column is (n, width), or (n,) where the width is None.  C: the
+    number of channels, None without an image; mm_dtype: the name of the dtype of min and max -- the image's for a float image, for
+    which sum and sum2 are float64, else int64 like everything else"""
+    cols = [("label", None, "int64"), ("area", None, "int64"), ("bbox", 2 * nd, "int64"), ("csum", nd, "int64")]
     if C is not None:
-        widths += [("sum", C, sum_dtype), ("sum2", C, sum_dtype), ("min", C, mm_dtype), ("max", C, mm_dtype)]
+        sum_dtype = "float64" if "float" in mm_dtype else "int64"
+        cols += [("sum", C, sum_dtype), ("sum2", C, sum_dtype), ("min", C, mm_dtype), ("max", C, mm_dtype)]
     if shape:
-        widths += [("m2", 6, "int64")] + ([("contour", _CONTOUR_WIDTH, "int64")] if nd == 2 else [])
+        cols += [("m2", 6, "int64")] + ([("contour", _CONTOUR_WIDTH, "int64")] if nd == 2 else [])
     if hull:
-        widths += [("hull", 2, "int64")]
-    raw, at = {}, 0
-    for key, w, dt in widths:
-        a = packed[:, at:at + w]
-        at += w
-        if is_t:
-            import torch
-            a = a.contiguous()
-            a = a.view(torch.float64).to(getattr(torch, dt)) if dt.startswith("float") else a
-        else:
-            a = np.ascontiguousarray(a)
-            a = a.view(np.float64).astype(dt) if dt.startswith("float") else a
-        raw[key] = a.reshape(-1) if key in ("label", "area") else a
+        cols += [("hull", 2, "int64")]
+    return cols
+
+
+def _as_bits(o, a):
+    """int64 as it is, a float array / tensor as the bits of its float64 value (o: R.ops of a)"""
+    return o.col(o.f64(a)).view(o.int64) if "float" in str(a.dtype) else o.i64(a)
+
+
+def _from_bits(o, a, dtype):
+    return o.astype(o.col(a).view(o.float64), dtype) if "float" in dtype else o.col(a)
+
+
+def _measure_pack(raw, schema):
+    """the raw columns side by side as one (n, K) int64 array / tensor (_as_bits): one copy moves it"""
+    o = R.ops(raw["label"])
+    return o.col(o.cat([_as_bits(o, raw[key] if w else raw[key].reshape(-1, 1)) for key, w, _ in schema], 1))
+
+
+def _measure_unpack(packed, schema):
+    """the raw columns of _measure_pack's array"""
+    o, raw, at = R.ops(packed), {}, 0
+    for key, w, dtype in schema:
+        a = _from_bits(o, packed[:, at:at + (w or 1)], dtype)
+        at += w or 1
+        raw[key] = a.reshape(-1) if w is None else a
     return raw
-
-
-def _tensor_sqrt(a):
-    """the correctly rounded square root of a tensor: torch's on the device; numpy's for a host tensor, where torch's goes through a
-    vector maths library that on some CPUs is an ulp off, so that host tensors and numpy arrays give the same bits"""
-    import torch
-    return torch.sqrt(a) if a.is_cuda else torch.from_numpy(np.sqrt(a.contiguous().numpy()))
 
 
 def _measure_columns(raw, nd, channel_axis, qs=None):
     """the table of measure_labels from the raw columns (numpy arrays or tensors): centroid = float64(coordinate sum) / count, mean =
     float64(sum) / count, var = max(0, float64(sum2) / count - mean^2), std = sqrt(var), every operation rounded on its own; qs: the
     percentiles of raw["pct"] (n, C, len(qs)), whose columns come after the intensity columns"""
-    if R.is_torch(raw["label"]):
-        import torch
-        f64, sqrt, col = (lambda a: a.to(torch.float64)), _tensor_sqrt, (lambda a: a.contiguous())
-    else:
-        f64, sqrt, col = (lambda a: a.astype(np.float64)), np.sqrt, np.ascontiguousarray
+    o = R.ops(raw["label"])
+    f64, sqrt, col = o.f64, o.sqrt, o.col
     out = {"label": raw["label"], "area": raw["area"]}
     for k in range(2 * nd):
         out["bbox-%d" % k] = col(raw["bbox"][:, k])
@@ -235,10 +228,11 @@ def _measure_columns(raw, nd, channel_axis, qs=None):
     return out
 
 
-def _jacobi_eigvals(T, xp, sqrt):
+def _jacobi_eigvals(T, o):
     """eigenvalues of the symmetric matrices T[i][j] (arrays / tensors of one length), unsorted: _JACOBI_SWEEPS cyclic Jacobi sweeps of
-    + - * / sqrt, comparisons and selects, the same code for numpy and torch (xp, sqrt).  A zero off-diagonal element is left alone; an
-    angle whose square would overflow takes its limit t = 1 / (2 theta)."""
+    + - * / sqrt, comparisons and selects, the same code for numpy and torch (o: their R.ops).  A zero off-diagonal element is left
+    alone; an angle whose square would overflow takes its limit t = 1 / (2 theta)."""
+    xp, sqrt = o.xp, o.sqrt
     n = len(T)
     T = [list(row) for row in T]
     for _ in range(_JACOBI_SWEEPS):
@@ -268,12 +262,8 @@ def _shape_columns(out, raw, nd):
     """adds the shape columns to the table `out` from the raw columns (numpy arrays or tensors), DESIGN.md section 3q: every operation
     is rounded on its own, in the order written there; only orientation (atan2) and the 3D equivalent_diameter (pow) call a maths
     library, everything else is + - * / sqrt, comparisons and selects and so has the same bits on every route"""
-    if R.is_torch(raw["label"]):
-        import torch as xp
-        f64, col, atan2, sqrt = (lambda a: a.to(xp.float64)), (lambda a: a.contiguous()), xp.atan2, _tensor_sqrt
-    else:
-        xp = np
-        f64, col, atan2, sqrt = (lambda a: a.astype(np.float64)), np.ascontiguousarray, np.arctan2, np.sqrt
+    o = R.ops(raw["label"])
+    xp, f64, col, atan2, sqrt = o.xp, o.f64, o.col, o.atan2, o.sqrt
     with np.errstate(all="ignore"):
         area = raw["area"]
         A = f64(area)
@@ -285,7 +275,7 @@ def _shape_columns(out, raw, nd):
         for d in range(1, nd):
             tr = tr + mu[(d, d)]
         T = [[((tr - mu[(i, i)]) / A) if i == j else (-mu[(min(i, j), max(i, j))] / A) for j in range(nd)] for i in range(nd)]
-        lam = [xp.where(l > 0, l, 0.0 * l) for l in _jacobi_eigvals(T, xp, sqrt)]
+        lam = [xp.where(l > 0, l, 0.0 * l) for l in _jacobi_eigvals(T, o)]
         # descending by a sorting network of maxima and minima
         for i, j in (((0, 1),) if nd == 2 else ((0, 1), (1, 2), (0, 1))):
             lam[i], lam[j] = xp.maximum(lam[i], lam[j]), xp.minimum(lam[i], lam[j])
@@ -322,11 +312,8 @@ def _shape_columns(out, raw, nd):
 def _hull_columns(out, raw):
     """adds the hull columns to the table `out` from the raw columns (numpy arrays or tensors), DESIGN.md section 3u: convex_area as it
     is, solidity = float64(area) / float64(convex_area), feret_diameter_max = sqrt(float64(F2) / 4), every operation rounded on its own"""
-    if R.is_torch(raw["label"]):
-        import torch
-        f64, col, sqrt = (lambda a: a.to(torch.float64)), (lambda a: a.contiguous()), _tensor_sqrt
-    else:
-        f64, col, sqrt = (lambda a: a.astype(np.float64)), np.ascontiguousarray, np.sqrt
+    o = R.ops(raw["label"])
+    f64, col, sqrt = o.f64, o.col, o.sqrt
     convex = col(raw["hull"][:, 0])
     f2 = f64(raw["hull"][:, 1])
     out["convex_area"] = convex
@@ -505,17 +492,14 @@ def _measure_raw_host(lbl, img, shape=False, percentiles=None, hull=False):
         lab = np.maximum(lbl, 0) if lbl.dtype.kind != "u" else lbl
     boxes = _object_boxes(lab) if lab.size else []
     n = len(boxes)
-    raw = {"label": np.array([k for k, _ in boxes], np.int64).reshape(n), "area": np.zeros(n, np.int64),
-           "bbox": np.zeros((n, 2 * nd), np.int64), "csum": np.zeros((n, nd), np.int64)}
+    C = None if img is None else 1 if img.ndim == nd else img.shape[-1]
+    exact = img is not None and img.dtype.kind in "iub"
+    raw = {key: np.zeros((n,) if w is None else (n, w), dtype)              # (m2, contour and hull come whole from their functions)
+           for key, w, dtype in _measure_schema(nd, C, None if img is None else "int64" if exact else img.dtype.name)}
+    raw["label"] = np.array([k for k, _ in boxes], np.int64).reshape(n)
     if ids is not None:
         raw["label"] = ids.astype(np.int64)[raw["label"] - 1]
     if img is not None:
-        C = 1 if img.ndim == nd else img.shape[-1]
-        exact = img.dtype.kind in "iub"
-        raw["sum"] = np.zeros((n, C), np.int64 if exact else np.float64)
-        raw["sum2"] = np.zeros((n, C), np.int64 if exact else np.float64)
-        raw["min"] = np.zeros((n, C), np.int64 if exact else img.dtype)
-        raw["max"] = np.zeros((n, C), np.int64 if exact else img.dtype)
         if percentiles:
             if img.dtype.kind == "b":
                 img = img.astype(np.uint8)
@@ -568,20 +552,10 @@ def _measure_raw_device(lbl, img, C, device, shape=False, percentiles=None, hull
     sum_t, mm_t = (torch.float64, torch.float32) if code == 2 else (torch.int64, torch.int32)
     pct_t = torch.float32 if code == 2 else torch.float64
     if lab.numel() == 0 or top <= 0:
-        raw = {"label": torch.zeros(0, dtype=torch.int64, device=dev), "area": torch.zeros(0, dtype=torch.int64, device=dev),
-               "bbox": torch.zeros((0, 2 * nd), dtype=torch.int64, device=dev), "csum": torch.zeros((0, nd), dtype=torch.int64, device=dev)}
-        if img is not None:
-            raw.update(sum=torch.zeros((0, C), dtype=sum_t, device=dev), sum2=torch.zeros((0, C), dtype=sum_t, device=dev),
-                       min=torch.zeros((0, C), dtype=torch.float32 if code == 2 else torch.int64, device=dev),
-                       max=torch.zeros((0, C), dtype=torch.float32 if code == 2 else torch.int64, device=dev))
+        schema = _measure_schema(nd, C, "float32" if code == 2 else "int64", shape, hull)
+        raw = {key: torch.zeros((0,) if w is None else (0, w), dtype=getattr(torch, dtype), device=dev) for key, w, dtype in schema}
         if percentiles:
             raw["pct"] = torch.zeros((0, C, len(percentiles)), dtype=pct_t, device=dev)
-        if shape:
-            raw["m2"] = torch.zeros((0, 6), dtype=torch.int64, device=dev)
-            if nd == 2:
-                raw["contour"] = torch.zeros((0, _CONTOUR_WIDTH), dtype=torch.int64, device=dev)
-        if hull:
-            raw["hull"] = torch.zeros((0, 2), dtype=torch.int64, device=dev)
         return raw
     boxes, sums = R.label_tables(lab, top, boxes=True, sums=True)
     if img is not None:
@@ -644,28 +618,17 @@ def _proximity_columns(label, csum, area, k, radius, r2, per_axis):
     """the columns of _proximity_names from the objects' labels, coordinate sums and pixel counts (numpy arrays, or tensors on the
     device): point_neighbors over the centroids float64(sum) / count times the spacing, the points their own queries; an index becomes
     the label of that row, 0 where there is none"""
+    o = R.ops(label)
+    P = o.col(o.f64(csum) / o.f64(area)[:, None] * o.f64(per_axis))
     cols = []
-    if R.is_torch(label):
-        import torch
-        P = (csum.to(torch.float64) / area.to(torch.float64)[:, None] * torch.as_tensor(per_axis, dtype=torch.float64, device=label.device)).contiguous()
-        if k is not None:
-            idx, d2 = _point_neighbors_device(P, None, 0, k, None)
-            lab = torch.where(idx >= 0, label[idx.clamp(min=0)] if len(label) else idx, torch.zeros_like(idx))
-            dist = _tensor_sqrt(d2)
-            for j in range(k):
-                cols += [lab[:, j].contiguous(), dist[:, j].contiguous()]
-        if radius is not None:
-            cols.append(_point_neighbors_device(P, None, 1, None, r2))
-        return cols
-    P = csum.astype(np.float64) / area.astype(np.float64)[:, None] * np.asarray(per_axis, np.float64)
     if k is not None:
-        idx, d2 = _nearest_host(P, P, True, k, None)
-        lab = np.where(idx >= 0, label[np.maximum(idx, 0)] if len(label) else idx, 0).astype(np.int64)
-        dist = np.sqrt(d2)
+        idx, d2 = _point_neighbors_device(P, None, 0, k, None) if o.is_torch else _nearest_host(P, P, True, k, None)
+        lab = o.xp.where(idx >= 0, label[idx.clip(min=0)] if len(label) else idx, 0 * idx)
+        dist = o.sqrt(d2)
         for j in range(k):
-            cols += [np.ascontiguousarray(lab[:, j]), np.ascontiguousarray(dist[:, j])]
+            cols += [o.col(lab[:, j]), o.col(dist[:, j])]
     if radius is not None:
-        cols.append(_within_host(P, P, True, radius, r2, True)[0])
+        cols.append(_point_neighbors_device(P, None, 1, None, r2) if o.is_torch else _within_host(P, P, True, radius, r2, True)[0])
     return cols
 
 
@@ -684,27 +647,18 @@ def _spot_coords(spots, nd):
 def _spot_counts(label, lbl, coords):
     """the spot_count column: for every row of the label column `label` (ascending ids) the number of rows of `coords` whose pixel of
     the label image `lbl` carries that id -- gather, search in the label column, bincount; numpy arrays, or tensors on one device"""
-    if R.is_torch(label):
-        import torch
-        c = coords.to(device=label.device, dtype=torch.int64)
-        extent = torch.as_tensor([int(n) for n in lbl.shape], dtype=torch.int64, device=label.device)
-        if c.numel() and bool(((c < 0) | (c >= extent)).any()):
-            raise ValueError("measure_labels: a coordinate of spots lies outside the image")
-        ids = lbl[tuple(c.t())].to(torch.int64) if lbl.dtype != torch.uint16 else lbl.to(torch.int32)[tuple(c.t())].to(torch.int64)
-        if not len(label):
-            return torch.zeros(0, dtype=torch.int64, device=label.device)
-        at = torch.searchsorted(label, ids).clamp(max=len(label) - 1)
-        hit = (ids > 0) & (label[at] == ids)
-        return torch.bincount(at[hit], minlength=len(label))
-    c = coords.astype(np.int64)
-    if c.size and ((c < 0) | (c >= np.asarray(lbl.shape, np.int64))).any():
+    o = R.ops(label)
+    c = o.i64(coords)
+    if len(c) and bool(((c < 0) | (c >= o.i64([int(n) for n in lbl.shape]))).any()):
         raise ValueError("measure_labels: a coordinate of spots lies outside the image")
-    ids = lbl[tuple(c.T)].astype(np.int64)
+    if R.dtype_name(lbl) == "uint16" and o.is_torch:                        # (torch does not index a uint16 tensor)
+        lbl = o.astype(lbl, "int32")
+    ids = o.i64(lbl[tuple(c.T)])
     if not len(label):
-        return np.zeros(0, np.int64)
-    at = np.minimum(np.searchsorted(label, ids), len(label) - 1)
+        return o.zeros_i64(0)
+    at = o.clip_max(o.searchsorted(label, ids), len(label) - 1)
     hit = (ids > 0) & (label[at] == ids)
-    return np.bincount(at[hit], minlength=len(label)).astype(np.int64)
+    return o.bincount(at[hit], len(label))
 
 
 def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, neighbors=None, nearest=None, within=None, spacing=1,
@@ -755,12 +709,12 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
       columns stay in pixels -- and raises ValueError without them.  The two are point_neighbors(centroids, k, spacing=spacing) and
       point_neighbors(centroids, radius=r, spacing=spacing, count_only=True) over the table's own centroid columns; on the device
       route the centroids stay on the device (the read-backs of point_neighbors' device route apply: the box of the points, once per
-      keyword) and the new columns come to the host in one more small copy.
+      keyword).
       with spots=coords ((n, ndim) integer coordinates, numpy or tensor: peak_local_max's), after every column above:
         spot_count             int64    the number of rows of coords whose pixel carries the object's label
       Rows on the background count for nobody, a coordinate given twice counts twice; a coordinate outside the image raises
       ValueError.  On the device route the column is made there by tensor operations (gather, search, bincount), one flag comes to
-      the host for that check, and the column comes to the host in one more small copy.
+      the host for that check.
 
     The shape columns are scikit-image 0.18's regionprops_table columns of these names, computed from integer tables per object
     (second-order coordinate sums, three counts of contour-pixel classes, a histogram of 2 x 2 pixel configurations: DESIGN.md section
@@ -798,9 +752,10 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
     written): its float64 sums are added in a fixed order without floating-point atomics, so they depend on (shape, lbl, img) alone --
     the same bits from call to call and from process to process -- and differ from the host's only by the order of the additions.  Any
     other dtype goes through the host code.  Ids beyond int32, or sparse huge ids, are compacted in ascending order for the call;
-    `label` reports the originals.  Its own (exception 4 there): the columns are numpy arrays whatever the input's kind, which the
-    device route reads back in one copy of the table; as_tensors=True makes them tensors, on the device for the device route (besides
-    what reading the largest label needs, one scalar comes to the host, the number of rows), else where the labels are or on `device`.
+    `label` reports the originals.  Its own (exception 4 there, R.table_exit): the columns are numpy arrays whatever the input's kind, which
+    the device route reads back with one synchronisation, whatever the keywords; as_tensors=True makes them tensors, on the device for the
+    device route (besides what reading the largest label needs, one scalar comes to the host, the number of rows), else where the labels
+    are or on `device`.
     A label image that is not 2D / 3D or an image of another shape raises ValueError before anything runs."""
     lbl, lbl_t, on_device = R.classify(lbl, device)
     img_t = img is not None and R.is_torch(img)
@@ -824,81 +779,38 @@ def measure_labels(lbl, img=None, *, shape=False, hull=False, percentiles=None, 
     near_names = _proximity_names(near_k, near_r)
     if spots is not None:
         spots = _spot_coords(spots, nd)
-    more = {"shape": True} if shape else {}                                 # without shape / percentiles the two halves are called as before
-    if qs:
-        more["percentiles"] = qs
-    if hull:
-        more["hull"] = True
+    # without shape / percentiles / hull the two halves are called as before
+    more = {key: value for key, value in (("shape", shape), ("percentiles", qs), ("hull", hull)) if value}
     lbl_ok = (str(lbl.dtype) in _DEVICE_LABEL_DTYPES) if lbl_t else (lbl.dtype.kind in "iu")
     img_ok = img is None or (str(img.dtype) if img_t else "torch." + img.dtype.name) in _DEVICE_DTYPE_CODE
     if on_device and lbl_ok and img_ok:
         raw = _measure_raw_device(lbl, img, C, device, **more)
-        near = None
-        if neighbors is not None:                                          # on the device, from the edge table there
-            near = _neighbor_columns(raw["label"], *_label_contacts_device(lbl, neighbors, True, device))
-        close = _proximity_columns(raw["label"], raw["csum"], raw["area"], near_k, near_r, near_r2, near_spacing) if near_names else []
-        spot = None
+        contacts = None if neighbors is None else _label_contacts_device(lbl, neighbors, True, device)    # the edge table, there
         if spots is not None:
-            where = raw["label"].device
-            spot = _spot_counts(raw["label"], R.to_device_tensor(lbl, where), R.to_device_tensor(spots, where))
-        if as_tensors:
-            out = _measure_columns(raw, nd, channel_axis, qs)
-            out.update(zip(_NEIGHBOR_NAMES, near or ()))
-            out.update(zip(near_names, close))
-            if spot is not None:
-                out["spot_count"] = spot
-            return out
-        from .utils import to_host
-        sum_dtype, mm_dtype = (str(raw["sum"].dtype)[6:], str(raw["min"].dtype)[6:]) if img is not None else (None, None)
-        back = _measure_unpack(to_host(_measure_pack(raw)), nd, C, sum_dtype, mm_dtype, shape, hull)
-        if qs:
-            back["pct"] = to_host(raw["pct"].contiguous())                  # a second, small copy: the packed table keeps its layout
-        out = _measure_columns(back, nd, channel_axis, qs)
-        if near is not None:
-            import torch
-            near = to_host(torch.stack(near))                               # one more small copy, as for the percentiles
-            out.update((name, np.ascontiguousarray(near[k])) for k, name in enumerate(_NEIGHBOR_NAMES))
-        if close:
-            import torch
-            back = to_host(torch.stack([c.view(torch.int64) if c.dtype.is_floating_point else c for c in close]))      # one small copy
-            out.update((name, np.ascontiguousarray(back[j]).view(np.float64 if "distance" in name else np.int64))
-                       for j, name in enumerate(near_names))
-        if spot is not None:
-            out["spot_count"] = to_host(spot)
-        return out
-    host_lbl = lbl.cpu().numpy() if lbl_t else lbl
-    raw = _measure_raw_host(host_lbl, img.cpu().numpy() if img_t else img, **more)
-    contacts = None if neighbors is None else _label_contacts_host(host_lbl, neighbors, True)
-    spot = None if spots is None else _spot_counts(raw["label"], host_lbl, spots.cpu().numpy() if R.is_torch(spots) else spots)
-    if not as_tensors:
-        out = _measure_columns(raw, nd, channel_axis, qs)
-        if contacts is not None:
-            out.update(zip(_NEIGHBOR_NAMES, _neighbor_columns(out["label"], *contacts)))
-        if near_names:
-            out.update(zip(near_names, _proximity_columns(raw["label"], raw["csum"], raw["area"], near_k, near_r, near_r2, near_spacing)))
-        if spot is not None:
-            out["spot_count"] = spot
-        return out
-    # the host table as tensors where the labels are (or on `device`): the packed raw columns make the trip
-    import torch
-    where = torch.device(device) if device is not None else (lbl.device if lbl_t else torch.device("cpu"))
-    packed = torch.as_tensor(_measure_pack(raw), device=where)
-    sum_dtype = mm_dtype = None
-    if img is not None:
-        name = str(img.dtype)[6:] if img_t else img.dtype.name
-        floating = name.startswith("float") or name.startswith("bfloat")
-        sum_dtype, mm_dtype = ("float64", name) if floating else ("int64", "int64")
-    back = _measure_unpack(packed, nd, C, sum_dtype, mm_dtype, shape, hull)
-    if qs:
-        back["pct"] = torch.as_tensor(raw["pct"], device=where)
-    out = _measure_columns(back, nd, channel_axis, qs)
-    if contacts is not None:
-        out.update(zip(_NEIGHBOR_NAMES, _neighbor_columns(out["label"], *[torch.as_tensor(c, device=where) for c in contacts])))
+            image, spots = (R.to_device_tensor(x, raw["label"].device) for x in (lbl, spots))
+    else:
+        image = lbl.cpu().numpy() if lbl_t else lbl
+        raw = _measure_raw_host(image, img.cpu().numpy() if img_t else img, **more)
+        contacts = None if neighbors is None else _label_contacts_host(image, neighbors, True)
+        spots = spots.cpu().numpy() if R.is_torch(spots) else spots
+    # the optional column families, in the raw columns' kind and in the table's order
+    extras = [] if contacts is None else list(zip(_NEIGHBOR_NAMES, _neighbor_columns(raw["label"], *contacts)))
     if near_names:
-        close = _proximity_columns(raw["label"], raw["csum"], raw["area"], near_k, near_r, near_r2, near_spacing)
-        out.update((name, torch.as_tensor(c, device=where)) for name, c in zip(near_names, close))
-    if spot is not None:
-        out["spot_count"] = torch.as_tensor(spot, device=where)
+        extras += zip(near_names, _proximity_columns(raw["label"], raw["csum"], raw["area"], near_k, near_r, near_r2, near_spacing))
+    if spots is not None:
+        extras.append(("spot_count", _spot_counts(raw["label"], image, spots)))
+    if R.is_torch(raw["label"]) != bool(as_tensors):
+        # the table changes its kind (R.table_exit): the packed raw columns, pct and one block of all extra columns make the trip
+        o = R.ops(raw["label"])
+        schema = _measure_schema(nd, C, None if img is None else R.dtype_name(raw["min"]), shape, hull)
+        block = o.cat([_as_bits(o, c).reshape(1, -1) for _, c in extras]) if extras else None
+        packed, pct, block = R.table_exit([_measure_pack(raw, schema), raw.get("pct"), block], as_tensors, lbl, device)
+        raw = _measure_unpack(packed, schema)
+        if qs:
+            raw["pct"] = pct
+        extras = [(name, _from_bits(R.ops(block), block[j], R.dtype_name(c))) for j, (name, c) in enumerate(extras)]
+    out = _measure_columns(raw, nd, channel_axis, qs)
+    out.update(extras)
     return out
 
 
@@ -1667,27 +1579,17 @@ def _label_contacts_device(lbl, connectivity, background, device=None, runs=None
     return R.original_labels(keys >> 32, ids), R.original_labels(keys & 0xFFFFFFFF, ids), counts
 
 
-def _int64_ops(x):
-    """(concatenate, searchsorted, zeros like x of a length, add-at in place, stable argsort) for numpy arrays or tensors, after x"""
-    if R.is_torch(x):
-        import torch
-        return (torch.cat, torch.searchsorted, lambda n: torch.zeros(n, dtype=torch.int64, device=x.device),
-                lambda out, at, v: out.index_add_(0, at, v), lambda k: torch.sort(k, stable=True)[1])
-    return (np.concatenate, np.searchsorted, lambda n: np.zeros(n, np.int64), lambda out, at, v: np.add.at(out, at, v),
-            lambda k: np.argsort(k, kind="stable"))
-
-
 def _symmetric_contacts(a, b, contacts, present):
     """the plain table listed both ways, sorted by (label_a, label_b), and the CSR offsets of the labels `present` (ascending, > 0):
     the rows of present[i] are offsets[i] : offsets[i + 1]; the rows of label_a = 0 come before offsets[0]"""
-    cat, searchsorted, zeros, _, argsort = _int64_ops(a)
-    sa, sb, sc = cat([a, b]), cat([b, a]), cat([contacts, contacts])
+    o = R.ops(a)
+    sa, sb, sc = o.cat([a, b]), o.cat([b, a]), o.cat([contacts, contacts])
     # two stable sorts, by label_b and then by label_a: no key of two ids has to fit 64 bits
-    order = argsort(sb)
-    order = order[argsort(sa[order])]
+    order = o.stable_argsort(sb)
+    order = order[o.stable_argsort(sa[order])]
     sa, sb, sc = sa[order], sb[order], sc[order]
-    offsets = zeros(len(present) + 1)
-    offsets[:len(present)] = searchsorted(sa, present)
+    offsets = o.zeros_i64(len(present) + 1)
+    offsets[:len(present)] = o.searchsorted(sa, present)
     offsets[len(present):] = len(sa)
     return sa, sb, sc, offsets
 
@@ -1696,9 +1598,10 @@ def _neighbor_columns(label, a, b, contacts):
     """(neighbors, contact_objects, contact_background) of the objects `label` (ascending, all > 0) from the plain contact table with
     the background's pairs: the number of rows an object shares with another object, the contacts of those rows, and the contacts of
     its row with 0"""
-    _, searchsorted, zeros, add_at, _ = _int64_ops(label)
+    o = R.ops(label)
+    searchsorted, add_at = o.searchsorted, o.add_at
     n = len(label)
-    neighbors, objects, bg = zeros(n), zeros(n), zeros(n)
+    neighbors, objects, bg = o.zeros_i64(n), o.zeros_i64(n), o.zeros_i64(n)
     if len(a):
         with_bg = a == 0
         both = ~with_bg
@@ -1745,9 +1648,10 @@ def label_contacts(lbl, connectivity=1, *, background=False, symmetric=False, de
     Objects "within a gap of d pixels" of each other are label_contacts(expand_labels(lbl, d / 2)); there is no distance argument.
     The objects near an object by centroid, with their distances, are point_neighbors'.
 
-    Routing: DESIGN.md section 3p, like measure_labels (exception 4 there): the columns are numpy arrays whatever the input's kind,
-    which the device route reads back in one copy; as_tensors=True makes them tensors, on the device for the device route, else where
-    the labels are or on `device`.  The host code is numpy: per forward offset two shifted slices and np.unique.  The device route
+    Routing: DESIGN.md section 3p, like measure_labels (exception 4 there, R.table_exit): the columns are numpy arrays whatever the
+    input's kind, which the device route reads back with one synchronisation; as_tensors=True makes them tensors, on the device for the
+    device route, else where the labels are or on `device`.  The host code is numpy: per forward offset two shifted slices and
+    np.unique.  The device route
     takes bool and integer images and equals the host result exactly (csrc/label_contacts.hip: a tile of labels with a halo of 1 in
     local memory, runs of equal pairs combined within a wave, a radix sort and a reduce-by-key; integers only, the same bits from call
     to call; the input is not written).  Ids beyond int32, or sparse huge ids, are compacted in ascending order for the call and mapped
@@ -1773,17 +1677,7 @@ def label_contacts(lbl, connectivity=1, *, background=False, symmetric=False, de
         present = _labels_present(lbl if taken else (host.astype(np.uint8) if host.dtype.kind == "b" else host), taken, device)
         cols = _symmetric_contacts(*cols, present)
         names += ("offsets",)
-    if taken and not as_tensors:
-        import torch
-        from .utils import to_host
-        m = len(cols[0])
-        flat = to_host(torch.cat([c.reshape(-1) for c in cols]))           # one copy
-        cols = [np.ascontiguousarray(flat[k * m:(k + 1) * m]) for k in range(3)] + ([np.ascontiguousarray(flat[3 * m:])] if symmetric else [])
-    elif not taken and as_tensors:
-        import torch
-        where = torch.device(device) if device is not None else (lbl.device if is_t else torch.device("cpu"))
-        cols = [torch.as_tensor(np.ascontiguousarray(c), device=where) for c in cols]
-    return dict(zip(names, cols))
+    return dict(zip(names, R.table_exit(cols, as_tensors, lbl, device)))
 
 
 # ----------------------------------------------------------------------------- point neighbours: the nearest points, the points within a radius
@@ -1982,8 +1876,9 @@ def point_neighbors(points, k=None, radius=None, *, queries=None, spacing=1, cou
         count_only=True   counts (m,) int64, the lengths of those rows; the lists are not made
 
     Routing: DESIGN.md section 3p, like label_contacts: numpy or host input without device= runs the host code, a tensor on a HIP
-    device or device= the kernels; the columns are numpy arrays (the device route reads them back with one synchronisation) unless
-    as_tensors=True, which makes them tensors -- on the device for the device route, else where the points are or on `device`.  The
+    device or device= the kernels; the columns leave as measure_labels' do (exception 4 there, R.table_exit): numpy arrays, which the
+    device route reads back with one synchronisation, unless as_tensors=True, which makes them tensors -- on the device for the device
+    route, else where the points are or on `device`.  The
     host code asks scipy.spatial.cKDTree for candidates only (a few more than k, doubled while ties or near-ties reach the last of
     them; the ball of radius * (1 + 2^-40)) and recomputes d2, the order and the radius test by the definition.  The device route
     (csrc/point_neighbors.hip) sorts the points into a uniform grid of about two points per cell and walks the
@@ -2027,14 +1922,11 @@ def point_neighbors(points, k=None, radius=None, *, queries=None, spacing=1, cou
             cols = [_point_neighbors_device(P, Q, 1, None, r2)]
         elif k is not None:
             idx, d2 = _point_neighbors_device(P, Q, 0, k, r2)
-            cols = [idx, _tensor_sqrt(d2)]
+            cols = [idx, R.ops(d2).sqrt(d2)]
         else:
             offsets, idx, d2 = _point_neighbors_device(P, Q, 2, None, r2)
-            cols = [offsets, idx, _tensor_sqrt(d2)]
-        if not as_tensors:
-            from .utils import to_host_many
-            cols = to_host_many(cols)                                       # one synchronisation
-        return dict(zip(names, cols))
+            cols = [offsets, idx, R.ops(d2).sqrt(d2)]
+        return dict(zip(names, R.table_exit(cols, as_tensors)))
     hP = P.cpu().numpy() if is_t else P
     hQ = hP if own else (Q.cpu().numpy() if R.is_torch(Q) else Q)
     if count_only:
@@ -2045,8 +1937,4 @@ def point_neighbors(points, k=None, radius=None, *, queries=None, spacing=1, cou
     else:
         counts, idx, d2 = _within_host(hP, hQ, own, radius, r2, False)
         cols = [np.concatenate([np.zeros(1, np.int64), np.cumsum(counts, dtype=np.int64)]), idx, np.sqrt(d2)]
-    if as_tensors:
-        import torch
-        where = points.device if is_t else torch.device("cpu")
-        cols = [torch.as_tensor(np.ascontiguousarray(c), device=where) for c in cols]
-    return dict(zip(names, cols))
+    return dict(zip(names, R.table_exit(cols, as_tensors, points)))

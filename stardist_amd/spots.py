@@ -356,16 +356,10 @@ def _peaks(img, is_t, on_device, device, labels, args, return_table, as_tensors)
         t = R.to_device_tensor(img, device)
         lab = None if labels is None else _labels_device(labels, img.shape, t.device)
         cols = _peaks_device(t, lab, d, b, t_abs, t_rel, per_label, num_peaks)
-        if not as_tensors:
-            from .utils import to_host_many
-            cols = to_host_many(cols if return_table else cols[:1])          # one synchronisation
     else:
         a = img.cpu().numpy() if is_t else img
         cols = _peaks_host(a, None if labels is None else _labels_host(labels, img.shape), d, b, t_abs, t_rel, per_label, num_peaks)
-        if as_tensors:
-            import torch
-            where = torch.device(device) if device is not None else (img.device if is_t else torch.device("cpu"))
-            cols = [torch.as_tensor(np.ascontiguousarray(c), device=where) for c in cols]
+    cols = R.table_exit(cols if return_table else cols[:1], as_tensors, img, device)         # without the table only the coordinates travel
     return dict(zip(("coords", "values", "labels"), cols)) if return_table else cols[0]
 
 
@@ -397,9 +391,10 @@ def peak_local_max(img, min_distance=1, threshold_abs=None, threshold_rel=None, 
     image" rule is replaced by rule 1 -- a constant image has no peak under the default threshold and, with a lower threshold_abs and
     no border, exactly one, at index 0.
 
-    Routing: DESIGN.md section 3p by the image; labels that are elsewhere are moved to it.  The columns are numpy arrays (the device
-    route reads them back with one synchronisation) unless as_tensors=True, which makes them tensors -- on the device for the device
-    route, else where the image is or on `device`.  The device route (csrc/spots.hip) reduces lo and hi and forms thr on the device,
+    Routing: DESIGN.md section 3p by the image; labels that are elsewhere are moved to it.  The columns leave as measure_labels' do
+    (exception 4 there, R.table_exit): numpy arrays, which the device route reads back with one synchronisation, unless
+    as_tensors=True, which makes them tensors -- on the device for the device route, else where the image is or on `device`.  The
+    device route (csrc/spots.hip) reduces lo and hi and forms thr on the device,
     tests every pixel in tiles with the window's halo in LDS while that fits in 48 KiB (peak_window_in_lds; 2D with one d: d <= 36)
     and from global memory beyond, appends peaks with one integer atomic per wave, sorts 64-bit keys (value key, index) and applies
     the cuts; integers and comparisons only, so the same bits from call to call.  One scalar comes to the host, the number of peaks

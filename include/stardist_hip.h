@@ -910,6 +910,38 @@ int sd_peak_local_max_device(const void* d_in, int dtype, int nd, long long n0, 
 int sd_peaks_emit_device(const void* d_in, int dtype, int nd, long long n0, long long n1, long long n2, const int32_t* d_labels,
                          const uint64_t* d_keys, long long count, int64_t* d_coords, void* d_values, int32_t* d_out_labels, void* stream);
 
+/* Rank filters and grey morphology (stardist_amd.rank_filters; the per-element rules are csrc/rank_filter.h's).
+ * Images as for spot detection: nd = 2 or 3 axes of extents n0, n1, n2 (n0 = 1 for nd = 2), at most 2^32 - 1 pixels, dtype 0 uint8
+ * (bool images travel as uint8), 1 uint16, 2 float32; never written.  The output has the image's dtype.  mode: 0 reflect, 1 nearest,
+ * 2 mirror, 3 constant -- scipy.ndimage's index rules, for windows longer than the axis as well; cval (mode 3) must be a value of the
+ * dtype and not NaN.  Along an axis a window of `size` elements starts size / 2 + origin elements before the output position
+ * (scipy's origin; 0 <= size / 2 + origin < size).  A window that covers a NaN gives NaN; -0.0 sorts below +0.0.  Window lengths go
+ * up to 1025 per axis, footprints up to 4096 elements.  No atomics, no read-back, no synchronisation: the same bits from call to call.
+ *
+ * sd_minmax_box_device: minimum_filter (is_max = 0) or maximum_filter (is_max = 1) under a box: h_size and h_origin (host, 3 ints,
+ * z y x; a 2D image has size 1 on axis 0), one separable pass per axis whose size is not 1, in the order 0, 1, 2.  fuse_op applies to
+ * what the last pass would store, x, and the pixel r of d_ref (an image like d_in): 0 x, 1 r - x, 2 x - r (both in the dtype; unsigned
+ * types wrap), 3 x ^ r (uint8 only) -- the top-hats' last step.  d_out receives the result, d_work (as large; needed for two or three
+ * passes) is scratch; d_in, d_ref, d_out and d_work are distinct.  A pass keeps its tile (1024 x 1 along the last axis, 32 x 64 along
+ * another) with its halo in LDS while that fits in 48 KiB -- always along the last axis, along another up to size 737 / 353 / 161 for
+ * uint8 / uint16 / float32 -- and reads global memory beyond.
+ *
+ * sd_rank_filter_device: the rank-th smallest (0-based, 0 <= rank < count) of the `count` pixels under a footprint of extents
+ * h_extent (host, 3 ints) whose true elements are h_offsets (host, count x 3 ints (dz, dy, dx), each inside its extent; copied to the
+ * device on the stream).  Selection is a bisection over the key's bits (8 / 16 / 32 walks over the window); rank 0 and count - 1 are
+ * one walk.  The tile (1 x 16 x 64, 3D 4 x 4 x 64) with the footprint's halo lives in LDS while it fits in 48 KiB, else the window is
+ * read from global memory.  d_out is not d_in.
+ *
+ * Both return -1 before any launch for a null pointer, nd outside 2 .. 3, a dtype, mode or fuse code outside its range, an extent < 1,
+ * more than 2^32 - 1 pixels, a window length outside 1 .. 1025, an origin outside its window, a cval that is NaN or no value of the
+ * dtype, count outside 1 .. 4096, a rank outside 0 .. count - 1, an offset outside its extent, buffers that are not distinct. */
+int sd_minmax_box_device(const void* d_in, int dtype, int nd, long long n0, long long n1, long long n2, const int* h_size,
+                         const int* h_origin, int is_max, int mode, double cval, int fuse_op, const void* d_ref, void* d_out,
+                         void* d_work, void* stream);
+int sd_rank_filter_device(const void* d_in, int dtype, int nd, long long n0, long long n1, long long n2, const int* h_extent,
+                          const int* h_origin, const int* h_offsets, int count, int rank, int mode, double cval, void* d_out,
+                          void* stream);
+
 /* The augmentation chain of a training batch (stardist_amd.augment.Compose.apply_device; the rules are csrc/augment.h's) in ONE launch:
  * d_x (B, *shape) float32 and d_y (B, *shape) int32, nd = 2 or 3 extents in h_shape, give d_out_x and d_out_y of the same shapes
  * (not the inputs): per sample FlipRot90 (always, as an index map), then Warp (flags bit 0; bit 1: mode 'reflect', else 'constant'),

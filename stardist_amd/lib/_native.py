@@ -135,7 +135,9 @@ SIGNATURES = {
     "sd_peak_local_max_device": (_i, [_vp, _i, _i] + [ctypes.c_longlong] * 3 + [_vp, _vp, _vp, _i, ctypes.c_double, _i, ctypes.c_double]
                                  + [ctypes.c_longlong] * 3 + [_vp, _vp, _vp]),
     "sd_peaks_emit_device": (_i, [_vp, _i, _i] + [ctypes.c_longlong] * 3 + [_vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp]),
-    "sd_augment_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "sd_minmax_box_device": (_i, [_vp, _i, _i] + [ctypes.c_longlong] * 3 + [_vp, _vp, _i, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp]),
+    "sd_rank_filter_device": (_i, [_vp, _i, _i] + [ctypes.c_longlong] * 3 + [_vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp]),
+    "sd_augment_batch_device":(_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "sd_star_dist2d_points_device": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "sd_star_dist3d_points_device": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _vp, _vp]),
     "sd_star_dist2d_points_host": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]),

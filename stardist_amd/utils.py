@@ -605,3 +605,5 @@ from .label_ops import (clear_border, find_boundaries, remove_small_objects, sel
                         calculate_extents, distance_transform, expand_labels, fill_label_holes, label_components,
                         label_contacts, measure_labels, point_neighbors)
 from .spots import gaussian_filter, difference_of_gaussians, peak_local_max, detect_spots  # noqa: E402, F401
+from .rank_filters import (minimum_filter, maximum_filter, median_filter, rank_filter, percentile_filter,  # noqa: E402, F401
+                           grey_opening, grey_closing, white_tophat, black_tophat)
